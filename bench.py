@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- training rays/s of the per-tile volume-rendering hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--path fused|ops] [--rays B] [--arith f32|h3|t16|t16s]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--path fused|ops] [--rays B] [--arith f32|h3|t16|t16s] [--dump-outputs DIR]
 
 `value` / `ms_per_step` are measured under the fastest F32-EQUIVALENT decoder arithmetic (render.FP32_EQUIV_ARITH; gradient
 error against the oracle ~5e-6 relative L2, reported live as `arith_evidence`); the reduced-precision "t16" step and the
@@ -24,6 +24,11 @@ non-zero if any rank failed.  --dry-run-cpu runs the same launcher and collectiv
 no kernels (the CPU tests use it; its line says "dry_run": true and is not a measurement).
 
 Prints ONE JSON line on rank 0.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step computed as DIR/<name>.npy (float32, < 64 MB in
+all): the loss it returned (and the ray gradients with --pose-grads), the decoder parameters it updated and a fixed, seeded sample
+of the hash table it updated; for configs4-render, a fixed, seeded sample of the last frame's pixels.  Inputs depend on the
+arguments only, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -85,7 +90,29 @@ def parse():
                          "T_left * background branch, --samples fg + --samples bg samples per ray, one merged loss, one Adam step; "
                          "configs2: + sphere-shell occupancy at log2dim 7 and a bf16 table (fp32 master + fused sparse Adam); "
                          "configs4-render: 4 tiles per GPU + background, one 1920x1080 novel view per step (render rays/s)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy (rank 0; see the module docstring)")
     return ap.parse_args()
+
+
+DUMP_SAMPLE = 1 << 20   # entries of a sampled output (4 MB in float32)
+
+
+def seeded_rows(x, n, seed=0):
+    """A fixed sample of n rows of x (all rows if it has no more): the same rows for the same shape on every run."""
+    if x.shape[0] <= n:
+        return x
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randint(x.shape[0], (n,), generator=g).sort().values
+    return x[idx.to(x.device)]
+
+
+def dump_outputs(outdir, arrays):
+    """arrays: name -> tensor.  Each lands in outdir/<name>.npy as float32."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a.detach().to(torch.float32).cpu().numpy())
 
 
 def launch_ranks(args):
@@ -289,10 +316,10 @@ def psnr_vs_oracle(samples, B=2048, log2_T=15):
     return 10.0 * float(np.log10(255.0 ** 2 / (mse + 1e-8)))
 
 
-def time_render(args, world, rank, dev, steps, warmup):
+def time_render(args, world, rank, dev, steps, warmup, dump=None):
     """configs[4] render leg: 4 tiles per GPU (admm_trainer.py:74-83 round-robin), background shells, one 1920x1080 view
     per step through the multi-tile renderer (rendering.py:286-544 counterpart).  -> (seconds for `steps` frames, MAX over ranks;
-    H, W, ntile, fraction of opaque pixels)."""
+    H, W, ntile, fraction of opaque pixels).  dump: directory for a fixed sample of the last timed frame (dump_outputs)."""
     import tempfile
 
     from scanerf_amd import renderer as R
@@ -330,12 +357,18 @@ def time_render(args, world, rank, dev, steps, warmup):
     t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    if dump:
+        # the last timed frame: the same pixels of its four planes (diffuse, specular, depth, transparency)
+        g = torch.Generator().manual_seed(0)
+        px = torch.randint(H * W, (DUMP_SAMPLE // 2,), generator=g).sort().values.to(out[0].device)
+        dump_outputs(dump, {n: o.reshape(H * W, -1)[px] for n, o in zip(("diffuse", "specular", "depth", "transparency"), out)})
     return float(t.item()), H, W, ntile, float((out[3] < 0.5).float().mean())
 
 
 def bench_render(args, world, rank, dev):
     """`--workload configs4-render`: value = rendered rays (pixels) per second."""
-    elapsed, H, W, ntile, opaque = time_render(args, world, rank, dev, args.steps, args.warmup)
+    elapsed, H, W, ntile, opaque = time_render(args, world, rank, dev, args.steps, args.warmup,
+                                               dump=args.dump_outputs if rank == 0 else None)
     if rank == 0:
         print(json.dumps({
             "metric": "novel-view render rays/s per GPU (128 samples, L=16 hash)", "value": world * H * W * args.steps / elapsed,
@@ -775,6 +808,9 @@ def main():
     if world != args.gpus and rank == 0:
         print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}: running {world} rank(s)", file=sys.stderr)
     if args.dry_run_cpu:
+        if args.dump_outputs:
+            print("bench.py: --dump-outputs needs the kernels; --dry-run-cpu runs none", file=sys.stderr)
+            sys.exit(2)
         return dry_run_cpu(args, world, rank)
     torch.cuda.set_device(local)
     rccl_error = None
@@ -862,12 +898,20 @@ def main():
     t0 = time.perf_counter()
     for i in range(args.steps):
         mi, oi = models[i % ntile], dec_opts[i % ntile]
-        step_fn(mi, oi, rays_o, rays_d, target, S, step0 + args.warmup + i, timer=timer) if timer else \
+        res = step_fn(mi, oi, rays_o, rays_d, target, S, step0 + args.warmup + i, timer=timer) if timer else \
             step_fn(mi, oi, rays_o, rays_d, target, S, step0 + args.warmup + i)
         if (i + 1) % SYN_ITERS == 0:
             admm.exchange(se3)
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # the last timed step: what it returned, and the parameters of the tile it stepped (the side timings below step them again)
+        res = res if isinstance(res, tuple) else (res,)
+        outs = {"loss": res[0].reshape(1)}
+        if len(res) == 3:
+            outs.update(grad_rays_o=seeded_rows(res[1], DUMP_SAMPLE // 4), grad_rays_d=seeded_rows(res[2], DUMP_SAMPLE // 4))
+        outs.update(decoder_params=mi.decoder.params.reshape(-1), table_sample=seeded_rows(mi.features.reshape(-1), DUMP_SAMPLE))
+        dump_outputs(args.dump_outputs, outs)
     # consensus exchange timed on its own (it runs once per SYN_ITERS steps)
     sync()
     c0 = time.perf_counter()
