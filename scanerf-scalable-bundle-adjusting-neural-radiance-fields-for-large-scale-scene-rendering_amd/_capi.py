@@ -5,6 +5,7 @@ contiguous tensor of the expected dtype on a HIP device, the call raises.
 """
 import ctypes
 import os
+import types
 
 import torch
 
@@ -17,27 +18,82 @@ PARAMSIZE = 13994
 
 _lib = None
 
-# every symbol include/scanerf_hip.h declares
-SYMBOLS = [
-    "scanerf_last_error", "scanerf_abi_version", "scanerf_compute_ray_forward", "scanerf_compute_ray_backward",
-    "scanerf_ray_aabb_intersection", "scanerf_sample_points_grid", "scanerf_sample_insideout_block",
-    "scanerf_background_sampling", "scanerf_adam_step", "scanerf_adam_step_fp16", "scanerf_embedding_bg_forward",
-    "scanerf_embedding_bg_backward", "scanerf_embedding_forward", "scanerf_embedding_backward",
-    "scanerf_render_workspace_floats", "scanerf_pack_decoder", "scanerf_render_forward_packed",
-    "scanerf_embedding_bg_forward_ex", "scanerf_embedding_bwd_workspace_bytes",
-    "scanerf_embedding_bg_backward_binned", "scanerf_embedding_bg_backward_binned_adam", "scanerf_render_backward_grid", "scanerf_render_backward",
-    "scanerf_sort_tracing_blocks", "scanerf_render_forward_packed_plan", "scanerf_render_forward_plan_supported", "scanerf_ray_grad_epilogue", "scanerf_photometric_loss_scratch_floats", "scanerf_photometric_loss_grad", "scanerf_render_scatter_workspace_bytes", "scanerf_render_scatter_plan", "scanerf_render_scatter_accumulate", "scanerf_render_scatter_accumulate_adam", "scanerf_render_scatter_accumulate_adam2", "scanerf_photometric_loss_grad_fgbg",
-    "scanerf_ray_block_intersection", "scanerf_render_sample_points", "scanerf_prepare_points", "scanerf_pts_inference",
-    "scanerf_accumulate_color", "scanerf_render_inverse_z_sampling", "scanerf_bg_pts_inference_v2",
-    "scanerf_update_outgoing_bidx", "scanerf_update_outgoing_bidx_v2", "scanerf_get_last_block",
-    "scanerf_ray_firsthit_block", "scanerf_process_occupied_grid", "scanerf_embedding_bg_point_grad", "scanerf_voxelize_mesh", "scanerf_ray_valid", "scanerf_compact_rays",
-    "scanerf_decoder_forward", "scanerf_decoder_backward_grid", "scanerf_decoder_backward", "scanerf_pts_inference_tracing",
-    "scanerf_table_grad_scatter_adam_rays", "scanerf_experiments_enabled", "scanerf_composite_forward", "scanerf_composite_backward",
-]
-
-# test / measurement entry points (include/scanerf_hip.h declares them, the default build exports them): NOT required --
-# a lean product build may drop csrc/h3_selftest.hip and the probes; their users (tests, bench.py's live ceiling) check first
-OPTIONAL_SYMBOLS = ["scanerf_h3_selftest", "scanerf_rec8_selftest", "scanerf_icache_sweep", "scanerf_gather_rate_probe"]
+# Every export include/scanerf_hip.h declares -- name: (return type, argument types, required) -- one letter per C type:
+#   P  any pointer, array or scanerf_stream_t     I  int        U  unsigned       F  float
+#   Z  size_t                                     L  int64_t / long long          S  const char * (return only)
+# lib() sets each export's argtypes / restype from this table; tests/test_capi_cpu.py checks it against the header.
+# OPT: test / measurement entry points, NOT required -- a lean product build may drop csrc/h3_selftest.hip and the probes;
+# their users (tests, bench.py's live ceiling) check has_symbol() first.
+REQ, OPT = True, False
+PROTOTYPES = {
+    "scanerf_last_error": ("S", "", REQ),
+    "scanerf_abi_version": ("I", "", REQ),
+    "scanerf_experiments_enabled": ("I", "", REQ),
+    "scanerf_compute_ray_forward": ("I", "PPPPPIP", REQ),
+    "scanerf_compute_ray_backward": ("I", "PPPPPIIP", REQ),
+    "scanerf_ray_aabb_intersection": ("I", "PPPPPIIP", REQ),
+    "scanerf_sample_points_grid": ("I", "PPPPPPPPIIP", REQ),
+    "scanerf_sample_insideout_block": ("I", "PPIIPPFPPPIP", REQ),
+    "scanerf_background_sampling": ("I", "PPPIFIP", REQ),
+    "scanerf_adam_step": ("I", "PPPPFFFFILIP", REQ),
+    "scanerf_adam_step_fp16": ("I", "PPPPFFFFILIP", REQ),
+    "scanerf_embedding_bg_forward": ("I", "PPPPIIIIP", REQ),
+    "scanerf_embedding_bg_backward": ("I", "PPPPPPIIIP", REQ),
+    "scanerf_embedding_bwd_workspace_bytes": ("Z", "III", REQ),
+    "scanerf_embedding_bg_backward_binned": ("I", "PPPPIIIIPZIP", REQ),
+    "scanerf_embedding_bg_backward_binned_adam": ("I", "PPPIIIIPZPPPPIPFFFFIIP", REQ),
+    "scanerf_table_grad_scatter_adam_rays": ("I", "PPIPPPIIPPPIIPPPIPZPPPPIPFFFFIIP", REQ),
+    "scanerf_embedding_forward": ("I", "PPPPPPIIIP", REQ),
+    "scanerf_embedding_backward": ("I", "PPPPPPPPIIIP", REQ),
+    "scanerf_render_workspace_floats": ("I", "", REQ),
+    "scanerf_pack_decoder": ("I", "PPPP", REQ),
+    "scanerf_render_forward_packed": ("I", "PPPPPIPPPPPPPPIIIP", REQ),
+    "scanerf_render_forward_packed_plan": ("I", "PPPPPIPPPPPPPPPIIIPZP", REQ),
+    "scanerf_render_forward_plan_supported": ("I", "III", REQ),
+    "scanerf_render_backward_grid": ("I", "I", REQ),
+    "scanerf_render_backward": ("I", "PPPPPIPPPPPPPPPPPPPPPPPZPIIIP", REQ),
+    "scanerf_render_scatter_workspace_bytes": ("Z", "III", REQ),
+    "scanerf_render_scatter_plan": ("I", "PPPPPPIIIPZP", REQ),
+    "scanerf_render_scatter_accumulate": ("I", "PIIIPZP", REQ),
+    "scanerf_render_scatter_accumulate_adam": ("I", "PPPPIPFFFFIIIIPZP", REQ),
+    "scanerf_render_scatter_accumulate_adam2": ("I", "PPPPIPFFFFIIIIPZIPZP", REQ),
+    "scanerf_ray_valid": ("I", "PPIIP", REQ),
+    "scanerf_compact_rays": ("I", "PIIPPPPPPPPPPPPP", REQ),
+    "scanerf_ray_grad_epilogue": ("I", "PPPPPPPPIIP", REQ),
+    "scanerf_composite_forward": ("I", "PPPPPPPPPIIIP", REQ),
+    "scanerf_composite_backward": ("I", "PPPPPPPPPPPPPPPIIIP", REQ),
+    "scanerf_photometric_loss_scratch_floats": ("I", "", REQ),
+    "scanerf_photometric_loss_grad": ("I", "PPPFPPPIP", REQ),
+    "scanerf_photometric_loss_grad_fgbg": ("I", "PPPPPFPPPPIP", REQ),
+    "scanerf_h3_selftest": ("I", "PPPPPPP", OPT),
+    "scanerf_icache_sweep": ("I", "P", OPT),
+    "scanerf_gather_rate_probe": ("I", "PLIIPP", OPT),
+    "scanerf_rec8_selftest": ("I", "PPPPPIPPP", OPT),
+    "scanerf_embedding_bg_point_grad": ("I", "PPPPPIIIP", REQ),
+    "scanerf_embedding_bg_forward_ex": ("I", "PPPPIIIIIIP", REQ),
+    "scanerf_ray_block_intersection": ("I", "PPPPPIIP", REQ),
+    "scanerf_render_sample_points": ("I", "PPPPPPPPPPPPPIIIIP", REQ),
+    "scanerf_prepare_points": ("I", "PPPPIIIIP", REQ),
+    "scanerf_pts_inference": ("I", "PPPPPPPPPPPPPPPPIIIIIP", REQ),
+    "scanerf_pts_inference_tracing": ("I", "PPPPPPPPPPPPPPPPPIIIIIP", REQ),
+    "scanerf_accumulate_color": ("I", "PPPPPPPPIIIP", REQ),
+    "scanerf_render_inverse_z_sampling": ("I", "PPPFIIIIP", REQ),
+    "scanerf_bg_pts_inference_v2": ("I", "PPPPIPPPPPPPPIIIIIP", REQ),
+    "scanerf_update_outgoing_bidx": ("I", "PPPPPPPPFIIIP", REQ),
+    "scanerf_update_outgoing_bidx_v2": ("I", "PPPPPIIP", REQ),
+    "scanerf_sort_tracing_blocks": ("I", "PPIIP", REQ),
+    "scanerf_get_last_block": ("I", "PPPIIP", REQ),
+    "scanerf_ray_firsthit_block": ("I", "PPPPPPPPPPIIP", REQ),
+    "scanerf_process_occupied_grid": ("I", "IIPPPPPPIP", REQ),
+    "scanerf_voxelize_mesh": ("I", "PPIIPPPPIPPP", REQ),
+    "scanerf_decoder_forward": ("I", "PIPIPPPPPLP", REQ),
+    "scanerf_decoder_backward_grid": ("I", "L", REQ),
+    "scanerf_decoder_backward": ("I", "PIPIPPPPPPPIPIPPLP", REQ),
+}
+SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if required]
+OPTIONAL_SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if not required]
+CTYPES = {"P": ctypes.c_void_p, "I": ctypes.c_int, "U": ctypes.c_uint, "F": ctypes.c_float, "Z": ctypes.c_size_t,
+          "L": ctypes.c_int64, "S": ctypes.c_char_p}
 
 
 def has_symbol(name):
@@ -54,20 +110,36 @@ ARITH_F32, ARITH_H3, ARITH_T16, ARITH_T16S = 0, 1, 2, 3
 T16_FAMILY = (ARITH_T16, ARITH_T16S)   # backward on 16-sample tiles: x-stash, plan counted by the forward, in-kernel pose path
 
 
+def _typed(fn, name, ret, args):
+    """fn with the prototype's types; a call with the wrong number of arguments raises TypeError (ctypes itself passes
+    extra arguments through)."""
+    fn.restype = CTYPES[ret]
+    fn.argtypes = [CTYPES[a] for a in args]
+    n = len(args)
+
+    def call(*a):
+        if len(a) != n:
+            raise TypeError(f"{name}() takes {n} arguments ({len(a)} given)")
+        return fn(*a)
+    call.__name__ = name
+    return call
+
+
 def lib():
-    """Load the HIP library or fail loudly (no fallback)."""
+    """Load the HIP library or fail loudly (no fallback): a namespace of the exports in PROTOTYPES, typed; an optional
+    export the build does not have is absent (has_symbol)."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(
                 f"scanerf: HIP library not built: {LIB_PATH} is missing. "
                 "Run `python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc, gfx950).")
-        l = ctypes.CDLL(LIB_PATH)
-        l.scanerf_last_error.restype = ctypes.c_char_p
-        l.scanerf_embedding_bwd_workspace_bytes.restype = ctypes.c_size_t
-        l.scanerf_render_scatter_workspace_bytes.restype = ctypes.c_size_t
-        for name in SYMBOLS:
-            if not hasattr(l, name):
+        so = ctypes.CDLL(LIB_PATH)
+        l = types.SimpleNamespace()
+        for name, (ret, args, required) in PROTOTYPES.items():
+            if hasattr(so, name):
+                setattr(l, name, _typed(getattr(so, name), name, ret, args))
+            elif required:
                 raise RuntimeError(f"scanerf: {LIB_PATH} does not export {name}")
         _lib = l
         st = audit_state()
@@ -131,7 +203,7 @@ def check(status, what):
 
 
 def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return torch.cuda.current_stream().cuda_stream
 
 
 _DT = {torch.float32: "f32", torch.int32: "i32", torch.bool: "bool", torch.uint8: "u8", torch.float16: "f16",
@@ -144,7 +216,7 @@ def dev_ptr(t, dtypes, name, allow_none=False):
     non-contiguous output silently receives nothing)."""
     if t is None:
         if allow_none:
-            return ctypes.c_void_p(0)
+            return None
         raise RuntimeError(f"scanerf: {name} is None")
     if not isinstance(t, torch.Tensor):
         raise RuntimeError(f"scanerf: {name} must be a torch.Tensor, got {type(t).__name__}")
@@ -156,7 +228,7 @@ def dev_ptr(t, dtypes, name, allow_none=False):
         raise RuntimeError(f"scanerf: {name} has dtype {t.dtype}, expected {[_DT.get(d, d) for d in dtypes]}")
     if not t.is_contiguous():
         raise RuntimeError(f"scanerf: {name} must be contiguous")
-    return ctypes.c_void_p(t.data_ptr())
+    return t.data_ptr()
 
 
 def feat_dtype_code(t):

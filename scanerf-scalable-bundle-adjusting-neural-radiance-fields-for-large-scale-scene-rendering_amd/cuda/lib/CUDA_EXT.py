@@ -20,7 +20,7 @@ def compute_ray_forward(rays_o, rays_d, Ks, C2Ws, locs):
     B = rays_o.shape[0]
     check(lib().scanerf_compute_ray_forward(dev_ptr(rays_o, _f32, "rays_o"), dev_ptr(rays_d, _f32, "rays_d"),
                                             dev_ptr(Ks, _f32, "Ks"), dev_ptr(C2Ws, _f32, "C2Ws"),
-                                            dev_ptr(locs, _i32, "locs"), ctypes.c_int(B), stream()),
+                                            dev_ptr(locs, _i32, "locs"), B, stream()),
           "compute_ray_forward")
 
 
@@ -28,29 +28,25 @@ def compute_ray_backward(grad_rays_o, grad_rays_d, Ks, grad_C2Ws, locs):
     """compute_ray.h:16-21.  Per-ray adjoint (the reference's kernel indexes the incoming
     gradients by view, compute_ray_kernel.cu:71-72)."""
     B = grad_rays_o.shape[0]
-    check(lib().scanerf_compute_ray_backward(dev_ptr(grad_rays_o, _f32, "grad_rays_o"),
-                                             dev_ptr(grad_rays_d, _f32, "grad_rays_d"), dev_ptr(Ks, _f32, "Ks"),
-                                             dev_ptr(grad_C2Ws, _f32, "grad_C2Ws"), dev_ptr(locs, _i32, "locs"),
-                                             ctypes.c_int(B), ctypes.c_int(grad_C2Ws.shape[0]), stream()),
+    check(lib().scanerf_compute_ray_backward(dev_ptr(grad_rays_o, _f32, "grad_rays_o"), dev_ptr(grad_rays_d, _f32, "grad_rays_d"),
+                                             dev_ptr(Ks, _f32, "Ks"), dev_ptr(grad_C2Ws, _f32, "grad_C2Ws"),
+                                             dev_ptr(locs, _i32, "locs"), B, grad_C2Ws.shape[0], stream()),
           "compute_ray_backward")
 
 
 def ray_aabb_intersection(rays_o, rays_d, aabb_center, aabb_size, bounds):
     """helper.h:10-15: bounds [B,2] pre-filled by the caller (-1)."""
     check(lib().scanerf_ray_aabb_intersection(dev_ptr(rays_o, _f32, "rays_o"), dev_ptr(rays_d, _f32, "rays_d"),
-                                              dev_ptr(aabb_center, _f32, "aabb_center"),
-                                              dev_ptr(aabb_size, _f32, "aabb_size"), dev_ptr(bounds, _f32, "bounds"),
-                                              ctypes.c_int(rays_o.shape[0]), ctypes.c_int(1), stream()),
+                                              dev_ptr(aabb_center, _f32, "aabb_center"), dev_ptr(aabb_size, _f32, "aabb_size"),
+                                              dev_ptr(bounds, _f32, "bounds"), rays_o.shape[0], 1, stream()),
           "ray_aabb_intersection")
 
 
 def ray_aabb_intersection_v2(rays_o, rays_d, aabb_center, aabb_size, bounds):
     """helper.h:17-22: K boxes, bounds [B,K,2]."""
     check(lib().scanerf_ray_aabb_intersection(dev_ptr(rays_o, _f32, "rays_o"), dev_ptr(rays_d, _f32, "rays_d"),
-                                              dev_ptr(aabb_center, _f32, "aabb_center"),
-                                              dev_ptr(aabb_size, _f32, "aabb_size"), dev_ptr(bounds, _f32, "bounds"),
-                                              ctypes.c_int(rays_o.shape[0]), ctypes.c_int(aabb_center.shape[0]),
-                                              stream()),
+                                              dev_ptr(aabb_center, _f32, "aabb_center"), dev_ptr(aabb_size, _f32, "aabb_size"),
+                                              dev_ptr(bounds, _f32, "bounds"), rays_o.shape[0], aabb_center.shape[0], stream()),
           "ray_aabb_intersection_v2")
 
 
@@ -60,11 +56,9 @@ def sample_points_grid(rays_o, rays_d, z_vals, dists, block_corner, block_size, 
         raise RuntimeError(f"scanerf: log2dim must be int32 (the reference reinterprets it as int*), got {log2dim.dtype}")
     check(lib().scanerf_sample_points_grid(dev_ptr(rays_o, _f32, "rays_o"), dev_ptr(rays_d, _f32, "rays_d"),
                                            dev_ptr(z_vals, _f32, "z_vals"), dev_ptr(dists, _f32, "dists"),
-                                           dev_ptr(block_corner, _f32, "block_corner"),
-                                           dev_ptr(block_size, _f32, "block_size"),
+                                           dev_ptr(block_corner, _f32, "block_corner"), dev_ptr(block_size, _f32, "block_size"),
                                            dev_ptr(occupied_gird, (torch.bool, torch.uint8), "occupied_gird"),
-                                           dev_ptr(log2dim, _i32, "log2dim"), ctypes.c_int(rays_o.shape[0]),
-                                           ctypes.c_int(z_vals.shape[1]), stream()),
+                                           dev_ptr(log2dim, _i32, "log2dim"), rays_o.shape[0], z_vals.shape[1], stream()),
           "sample_points_grid")
 
 
@@ -78,28 +72,24 @@ def sample_points_contract(rays_o, rays_d, z_vals, block_corner, block_size, occ
 def sample_insideout_block(rays_o, rays_d, num_sample, num_sample_bg, block_center, block_size, far, z_vals,
                            z_vals_bg):
     """sample.h:9-17"""
-    check(lib().scanerf_sample_insideout_block(dev_ptr(rays_o, _f32, "rays_o"), dev_ptr(rays_d, _f32, "rays_d"),
-                                               ctypes.c_int(num_sample), ctypes.c_int(num_sample_bg),
-                                               dev_ptr(block_center, _f32, "block_center"),
-                                               dev_ptr(block_size, _f32, "block_size"), ctypes.c_float(far),
-                                               dev_ptr(z_vals, _f32, "z_vals"), dev_ptr(z_vals_bg, _f32, "z_vals_bg"),
-                                               ctypes.c_void_p(0), ctypes.c_int(rays_o.shape[0]), stream()),
+    check(lib().scanerf_sample_insideout_block(dev_ptr(rays_o, _f32, "rays_o"), dev_ptr(rays_d, _f32, "rays_d"), num_sample,
+                                               num_sample_bg, dev_ptr(block_center, _f32, "block_center"),
+                                               dev_ptr(block_size, _f32, "block_size"), far, dev_ptr(z_vals, _f32, "z_vals"),
+                                               dev_ptr(z_vals_bg, _f32, "z_vals_bg"), None, rays_o.shape[0], stream()),
           "sample_insideout_block")
 
 
 def background_sampling_cuda(rays_o, rays_d, starts, bg_depth, z_vals, num_sample, sample_range):
     """sample.h:19-26 (rays are unused by the reference kernel too)."""
     check(lib().scanerf_background_sampling(dev_ptr(starts, _f32, "starts"), dev_ptr(bg_depth, _f32, "bg_depth"),
-                                            dev_ptr(z_vals, _f32, "z_vals"), ctypes.c_int(num_sample),
-                                            ctypes.c_float(sample_range), ctypes.c_int(rays_o.shape[0]), stream()),
+                                            dev_ptr(z_vals, _f32, "z_vals"), num_sample, sample_range, rays_o.shape[0], stream()),
           "background_sampling_cuda")
 
 
 def _adam(fn, name, params, grad_params, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, mdt):
     check(fn(dev_ptr(params, _f32, "params"), dev_ptr(grad_params, _f32, "grad_params"),
-             dev_ptr(exp_avg, mdt, "exp_avg"), dev_ptr(exp_avg_sq, mdt, "exp_avg_sq"), ctypes.c_float(lr),
-             ctypes.c_float(beta1), ctypes.c_float(beta2), ctypes.c_float(eps), ctypes.c_int(step),
-             ctypes.c_int64(params.shape[0]), ctypes.c_int(params.shape[1]), stream()), name)
+             dev_ptr(exp_avg, mdt, "exp_avg"), dev_ptr(exp_avg_sq, mdt, "exp_avg_sq"), lr, beta1, beta2, eps, step,
+             params.shape[0], params.shape[1], stream()), name)
 
 
 def adam_step_cuda(params, grad_params, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step):
@@ -141,9 +131,9 @@ def voxelize_mesh(_log2dim, block_corner, block_size, model_path, vis, init_out,
     scratch = torch.empty(6, dtype=torch.int32, device=dev)
     corner = (ctypes.c_float * 3)(*[float(x) for x in block_corner.detach().cpu().reshape(-1).tolist()])
     size = (ctypes.c_float * 3)(*[float(x) for x in block_size.detach().cpu().reshape(-1).tolist()])
-    check(lib().scanerf_voxelize_mesh(dev_ptr(v, _f32, "vertices"), dev_ptr(f, _i32, "faces"), ctypes.c_int(v.shape[0]),
-                                      ctypes.c_int(f.shape[0]), (ctypes.c_int32 * 3)(*l2d), corner, size,
-                                      dev_ptr(gv, torch.bool, "vis"), ctypes.c_int(int(bool(init_out))),
+    check(lib().scanerf_voxelize_mesh(dev_ptr(v, _f32, "vertices"), dev_ptr(f, _i32, "faces"), v.shape[0],
+                                      f.shape[0], (ctypes.c_int32 * 3)(*l2d), corner, size,
+                                      dev_ptr(gv, torch.bool, "vis"), int(bool(init_out)),
                                       dev_ptr(go, torch.bool, "outside"), dev_ptr(scratch, _i32, "scratch"), stream()),
           "voxelize_mesh")
     if gv is not vis:

@@ -6,8 +6,6 @@ forward = scanerf_decoder_forward, backward = scanerf_decoder_backward (one laun
 f32-equivalent); x and its gradient are addressed in place with row stride 35 (features at column 0, direction at 32).
 There is no CPU path: CPU tensors raise (as every op of this package).
 """
-import ctypes
-
 import torch
 
 from . import _capi
@@ -18,7 +16,7 @@ _f32 = torch.float32
 
 
 def _off(t, floats):
-    return ctypes.c_void_p(t.data_ptr() + 4 * floats)
+    return t.data_ptr() + 4 * floats
 
 
 class _DecoderFn(torch.autograd.Function):
@@ -34,9 +32,9 @@ class _DecoderFn(torch.autograd.Function):
         sigma = torch.empty((N, 1), dtype=_f32, device=x.device)
         dif, spec, tint = (torch.empty((N, 3), dtype=_f32, device=x.device) for _ in range(3))
         check(lib().scanerf_decoder_forward(
-            dev_ptr(x, _f32, "x"), ctypes.c_int(35), _off(x, 32), ctypes.c_int(35), dev_ptr(packed.workspace, _f32, "workspace"),
+            dev_ptr(x, _f32, "x"), 35, _off(x, 32), 35, dev_ptr(packed.workspace, _f32, "workspace"),
             dev_ptr(sigma, _f32, "sigma"), dev_ptr(dif, _f32, "diffuse"), dev_ptr(spec, _f32, "specular"),
-            dev_ptr(tint, _f32, "tint"), ctypes.c_longlong(N), stream()), "decoder_forward")
+            dev_ptr(tint, _f32, "tint"), N, stream()), "decoder_forward")
         ctx.save_for_backward(x, wf)
         ctx.packed = packed
         return sigma, dif, spec, tint
@@ -48,15 +46,15 @@ class _DecoderFn(torch.autograd.Function):
         dev = x.device
         gx = torch.empty_like(x)
         gblob = torch.zeros(_capi.PARAMSIZE, dtype=_f32, device=dev)
-        nblk = lib().scanerf_decoder_backward_grid(ctypes.c_longlong(N))
+        nblk = lib().scanerf_decoder_backward_grid(N)
         dw_partial = torch.empty((nblk, _capi.PARAMSIZE), dtype=_f32, device=dev)
         keep = [None if t is None else t.contiguous().to(_f32) for t in (g_sigma, g_dif, g_spec, g_tint)]
         check(lib().scanerf_decoder_backward(
-            dev_ptr(x, _f32, "x"), ctypes.c_int(35), _off(x, 32), ctypes.c_int(35), dev_ptr(ctx.packed.workspace, _f32, "workspace"),
+            dev_ptr(x, _f32, "x"), 35, _off(x, 32), 35, dev_ptr(ctx.packed.workspace, _f32, "workspace"),
             dev_ptr(wf, _f32, "weight_feature"),
             *(dev_ptr(t, _f32, n, allow_none=True) for t, n in zip(keep, ("g_sigma", "g_diffuse", "g_specular", "g_tint"))),
-            dev_ptr(gx, _f32, "gx"), ctypes.c_int(35), _off(gx, 32), ctypes.c_int(35), dev_ptr(dw_partial, _f32, "dw_partial"),
-            dev_ptr(gblob, _f32, "grad_blob"), ctypes.c_longlong(N), stream()), "decoder_backward")
+            dev_ptr(gx, _f32, "gx"), 35, _off(gx, 32), 35, dev_ptr(dw_partial, _f32, "dw_partial"),
+            dev_ptr(gblob, _f32, "grad_blob"), N, stream()), "decoder_backward")
         return gx, gblob, None
 
 
@@ -75,9 +73,9 @@ class _DecoderPartsFn(torch.autograd.Function):
         sigma = torch.empty((N, 1), dtype=_f32, device=dev)
         dif, spec, tint = (torch.empty((N, 3), dtype=_f32, device=dev) for _ in range(3))
         check(lib().scanerf_decoder_forward(
-            dev_ptr(feats, _f32, "features"), ctypes.c_int(32), dev_ptr(dirs, _f32, "dirs"), ctypes.c_int(3),
+            dev_ptr(feats, _f32, "features"), 32, dev_ptr(dirs, _f32, "dirs"), 3,
             dev_ptr(packed.workspace, _f32, "workspace"), dev_ptr(sigma, _f32, "sigma"), dev_ptr(dif, _f32, "diffuse"),
-            dev_ptr(spec, _f32, "specular"), dev_ptr(tint, _f32, "tint"), ctypes.c_longlong(N), stream()), "decoder_forward")
+            dev_ptr(spec, _f32, "specular"), dev_ptr(tint, _f32, "tint"), N, stream()), "decoder_forward")
         ctx.save_for_backward(feats, dirs, wf)
         ctx.packed = packed
         return sigma, dif, spec, tint
@@ -89,15 +87,15 @@ class _DecoderPartsFn(torch.autograd.Function):
         # (directions that carry no gradient -- no pose refinement -- skip the harmonics' adjoint: d_dirs = NULL)
         gf, gd = torch.empty_like(feats), (torch.empty_like(dirs) if ctx.needs_input_grad[1] else None)
         gblob = torch.zeros(_capi.PARAMSIZE, dtype=_f32, device=dev)
-        nblk = lib().scanerf_decoder_backward_grid(ctypes.c_longlong(N))
+        nblk = lib().scanerf_decoder_backward_grid(N)
         dw_partial = torch.empty((nblk, _capi.PARAMSIZE), dtype=_f32, device=dev)
         keep = [None if t is None else t.contiguous().to(_f32) for t in (g_sigma, g_dif, g_spec, g_tint)]
         check(lib().scanerf_decoder_backward(
-            dev_ptr(feats, _f32, "features"), ctypes.c_int(32), dev_ptr(dirs, _f32, "dirs"), ctypes.c_int(3),
+            dev_ptr(feats, _f32, "features"), 32, dev_ptr(dirs, _f32, "dirs"), 3,
             dev_ptr(ctx.packed.workspace, _f32, "workspace"), dev_ptr(wf, _f32, "weight_feature"),
             *(dev_ptr(t, _f32, n, allow_none=True) for t, n in zip(keep, ("g_sigma", "g_diffuse", "g_specular", "g_tint"))),
-            dev_ptr(gf, _f32, "g_features"), ctypes.c_int(32), dev_ptr(gd, _f32, "g_dirs", allow_none=True), ctypes.c_int(3),
-            dev_ptr(dw_partial, _f32, "dw_partial"), dev_ptr(gblob, _f32, "grad_blob"), ctypes.c_longlong(N), stream()), "decoder_backward")
+            dev_ptr(gf, _f32, "g_features"), 32, dev_ptr(gd, _f32, "g_dirs", allow_none=True), 3,
+            dev_ptr(dw_partial, _f32, "dw_partial"), dev_ptr(gblob, _f32, "grad_blob"), N, stream()), "decoder_backward")
         return gf, gd, gblob, None
 
 

@@ -3,8 +3,6 @@
 Same names / positional order / in-place outputs as hashgrid/include/hashgrid.h:19-51 (encoder ops) and
 hashgrid/include/rendering.h:20-182 (the render-time ops of rendering.py's novel-view loop, second half of this file).
 """
-import ctypes
-
 import torch
 
 from ..._capi import check, dev_ptr, feat_dtype_code, lib, stream, workspace
@@ -24,9 +22,8 @@ def embedding_bg_forward_cuda(points, outputs, features, resolutions):
     features [L,T,2].  fp32 tables as in the reference; f16/bf16 tables are also accepted."""
     N, (L, T) = points.shape[0], features.shape[:2]
     check(lib().scanerf_embedding_bg_forward(dev_ptr(points, _f32, "points"), dev_ptr(outputs, _f32, "outputs"),
-                                             dev_ptr(features, _feat, "features"), _res(resolutions),
-                                             ctypes.c_int(N), ctypes.c_int(L), ctypes.c_int(T),
-                                             ctypes.c_int(feat_dtype_code(features)), stream()),
+                                             dev_ptr(features, _feat, "features"), _res(resolutions), N, L, T,
+                                             feat_dtype_code(features), stream()),
           "embedding_bg_forward_cuda")
 
 
@@ -46,13 +43,12 @@ def embedding_bg_backward_cuda(points, grad_in, grad_points, grad_features, feat
     N, (L, T) = points.shape[0], features.shape[:2]
     need = 0
     if grad_features is not None and N >= 4096 and TABLE_GRAD_ROUTE != "atomics":
-        need = lib().scanerf_embedding_bwd_workspace_bytes(ctypes.c_int(N), ctypes.c_int(L), ctypes.c_int(T))
+        need = lib().scanerf_embedding_bwd_workspace_bytes(N, L, T)
     if need:
         ws = workspace(points.device, need)
         check(lib().scanerf_embedding_bg_backward_binned(
-            dev_ptr(points, _f32, "points"), dev_ptr(grad_in, _f32, "grad_in"),
-            dev_ptr(grad_features, _f32, "grad_features"), _res(resolutions), ctypes.c_int(N), ctypes.c_int(L),
-            ctypes.c_int(T), ctypes.c_int(0), ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), ctypes.c_int(RECORD_FORMAT),
+            dev_ptr(points, _f32, "points"), dev_ptr(grad_in, _f32, "grad_in"), dev_ptr(grad_features, _f32, "grad_features"),
+            _res(resolutions), N, L, T, 0, ws.data_ptr(), ws.numel(), RECORD_FORMAT,
             stream()), "embedding_bg_backward_cuda(binned)")
         if grad_points is None:
             return
@@ -60,8 +56,7 @@ def embedding_bg_backward_cuda(points, grad_in, grad_points, grad_features, feat
     check(lib().scanerf_embedding_bg_backward(dev_ptr(points, _f32, "points"), dev_ptr(grad_in, _f32, "grad_in"),
                                               dev_ptr(grad_points, _f32, "grad_points", allow_none=True),
                                               dev_ptr(grad_features, _f32, "grad_features", allow_none=True),
-                                              dev_ptr(features, _f32, "features"), _res(resolutions),
-                                              ctypes.c_int(N), ctypes.c_int(L), ctypes.c_int(T), stream()),
+                                              dev_ptr(features, _f32, "features"), _res(resolutions), N, L, T, stream()),
           "embedding_bg_backward_cuda")
 
 
@@ -69,10 +64,8 @@ def embedding_forward_cuda(points, outputs, features, block_corner, block_size, 
     """hashgrid.h:19-25 (world-space box variant)."""
     N, (L, T) = points.shape[0], features.shape[:2]
     check(lib().scanerf_embedding_forward(dev_ptr(points, _f32, "points"), dev_ptr(outputs, _f32, "outputs"),
-                                          dev_ptr(features, _f32, "features"),
-                                          dev_ptr(block_corner, _f32, "block_corner"),
-                                          dev_ptr(block_size, _f32, "block_size"), _res(resolutions),
-                                          ctypes.c_int(N), ctypes.c_int(L), ctypes.c_int(T), stream()),
+                                          dev_ptr(features, _f32, "features"), dev_ptr(block_corner, _f32, "block_corner"),
+                                          dev_ptr(block_size, _f32, "block_size"), _res(resolutions), N, L, T, stream()),
           "embedding_forward_cuda")
 
 
@@ -82,17 +75,14 @@ def embedding_backward_cuda(points, grad_in, grad_points, grad_features, feature
     N, (L, T) = points.shape[0], features.shape[:2]
     check(lib().scanerf_embedding_backward(dev_ptr(points, _f32, "points"), dev_ptr(grad_in, _f32, "grad_in"),
                                            dev_ptr(grad_points, _f32, "grad_points", allow_none=True),
-                                           dev_ptr(grad_features, _f32, "grad_features"),
-                                           dev_ptr(features, _f32, "features"),
-                                           dev_ptr(block_corner, _f32, "block_corner"),
-                                           dev_ptr(block_size, _f32, "block_size"), _res(resolutions),
-                                           ctypes.c_int(N), ctypes.c_int(L), ctypes.c_int(T), stream()),
+                                           dev_ptr(grad_features, _f32, "grad_features"), dev_ptr(features, _f32, "features"),
+                                           dev_ptr(block_corner, _f32, "block_corner"), dev_ptr(block_size, _f32, "block_size"),
+                                           _res(resolutions), N, L, T, stream()),
           "embedding_backward_cuda")
 
 
 # ------------------------------------------------------------------ render-time ops (rendering.h:20-182)
 _i16, _i64, _bool = torch.int16, torch.int64, (torch.bool, torch.uint8)
-_I = ctypes.c_int
 
 
 # The 16-sample-tile inference kernel takes images whose three Gaussian-activated layers (blob floats [0, 2112): Spatial_MLP.mlp.0,
@@ -113,8 +103,8 @@ def _pack_images(params, images, folded=False):
             p[:, lo:hi] *= _FOLD_C
     ones = torch.ones(32, dtype=_f32, device=p.device)
     for b in range(p.shape[0]):
-        check(lib().scanerf_pack_decoder(ctypes.c_void_p(p[b].data_ptr()), dev_ptr(ones, _f32, "wf"),
-                                         ctypes.c_void_p(images[b].data_ptr()), stream()), "pack_decoder")
+        check(lib().scanerf_pack_decoder(p[b].data_ptr(), dev_ptr(ones, _f32, "wf"),
+                                         images[b].data_ptr(), stream()), "pack_decoder")
     return images
 
 
@@ -178,13 +168,13 @@ def ray_block_intersection(rays_o, rays_d, block_corners, block_sizes, intersect
     check(lib().scanerf_ray_block_intersection(dev_ptr(rays_o, _f32, "rays_o"), dev_ptr(rays_d, _f32, "rays_d"),
                                                dev_ptr(block_corners, _f32, "block_corners"),
                                                dev_ptr(block_sizes, _f32, "block_sizes"),
-                                               dev_ptr(intersections, _f32, "intersections"), _I(rays_d.shape[0]),
-                                               _I(block_corners.shape[0]), stream()), "ray_block_intersection")
+                                               dev_ptr(intersections, _f32, "intersections"), rays_d.shape[0],
+                                               block_corners.shape[0], stream()), "ray_block_intersection")
 
 
 def _S(z_vals, sample_major):
     """per-sample arrays: [B,S] (0, the reference's), [S,B] (1) or [B/32,S,32] (2) -- scanerf_hip.h `sample_major`"""
-    return _I(z_vals.shape[0] if (int(sample_major) & 3) == 1 else z_vals.shape[1])
+    return z_vals.shape[0] if (int(sample_major) & 3) == 1 else z_vals.shape[1]
 
 
 def sort_tracing_blocks(intersections):
@@ -193,7 +183,7 @@ def sort_tracing_blocks(intersections):
     if nb > 64:
         return torch.argsort(intersections[..., 0], dim=-1, stable=True).int().contiguous()
     order = torch.empty((B, nb), dtype=torch.int32, device=intersections.device)
-    check(lib().scanerf_sort_tracing_blocks(dev_ptr(intersections, _f32, "intersections"), dev_ptr(order, _i32, "order"), _I(B), _I(nb),
+    check(lib().scanerf_sort_tracing_blocks(dev_ptr(intersections, _f32, "intersections"), dev_ptr(order, _i32, "order"), B, nb,
                                             stream()), "sort_tracing_blocks")
     return order
 
@@ -206,15 +196,15 @@ def sample_points(rays_o, rays_d, block_corners, block_sizes, grid_occupied, gri
         dev_ptr(grid_starts, _i64, "grid_starts"), dev_ptr(grid_log2dim, _i32, "grid_log2dim"),
         dev_ptr(tracing_blocks, _i32, "tracing_blocks"), dev_ptr(intersections, _f32, "intersections"),
         dev_ptr(tracing_idx, _i32, "tracing_idx"), dev_ptr(z_start, _f32, "z_start"), dev_ptr(z_vals, _f32, "z_vals"),
-        dev_ptr(dists, _f32, "dists"), _I(rays_d.shape[0]), _S(z_vals, sample_major), _I(block_corners.shape[0]),
-        _I(int(sample_major)), stream()), "sample_points")
+        dev_ptr(dists, _f32, "dists"), rays_d.shape[0], _S(z_vals, sample_major), block_corners.shape[0],
+        int(sample_major), stream()), "sample_points")
 
 
 def prepare_points(z_vals, runing_mask, intersections, block_idxs, sample_major=False):
     check(lib().scanerf_prepare_points(dev_ptr(z_vals, _f32, "z_vals"), dev_ptr(runing_mask, _bool, "runing_mask"),
                                        dev_ptr(intersections, _f32, "intersections"),
-                                       dev_ptr(block_idxs, _i16, "block_idxs"), _I(intersections.shape[0]), _S(z_vals, sample_major),
-                                       _I(intersections.shape[1]), _I(int(sample_major)), stream()), "prepare_points")
+                                       dev_ptr(block_idxs, _i16, "block_idxs"), intersections.shape[0], _S(z_vals, sample_major),
+                                       intersections.shape[1], int(sample_major), stream()), "prepare_points")
 
 
 def pts_inference(rays_o, rays_d, z_vals, dists, block_idxs, features_tables, params, resolution, grid_occupied,
@@ -229,8 +219,8 @@ def pts_inference(rays_o, rays_d, z_vals, dists, block_idxs, features_tables, pa
         dev_ptr(grid_starts, _i64, "grid_starts"), dev_ptr(grid_log2dim, _i32, "grid_log2dim"),
         dev_ptr(block_corners, _f32, "block_corners"), dev_ptr(block_sizes, _f32, "block_sizes"),
         dev_ptr(diffuse, _f32, "diffuse"), dev_ptr(specular, _f32, "specular"), dev_ptr(alpha, _f32, "alpha"),
-        _I(rays_d.shape[0]), _S(z_vals, sample_major), _I(features_tables.shape[2]), _I(block_corners.shape[0]),
-        _I(int(sample_major) | _infer_flags(folded)), stream()), "pts_inference")
+        rays_d.shape[0], _S(z_vals, sample_major), features_tables.shape[2], block_corners.shape[0],
+        int(sample_major) | _infer_flags(folded), stream()), "pts_inference")
 
 
 SKIP_UNSAMPLED = 4   # include/scanerf_hip.h SCANERF_SKIP_UNSAMPLED: OR into `sample_major` of pts_inference_tracing / accumulate_color
@@ -257,8 +247,8 @@ def pts_inference_tracing(rays_o, rays_d, z_vals, dists, running_mask, intersect
         dev_ptr(grid_starts, _i64, "grid_starts"), dev_ptr(grid_log2dim, _i32, "grid_log2dim"),
         dev_ptr(block_corners, _f32, "block_corners"), dev_ptr(block_sizes, _f32, "block_sizes"),
         dev_ptr(diffuse, _f32, "diffuse"), dev_ptr(specular, _f32, "specular"), dev_ptr(alpha, _f32, "alpha"),
-        _I(rays_d.shape[0]), _S(z_vals, sample_major), _I(features_tables.shape[2]), _I(block_corners.shape[0]),
-        _I(int(sample_major) | _infer_flags(folded)), stream()), "pts_inference_tracing")
+        rays_d.shape[0], _S(z_vals, sample_major), features_tables.shape[2], block_corners.shape[0],
+        int(sample_major) | _infer_flags(folded), stream()), "pts_inference_tracing")
 
 
 def accumulate_color(pts_diffuse, pts_specular, pts_alpha, transparency, z_vals, diffuse, specular, depth, sample_major=False):
@@ -266,15 +256,14 @@ def accumulate_color(pts_diffuse, pts_specular, pts_alpha, transparency, z_vals,
         dev_ptr(pts_diffuse, _f32, "pts_diffuse"), dev_ptr(pts_specular, _f32, "pts_specular"),
         dev_ptr(pts_alpha, _f32, "pts_alpha"), dev_ptr(transparency, _f32, "transparency"), dev_ptr(z_vals, _f32, "z_vals"),
         dev_ptr(diffuse, _f32, "diffuse"), dev_ptr(specular, _f32, "specular"), dev_ptr(depth, _f32, "depth"),
-        _I(transparency.shape[0]), _S(z_vals, sample_major), _I(int(sample_major)), stream()), "accumulate_color")
+        transparency.shape[0], _S(z_vals, sample_major), int(sample_major), stream()), "accumulate_color")
 
 
 def inverse_z_sampling(intersections, related_bidx, z_vals, sample_range, sample_major=False):
     check(lib().scanerf_render_inverse_z_sampling(dev_ptr(intersections, _f32, "intersections"),
-                                                  dev_ptr(related_bidx, _i16, "related_bidx"),
-                                                  dev_ptr(z_vals, _f32, "z_vals"), ctypes.c_float(sample_range),
-                                                  _I(intersections.shape[0]), _S(z_vals, sample_major),
-                                                  _I(intersections.shape[1]), _I(int(sample_major)), stream()), "inverse_z_sampling")
+                                                  dev_ptr(related_bidx, _i16, "related_bidx"), dev_ptr(z_vals, _f32, "z_vals"),
+                                                  sample_range, intersections.shape[0], _S(z_vals, sample_major),
+                                                  intersections.shape[1], int(sample_major), stream()), "inverse_z_sampling")
 
 
 def bg_pts_inference_v2(rays_o, rays_d, z_vals, bg_idxs, step, block_corners, block_sizes, resolution, features_tables,
@@ -283,12 +272,12 @@ def bg_pts_inference_v2(rays_o, rays_d, z_vals, bg_idxs, step, block_corners, bl
     img = _packed_images(params, folded)
     check(lib().scanerf_bg_pts_inference_v2(
         dev_ptr(rays_o, _f32, "rays_o"), dev_ptr(rays_d, _f32, "rays_d"), dev_ptr(z_vals, _f32, "z_vals"),
-        dev_ptr(bg_idxs, _i16, "bg_idxs"), _I(step), dev_ptr(block_corners, _f32, "block_corners"),
+        dev_ptr(bg_idxs, _i16, "bg_idxs"), step, dev_ptr(block_corners, _f32, "block_corners"),
         dev_ptr(block_sizes, _f32, "block_sizes"), dev_ptr(resolution, _i32, "resolution"),
         dev_ptr(features_tables, torch.float16, "features_tables"), dev_ptr(img, _f32, "images"),
         dev_ptr(diffuse, _f32, "diffuse"), dev_ptr(specular, _f32, "specular"), dev_ptr(alpha, _f32, "alpha"),
-        _I(rays_d.shape[0]), _S(z_vals, sample_major), _I(features_tables.shape[2]), _I(block_corners.shape[0]),
-        _I(int(sample_major) | _infer_flags(folded)), stream()), "bg_pts_inference_v2")
+        rays_d.shape[0], _S(z_vals, sample_major), features_tables.shape[2], block_corners.shape[0],
+        int(sample_major) | _infer_flags(folded), stream()), "bg_pts_inference_v2")
 
 
 def bg_pts_inference(rays_o, rays_d, z_vals, outgoing_bidxs, blend_weights, block_corners, block_sizes, resolution,
@@ -325,8 +314,8 @@ def update_outgoing_bidx(rays_o, rays_d, block_corners, block_sizes, tracing_blo
         dev_ptr(rays_o, _f32, "rays_o"), dev_ptr(rays_d, _f32, "rays_d"), dev_ptr(block_corners, _f32, "block_corners"),
         dev_ptr(block_sizes, _f32, "block_sizes"), dev_ptr(tracing_blocks, _i32, "tracing_blocks"),
         dev_ptr(intersections, _f32, "intersections"), dev_ptr(outgoing_bidxs, _i16, "outgoing_bidxs"),
-        dev_ptr(blend_weights, _f32, "blend_weights"), ctypes.c_float(ratio), _I(int(bool(skip))),
-        _I(tracing_blocks.shape[0]), _I(tracing_blocks.shape[1]), stream()), "update_outgoing_bidx")
+        dev_ptr(blend_weights, _f32, "blend_weights"), ratio, int(bool(skip)),
+        tracing_blocks.shape[0], tracing_blocks.shape[1], stream()), "update_outgoing_bidx")
 
 
 def update_outgoing_bidx_v2(rays_o, rays_d, block_corners, block_sizes, tracing_blocks, intersections, inside_bidxs,
@@ -334,14 +323,14 @@ def update_outgoing_bidx_v2(rays_o, rays_d, block_corners, block_sizes, tracing_
     check(lib().scanerf_update_outgoing_bidx_v2(
         dev_ptr(rays_o, _f32, "rays_o"), dev_ptr(block_corners, _f32, "block_corners"),
         dev_ptr(block_sizes, _f32, "block_sizes"), dev_ptr(inside_bidxs, _i16, "inside_bidxs"),
-        dev_ptr(blend_weights, _f32, "blend_weights"), _I(tracing_blocks.shape[0]), _I(tracing_blocks.shape[1]), stream()),
+        dev_ptr(blend_weights, _f32, "blend_weights"), tracing_blocks.shape[0], tracing_blocks.shape[1], stream()),
         "update_outgoing_bidx_v2")
 
 
 def get_last_block(tracing_blocks, bidxs, intersections):
     check(lib().scanerf_get_last_block(dev_ptr(tracing_blocks, _i32, "tracing_blocks"), dev_ptr(bidxs, _i32, "bidxs"),
-                                       dev_ptr(intersections, _f32, "intersections"), _I(intersections.shape[0]),
-                                       _I(intersections.shape[1]), stream()), "get_last_block")
+                                       dev_ptr(intersections, _f32, "intersections"), intersections.shape[0],
+                                       intersections.shape[1], stream()), "get_last_block")
 
 
 def ray_firsthit_block(rays_o, rays_d, block_corners, block_sizes, grid_occupied, grid_starts, grid_log2dim,
@@ -351,17 +340,17 @@ def ray_firsthit_block(rays_o, rays_d, block_corners, block_sizes, grid_occupied
         dev_ptr(block_sizes, _f32, "block_sizes"), dev_ptr(grid_occupied, _bool, "grid_occupied"),
         dev_ptr(grid_starts, _i64, "grid_starts"), dev_ptr(grid_log2dim, _i32, "grid_log2dim"),
         dev_ptr(tracing_blocks, _i32, "tracing_blocks"), dev_ptr(intersections, _f32, "intersections"),
-        dev_ptr(hit_blockIdxs, _i16, "hit_blockIdxs"), _I(rays_d.shape[0]), _I(block_corners.shape[0]), stream()),
+        dev_ptr(hit_blockIdxs, _i16, "hit_blockIdxs"), rays_d.shape[0], block_corners.shape[0], stream()),
         "ray_firsthit_block")
 
 
 def process_occupied_grid(bidx, total_grid, block_corners, block_sizes, grid_occupied, grid_starts, grid_log2dim,
                           tgt_grid_occupied):
     check(lib().scanerf_process_occupied_grid(
-        _I(bidx), _I(total_grid), dev_ptr(block_corners, _f32, "block_corners"), dev_ptr(block_sizes, _f32, "block_sizes"),
+        bidx, total_grid, dev_ptr(block_corners, _f32, "block_corners"), dev_ptr(block_sizes, _f32, "block_sizes"),
         dev_ptr(grid_occupied, _bool, "grid_occupied"), dev_ptr(grid_starts, _i64, "grid_starts"),
         dev_ptr(grid_log2dim, _i32, "grid_log2dim"), dev_ptr(tgt_grid_occupied, _bool, "tgt_grid_occupied"),
-        _I(block_corners.shape[0]), stream()), "process_occupied_grid")
+        block_corners.shape[0], stream()), "process_occupied_grid")
 
 
 def sort_by_key(keys_tensor, values_tensor, starts_tensor):

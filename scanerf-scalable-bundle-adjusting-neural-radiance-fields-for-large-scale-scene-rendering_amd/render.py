@@ -114,7 +114,7 @@ def jstash_shape(B, S):
 
 def forward_plan_supported(B, S, T):
     """render_forward(plan=True) can do scatter_plan's work for the t16 backward of the same rays (equal kernel grids)."""
-    return bool(lib().scanerf_render_forward_plan_supported(ctypes.c_int(B), ctypes.c_int(S), ctypes.c_int(T)))
+    return bool(lib().scanerf_render_forward_plan_supported(B, S, T))
 
 
 def render_forward(rays_o, rays_d, z_vals, dists, features, resolutions, packed, min_bbox, bbox_size, contract_mode,
@@ -136,24 +136,23 @@ def render_forward(rays_o, rays_d, z_vals, dists, features, resolutions, packed,
     T = features.shape[1]
     args = (dev_ptr(rays_o, _f32, "rays_o"), dev_ptr(rays_d, _f32, "rays_d"), dev_ptr(z_vals, _f32, "z_vals"),
             dev_ptr(dists, _f32, "dists"), dev_ptr(features, (torch.float32, torch.float16, torch.bfloat16), "features"),
-            ctypes.c_int(feat_dtype_code(features)), dev_ptr(resolutions, torch.int32, "resolutions"),
+            feat_dtype_code(features), dev_ptr(resolutions, torch.int32, "resolutions"),
             dev_ptr(packed.workspace, _f32, "workspace"))
     tail = (dev_ptr(ray_valid, (torch.bool, torch.uint8), "ray_valid", allow_none=True), dev_ptr(out_ray, _f32, "out_ray"),
             dev_ptr(weights, _f32, "weights", allow_none=True), dev_ptr(tile_T, _f32, "tile_T", allow_none=True),
-            dev_ptr(xstash, _f32, "xstash", allow_none=True), ctypes.c_int(B), ctypes.c_int(S), ctypes.c_int(T))
+            dev_ptr(xstash, _f32, "xstash", allow_none=True), B, S, T)
     if plan or jstash is not None:
         ws = None
         if plan:
-            need = lib().scanerf_render_scatter_workspace_bytes(ctypes.c_int(B), ctypes.c_int(S), ctypes.c_int(T))
+            need = lib().scanerf_render_scatter_workspace_bytes(B, S, T)
             if not need or not forward_plan_supported(B, S, T):
                 raise RuntimeError(f"scanerf: render_forward(plan=True) does not support B={B} S={S} T={T}")
             ws = _capi.workspace(z_vals.device, need) if plan_workspace is None else plan_workspace
         cfg = _cfg(min_bbox, bbox_size, contract_mode, infinity, ARITH if ARITH in _capi.T16_FAMILY else _capi.ARITH_T16,
                    getattr(packed, "skip_levels", 0))
         tail = tail[:5] + (dev_ptr(jstash, JSTASH_DTYPE, "jstash", allow_none=True),) + tail[5:]
-        check(lib().scanerf_render_forward_packed_plan(*args, ctypes.byref(cfg), *tail,
-                                                       ctypes.c_void_p(ws.data_ptr() if ws is not None else None),
-                                                       ctypes.c_size_t(ws.numel() if ws is not None else 0), stream()),
+        check(lib().scanerf_render_forward_packed_plan(*args, ctypes.byref(cfg), *tail, ws.data_ptr() if ws is not None else None,
+                                                       ws.numel() if ws is not None else 0, stream()),
               "render_forward(plan)")
         return (out_ray, weights, ws) if plan else (out_ray, weights)
     cfg = _cfg(min_bbox, bbox_size, contract_mode, infinity, skip_levels=getattr(packed, "skip_levels", 0))
@@ -180,7 +179,7 @@ def render_backward(rays_o, rays_d, z_vals, dists, features, resolutions, packed
     if scatter is None and not want_dfeat:
         raise ValueError("render_backward: nothing would receive the feature gradients")
     dfeat = torch.empty((16, B * S, 2), dtype=_f32, device=dev) if want_dfeat else None
-    nblk = lib().scanerf_render_backward_grid(ctypes.c_int(B))
+    nblk = lib().scanerf_render_backward_grid(B)
     dw_partial = torch.empty((4 * nblk, _capi.PARAMSIZE), dtype=_f32, device=dev)
     if _KEEP_DW_PARTIAL is not None:   # investigation hook (tools/bwd_stamps.py: the -DT16_STAMPS build parks its cycle sums there)
         _KEEP_DW_PARTIAL[:] = [dw_partial, nblk]
@@ -190,7 +189,7 @@ def render_backward(rays_o, rays_d, z_vals, dists, features, resolutions, packed
     check(lib().scanerf_render_backward(
         dev_ptr(rays_o, _f32, "rays_o"), dev_ptr(rays_d, _f32, "rays_d"), dev_ptr(z_vals, _f32, "z_vals"),
         dev_ptr(dists, _f32, "dists"), dev_ptr(features, (torch.float32, torch.float16, torch.bfloat16), "features"),
-        ctypes.c_int(feat_dtype_code(features)), dev_ptr(resolutions, torch.int32, "resolutions"),
+        feat_dtype_code(features), dev_ptr(resolutions, torch.int32, "resolutions"),
         dev_ptr(packed.workspace, _f32, "workspace"), dev_ptr(weight_feature, _f32, "weight_feature"),
         ctypes.byref(cfg), dev_ptr(ray_valid, (torch.bool, torch.uint8), "ray_valid", allow_none=True),
         dev_ptr(out_ray, _f32, "out_ray"), dev_ptr(tile_T, _f32, "tile_T"), dev_ptr(grad_out, _f32, "grad_out"),
@@ -198,9 +197,9 @@ def render_backward(rays_o, rays_d, z_vals, dists, features, resolutions, packed
         dev_ptr(ray_grad_buffers[0] if ray_grad_buffers else None, _f32, "g_dnorm", allow_none=True),
         dev_ptr(ray_grad_buffers[1] if ray_grad_buffers else None, _f32, "g_rowsum", allow_none=True),
         dev_ptr(jstash, JSTASH_DTYPE, "jstash", allow_none=True), dev_ptr(ray_pos_grad, _f32, "ray_pos_grad", allow_none=True),
-        ctypes.c_void_p(scatter[0].data_ptr() if scatter else None), ctypes.c_size_t(scatter[0].numel() if scatter else 0),
+        scatter[0].data_ptr() if scatter else None, scatter[0].numel() if scatter else 0,
         dev_ptr(scatter[1] if scatter else None, _f32, "grad_features", allow_none=True),
-        ctypes.c_int(B), ctypes.c_int(S), ctypes.c_int(features.shape[1]), stream()), "render_backward")
+        B, S, features.shape[1], stream()), "render_backward")
     return dfeat, grad_blob
 
 
@@ -215,8 +214,8 @@ def photometric_loss_grad(out_ray, target, ray_valid=None, reg_weight=0.01, grad
     scratch = torch.empty(lib().scanerf_photometric_loss_scratch_floats(), dtype=_f32, device=dev)
     check(lib().scanerf_photometric_loss_grad(
         dev_ptr(out_ray, _f32, "out_ray"), dev_ptr(target, _f32, "target"),
-        dev_ptr(ray_valid, (torch.bool, torch.uint8), "ray_valid", allow_none=True), ctypes.c_float(reg_weight),
-        dev_ptr(grad_out, _f32, "grad_out"), dev_ptr(loss, _f32, "loss"), dev_ptr(scratch, _f32, "scratch"), ctypes.c_int(B),
+        dev_ptr(ray_valid, (torch.bool, torch.uint8), "ray_valid", allow_none=True), reg_weight,
+        dev_ptr(grad_out, _f32, "grad_out"), dev_ptr(loss, _f32, "loss"), dev_ptr(scratch, _f32, "scratch"), B,
         stream()), "photometric_loss_grad")
     return loss, grad_out
 
@@ -234,8 +233,8 @@ def photometric_loss_grad_fgbg(out_fg, out_bg, target, valid_fg=None, valid_bg=N
     check(lib().scanerf_photometric_loss_grad_fgbg(
         dev_ptr(out_fg, _f32, "out_fg"), dev_ptr(out_bg, _f32, "out_bg"), dev_ptr(target, _f32, "target"),
         dev_ptr(valid_fg, vt, "valid_fg", allow_none=True), dev_ptr(valid_bg, vt, "valid_bg", allow_none=True),
-        ctypes.c_float(reg_weight), dev_ptr(gfg, _f32, "grad_fg"), dev_ptr(gbg, _f32, "grad_bg"), dev_ptr(loss, _f32, "loss"),
-        dev_ptr(scratch, _f32, "scratch"), ctypes.c_int(B), stream()), "photometric_loss_grad_fgbg")
+        reg_weight, dev_ptr(gfg, _f32, "grad_fg"), dev_ptr(gbg, _f32, "grad_bg"), dev_ptr(loss, _f32, "loss"),
+        dev_ptr(scratch, _f32, "scratch"), B, stream()), "photometric_loss_grad_fgbg")
     return loss, gfg, gbg
 
 
@@ -246,11 +245,9 @@ def scatter_accumulate_adam2(ws1, S1, ws2, S2, params, exp_avg, exp_avg_sq, lr, 
     check(lib().scanerf_render_scatter_accumulate_adam2(
         dev_ptr(params, _f32, "params"), dev_ptr(exp_avg, _f32, "exp_avg"), dev_ptr(exp_avg_sq, _f32, "exp_avg_sq"),
         dev_ptr(half_table, (torch.float16, torch.bfloat16), "half_table", allow_none=True),
-        ctypes.c_int(feat_dtype_code(half_table) if half_table is not None else 0),
-        dev_ptr(overflow_grad, _f32, "overflow_grad", allow_none=True), ctypes.c_float(lr), ctypes.c_float(beta1),
-        ctypes.c_float(beta2), ctypes.c_float(eps), ctypes.c_int(step), ctypes.c_int(B), ctypes.c_int(params.shape[1]),
-        ctypes.c_int(S1), ctypes.c_void_p(ws1.data_ptr()), ctypes.c_size_t(ws1.numel()), ctypes.c_int(S2),
-        ctypes.c_void_p(ws2.data_ptr()), ctypes.c_size_t(ws2.numel()), stream()), "scatter_accumulate_adam2")
+        feat_dtype_code(half_table) if half_table is not None else 0,
+        dev_ptr(overflow_grad, _f32, "overflow_grad", allow_none=True), lr, beta1, beta2, eps, step, B, params.shape[1], S1,
+        ws1.data_ptr(), ws1.numel(), S2, ws2.data_ptr(), ws2.numel(), stream()), "scatter_accumulate_adam2")
 
 
 def ray_valid(z_vals):
@@ -258,8 +255,8 @@ def ray_valid(z_vals):
     B, S = z_vals.shape
     n = (B + 15) // 16 * 16  # scanerf_compact_rays reads the flags 16 bytes at a time
     buf = torch.zeros(n, dtype=torch.uint8, device=z_vals.device)
-    check(lib().scanerf_ray_valid(dev_ptr(z_vals, _f32, "z_vals"), dev_ptr(buf, torch.uint8, "valid"), ctypes.c_int(B),
-                                  ctypes.c_int(S), stream()), "ray_valid")
+    check(lib().scanerf_ray_valid(dev_ptr(z_vals, _f32, "z_vals"), dev_ptr(buf, torch.uint8, "valid"), B,
+                                  S, stream()), "ray_valid")
     return buf[:B]
 
 
@@ -278,7 +275,7 @@ def compact_rays(valid, rays_o, rays_d, target, z_vals, dists, want_index=False)
     idx = torch.empty(B, dtype=torch.int32, device=dev) if want_index else None
     count = torch.zeros(1, dtype=torch.int32, device=dev)
     check(lib().scanerf_compact_rays(
-        dev_ptr(valid, (torch.uint8, torch.bool), "valid"), ctypes.c_int(B), ctypes.c_int(S), dev_ptr(rays_o, _f32, "rays_o"),
+        dev_ptr(valid, (torch.uint8, torch.bool), "valid"), B, S, dev_ptr(rays_o, _f32, "rays_o"),
         dev_ptr(rays_d, _f32, "rays_d"), dev_ptr(target, _f32, "target", allow_none=True), dev_ptr(z_vals, _f32, "z_vals"),
         dev_ptr(dists, _f32, "dists"), dev_ptr(o, _f32, "out_o"), dev_ptr(d, _f32, "out_d"), dev_ptr(t, _f32, "out_t", allow_none=True),
         dev_ptr(z, _f32, "out_z"), dev_ptr(di, _f32, "out_dist"), dev_ptr(idx, torch.int32, "out_index", allow_none=True),
@@ -289,7 +286,7 @@ def compact_rays(valid, rays_o, rays_d, target, z_vals, dists, want_index=False)
 
 
 def scatter_supported(B, S, T):
-    return lib().scanerf_render_scatter_workspace_bytes(ctypes.c_int(B), ctypes.c_int(S), ctypes.c_int(T)) != 0
+    return lib().scanerf_render_scatter_workspace_bytes(B, S, T) != 0
 
 
 def scatter_plan(rays_o, rays_d, z_vals, resolutions, T, min_bbox, bbox_size, contract_mode, infinity, ray_valid=None,
@@ -300,7 +297,7 @@ def scatter_plan(rays_o, rays_d, z_vals, resolutions, T, min_bbox, bbox_size, co
     arith: the backward kernel that will emit the records (its ray -> workgroup map is reserved here); default
     backward_arith() = what render_backward picks when it is given an x-stash and no pose-gradient buffers."""
     B, S = z_vals.shape
-    need = lib().scanerf_render_scatter_workspace_bytes(ctypes.c_int(B), ctypes.c_int(S), ctypes.c_int(T))
+    need = lib().scanerf_render_scatter_workspace_bytes(B, S, T)
     if not need:
         raise RuntimeError(f"scanerf: fused scatter does not support B={B} S={S} T={T}")
     # (workspace: a caller-owned uint8 tensor instead of the cached one; smaller than `need` = overflow records take the
@@ -311,16 +308,15 @@ def scatter_plan(rays_o, rays_d, z_vals, resolutions, T, min_bbox, bbox_size, co
     check(lib().scanerf_render_scatter_plan(
         dev_ptr(rays_o, _f32, "rays_o"), dev_ptr(rays_d, _f32, "rays_d"), dev_ptr(z_vals, _f32, "z_vals"),
         dev_ptr(resolutions, torch.int32, "resolutions"), ctypes.byref(cfg),
-        dev_ptr(ray_valid, (torch.bool, torch.uint8), "ray_valid", allow_none=True), ctypes.c_int(B), ctypes.c_int(S),
-        ctypes.c_int(T), ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), stream()), "scatter_plan")
+        dev_ptr(ray_valid, (torch.bool, torch.uint8), "ray_valid", allow_none=True), B, S,
+        T, ws.data_ptr(), ws.numel(), stream()), "scatter_plan")
     return ws
 
 
 def scatter_accumulate(ws, grad_features, B, S):
     """grad_features [16,T,2] += the records the fused backward emitted into ws."""
     check(lib().scanerf_render_scatter_accumulate(
-        dev_ptr(grad_features, _f32, "grad_features"), ctypes.c_int(B), ctypes.c_int(S),
-        ctypes.c_int(grad_features.shape[1]), ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), stream()),
+        dev_ptr(grad_features, _f32, "grad_features"), B, S, grad_features.shape[1], ws.data_ptr(), ws.numel(), stream()),
         "scatter_accumulate")
     return grad_features
 
@@ -334,10 +330,9 @@ def scatter_accumulate_adam(ws, params, exp_avg, exp_avg_sq, lr, beta1, beta2, e
     check(lib().scanerf_render_scatter_accumulate_adam(
         dev_ptr(params, _f32, "params"), dev_ptr(exp_avg, _f32, "exp_avg"), dev_ptr(exp_avg_sq, _f32, "exp_avg_sq"),
         dev_ptr(half_table, (torch.float16, torch.bfloat16), "half_table", allow_none=True),
-        ctypes.c_int(feat_dtype_code(half_table) if half_table is not None else 0),
-        dev_ptr(overflow_grad, _f32, "overflow_grad", allow_none=True), ctypes.c_float(lr), ctypes.c_float(beta1),
-        ctypes.c_float(beta2), ctypes.c_float(eps), ctypes.c_int(step), ctypes.c_int(B), ctypes.c_int(S),
-        ctypes.c_int(params.shape[1]), ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), stream()),
+        feat_dtype_code(half_table) if half_table is not None else 0,
+        dev_ptr(overflow_grad, _f32, "overflow_grad", allow_none=True), lr, beta1, beta2, eps, step, B, S, params.shape[1],
+        ws.data_ptr(), ws.numel(), stream()),
         "scatter_accumulate_adam")
 
 
@@ -345,14 +340,13 @@ def scatter_table_grad(points, dfeat, grad_features, resolutions, compact_record
     """grad_features [16,T,2] += binned scatter of level-major dfeat at contracted `points` [N,3].
     compact_records: -1 = the layout's default (16-byte records for level-major gradients), 0 / 1 / 2 = 16- / 8- / 12-byte records."""
     N, (L, T) = points.shape[0], grad_features.shape[:2]
-    need = lib().scanerf_embedding_bwd_workspace_bytes(ctypes.c_int(N), ctypes.c_int(L), ctypes.c_int(T))
+    need = lib().scanerf_embedding_bwd_workspace_bytes(N, L, T)
     if not need:
         raise RuntimeError("scanerf: shape not supported by the binned scatter")
     ws = _capi.workspace(points.device, need, "scatter")
     check(lib().scanerf_embedding_bg_backward_binned(
         dev_ptr(points, _f32, "points"), dev_ptr(dfeat, _f32, "dfeat"), dev_ptr(grad_features, _f32, "grad_features"),
-        dev_ptr(resolutions, torch.int32, "resolutions"), ctypes.c_int(N), ctypes.c_int(L), ctypes.c_int(T),
-        ctypes.c_int(1), ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), ctypes.c_int(int(compact_records)), stream()),
+        dev_ptr(resolutions, torch.int32, "resolutions"), N, L, T, 1, ws.data_ptr(), ws.numel(), int(compact_records), stream()),
         "scatter_table_grad")
     return grad_features
 
@@ -364,18 +358,17 @@ def scatter_table_grad_adam(points, dfeat, resolutions, params, exp_avg, exp_avg
     compact_records: 1 = 8-byte records (for dfeat out of the t16 backward; scatter_common.h Rec8), 2 = 12-byte records
     (f32-grade, behind the t16s backward; Rec12), 0 = 16-byte records."""
     N, (L, T) = points.shape[0], params.shape[:2]
-    need = lib().scanerf_embedding_bwd_workspace_bytes(ctypes.c_int(N), ctypes.c_int(L), ctypes.c_int(T))
+    need = lib().scanerf_embedding_bwd_workspace_bytes(N, L, T)
     if not need:
         raise RuntimeError("scanerf: shape not supported by the binned scatter")
     ws = _capi.workspace(points.device, need, "scatter")
     check(lib().scanerf_embedding_bg_backward_binned_adam(
-        dev_ptr(points, _f32, "points"), dev_ptr(dfeat, _f32, "dfeat"), dev_ptr(resolutions, torch.int32, "resolutions"),
-        ctypes.c_int(N), ctypes.c_int(L), ctypes.c_int(T), ctypes.c_int(1), ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()),
-        dev_ptr(params, _f32, "params"), dev_ptr(exp_avg, _f32, "exp_avg"), dev_ptr(exp_avg_sq, _f32, "exp_avg_sq"),
+        dev_ptr(points, _f32, "points"), dev_ptr(dfeat, _f32, "dfeat"), dev_ptr(resolutions, torch.int32, "resolutions"), N, L, T,
+        1, ws.data_ptr(), ws.numel(), dev_ptr(params, _f32, "params"), dev_ptr(exp_avg, _f32, "exp_avg"),
+        dev_ptr(exp_avg_sq, _f32, "exp_avg_sq"),
         dev_ptr(half_table, (torch.float16, torch.bfloat16), "half_table", allow_none=True),
-        ctypes.c_int(feat_dtype_code(half_table) if half_table is not None else 0), dev_ptr(overflow_grad, _f32, "overflow_grad"),
-        ctypes.c_float(lr), ctypes.c_float(beta1), ctypes.c_float(beta2), ctypes.c_float(eps), ctypes.c_int(step),
-        ctypes.c_int(int(compact_records)), stream()), "scatter_table_grad_adam")
+        feat_dtype_code(half_table) if half_table is not None else 0, dev_ptr(overflow_grad, _f32, "overflow_grad"), lr, beta1,
+        beta2, eps, step, int(compact_records), stream()), "scatter_table_grad_adam")
 
 
 RAYS_SCATTER = True   # (False: tile_model builds contracted points in torch and concatenates the branches, as rounds 1-5 did)
@@ -398,7 +391,7 @@ def scatter_table_grad_adam_rays(rays_o, rays_d, branches, min_bbox, bbox_size, 
     if not 1 <= len(branches) <= 2 or params.shape[0] != 16:
         raise RuntimeError("scanerf: scatter_table_grad_adam_rays takes one or two branches and 16 levels")
     N = sum(B * z.shape[1] for z, _, _, _ in branches)
-    need = lib().scanerf_embedding_bwd_workspace_bytes(ctypes.c_int(N), ctypes.c_int(16), ctypes.c_int(T))
+    need = lib().scanerf_embedding_bwd_workspace_bytes(N, 16, T)
     if not need:
         raise RuntimeError("scanerf: shape not supported by the binned scatter")
     ws = _capi.workspace(rays_o.device, need, "scatter")
@@ -409,18 +402,17 @@ def scatter_table_grad_adam_rays(rays_o, rays_d, branches, min_bbox, bbox_size, 
             if tuple(dfeat.shape) != (16, B * z.shape[1], 2) or z.shape[0] != B:
                 raise RuntimeError(f"scanerf: branch {k}: dfeat {tuple(dfeat.shape)} does not match z {tuple(z.shape)}")
             args += [dev_ptr(z, _f32, f"z{k}"), dev_ptr(dfeat, _f32, f"dfeat{k}"),
-                     dev_ptr(valid, (torch.bool, torch.uint8), f"valid{k}", allow_none=True), ctypes.c_int(z.shape[1]), ctypes.c_int(int(mode))]
+                     dev_ptr(valid, (torch.bool, torch.uint8), f"valid{k}", allow_none=True), z.shape[1], int(mode)]
         else:
-            args += [None, None, None, ctypes.c_int(0), ctypes.c_int(0)]
+            args += [None, None, None, 0, 0]
     mn, sz = (ctypes.c_float * 3)(*[float(v) for v in min_bbox]), (ctypes.c_float * 3)(*[float(v) for v in bbox_size])
     check(lib().scanerf_table_grad_scatter_adam_rays(
-        dev_ptr(rays_o, _f32, "rays_o"), dev_ptr(rays_d, _f32, "rays_d"), ctypes.c_int(B), *args, mn, sz,
-        dev_ptr(resolutions, torch.int32, "resolutions"), ctypes.c_int(T), ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()),
-        dev_ptr(params, _f32, "params"), dev_ptr(exp_avg, mdt, "exp_avg"), dev_ptr(exp_avg_sq, mdt, "exp_avg_sq"),
+        dev_ptr(rays_o, _f32, "rays_o"), dev_ptr(rays_d, _f32, "rays_d"), B, *args, mn, sz,
+        dev_ptr(resolutions, torch.int32, "resolutions"), T, ws.data_ptr(), ws.numel(), dev_ptr(params, _f32, "params"),
+        dev_ptr(exp_avg, mdt, "exp_avg"), dev_ptr(exp_avg_sq, mdt, "exp_avg_sq"),
         dev_ptr(half_table, (torch.float16, torch.bfloat16), "half_table", allow_none=True),
-        ctypes.c_int(feat_dtype_code(half_table) if half_table is not None else 0), dev_ptr(overflow_grad, _f32, "overflow_grad"),
-        ctypes.c_float(lr), ctypes.c_float(beta1), ctypes.c_float(beta2), ctypes.c_float(eps), ctypes.c_int(step),
-        ctypes.c_int(1 if fp16_moments else 0), stream()), "scatter_table_grad_adam_rays")
+        feat_dtype_code(half_table) if half_table is not None else 0, dev_ptr(overflow_grad, _f32, "overflow_grad"), lr, beta1,
+        beta2, eps, step, 1 if fp16_moments else 0, stream()), "scatter_table_grad_adam_rays")
 
 
 def ray_gradients_fused(rays_o, rays_d, blob, ray_pos_grad, g_dnorm, g_rowsum, ray_valid=None):
@@ -434,7 +426,7 @@ def ray_gradients_fused(rays_o, rays_d, blob, ray_pos_grad, g_dnorm, g_rowsum, r
         dev_ptr(rays_d, _f32, "rays_d"), dev_ptr(blob.detach(), _f32, "mlp_blob"), dev_ptr(ray_pos_grad, _f32, "ray_pos_grad"),
         dev_ptr(g_dnorm, _f32, "g_dnorm"), dev_ptr(g_rowsum, _f32, "g_rowsum"),
         dev_ptr(ray_valid, (torch.bool, torch.uint8), "ray_valid", allow_none=True), dev_ptr(g_o, _f32, "g_o"), dev_ptr(g_d, _f32, "g_d"),
-        ctypes.c_int(B), ctypes.c_int(S), stream()), "ray_grad_epilogue")
+        B, S, stream()), "ray_grad_epilogue")
     return g_o, g_d
 
 
@@ -480,8 +472,8 @@ def ray_gradients(rays_o, rays_d, z_vals, features, resolutions, blob, min_bbox,
     xd = x.detach().contiguous()
     check(lib().scanerf_embedding_bg_point_grad(dev_ptr(xd, _f32, "points"), dev_ptr(dfeat, _f32, "dfeat"),
                                                 dev_ptr(gp, _f32, "grad_points"), dev_ptr(features, _f32, "features"),
-                                                dev_ptr(resolutions, torch.int32, "resolutions"), ctypes.c_int(B * S),
-                                                ctypes.c_int(16), ctypes.c_int(features.shape[1]), stream()),
+                                                dev_ptr(resolutions, torch.int32, "resolutions"), B * S,
+                                                16, features.shape[1], stream()),
           "embedding_bg_point_grad")
     w_sh = blob[6503 + 64 + 32 * 64: 6503 + 64 + 48 * 64].reshape(16, 64)  # Directional_MLP.mlp.0 weight^T rows 32..47
     g_sh = g_rowsum.sum(1) @ w_sh.t()
@@ -537,7 +529,7 @@ class FusedRenderRays(torch.autograd.Function):
         own_ws = None
         if (FORWARD_PLAN_IN_AUTOGRAD and ctx.needs_input_grad[4] and T <= (1 << 21) and scatter_supported(B, S, T)
                 and forward_plan_supported(B, S, T) and backward_arith(True, need_rays) in _capi.T16_FAMILY):
-            own_ws = torch.empty(lib().scanerf_render_scatter_workspace_bytes(ctypes.c_int(B), ctypes.c_int(S), ctypes.c_int(T)),
+            own_ws = torch.empty(lib().scanerf_render_scatter_workspace_bytes(B, S, T),
                                  dtype=torch.uint8, device=dev)
         r = render_forward(rays_o, rays_d, z_vals, dists, table, resolutions, packed, min_bbox, bbox_size, contract_mode,
                            infinity, ray_valid=ray_valid, want_weights=want_weights, tile_T=tile_T, xstash=xstash, jstash=jstash,
@@ -630,7 +622,7 @@ class CompositeRays(torch.autograd.Function):
         check(lib().scanerf_composite_forward(
             dev_ptr(sg, _f32, "sigma"), dev_ptr(cd, _f32, "diffuse"), dev_ptr(cs, _f32, "specular"), dev_ptr(tn, _f32, "tint"),
             dev_ptr(z, _f32, "z_vals"), dev_ptr(dd, _f32, "dists"), dev_ptr(rd, _f32, "rays_d"), dev_ptr(out, _f32, "out_ray"),
-            dev_ptr(w, _f32, "weights"), ctypes.c_int(B), ctypes.c_int(S), ctypes.c_int(1 if infinity else 0), stream()), "composite_forward")
+            dev_ptr(w, _f32, "weights"), B, S, 1 if infinity else 0, stream()), "composite_forward")
         ctx.save_for_backward(sg, cd, cs, tn, z, dd, rd, out)
         ctx.infinity, ctx.shapes = bool(infinity), (sigma.shape, diffuse.shape)
         return out, w
@@ -650,7 +642,7 @@ class CompositeRays(torch.autograd.Function):
             dev_ptr(z, _f32, "z_vals"), dev_ptr(dd, _f32, "dists"), dev_ptr(rd, _f32, "rays_d"), dev_ptr(out, _f32, "out_ray"),
             dev_ptr(go, _f32, "grad_out"), dev_ptr(gw, _f32, "grad_weights", allow_none=True), dev_ptr(g_sigma, _f32, "g_sigma"),
             dev_ptr(g_cd, _f32, "g_diffuse"), dev_ptr(g_cs, _f32, "g_specular"), dev_ptr(g_tn, _f32, "g_tint"),
-            dev_ptr(g_dn, _f32, "g_dnorm"), ctypes.c_int(B), ctypes.c_int(S), ctypes.c_int(1 if ctx.infinity else 0), stream()),
+            dev_ptr(g_dn, _f32, "g_dnorm"), B, S, 1 if ctx.infinity else 0, stream()),
             "composite_backward")
         g_rd = g_dn[:, None] * rd / rd.norm(dim=-1, keepdim=True) if ctx.needs_input_grad[6] else None
         sshape, cshape = ctx.shapes

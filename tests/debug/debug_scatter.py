@@ -1,4 +1,4 @@
-import ctypes, os, sys
+import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))  # repo root
 import scanerf_amd
@@ -20,8 +20,8 @@ for ws_bytes in (need, 1 << 20):
     ws = workspace(DEV, need)
     gf = torch.zeros(L, T, 2, device=DEV)
     P, G, R = g(pts), g(gin), g(res)
-    check(lib().scanerf_embedding_bg_backward_binned(ctypes.c_void_p(P.data_ptr()), ctypes.c_void_p(G.data_ptr()), ctypes.c_void_p(gf.data_ptr()),
-          ctypes.c_void_p(R.data_ptr()), N, L, T, 0, ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws_bytes), stream()), "b")
+    check(lib().scanerf_embedding_bg_backward_binned(P.data_ptr(), G.data_ptr(), gf.data_ptr(),
+          R.data_ptr(), N, L, T, 0, ws.data_ptr(), ws_bytes, -1, stream()), "b")
     out = gf.cpu().numpy()
     bad = np.argwhere(np.abs(out - gf_ref) > 3e-4 + 1e-3 * np.abs(gf_ref))
     print("ws", ws_bytes, "bad", len(bad), "levels", np.unique(bad[:, 0]) if len(bad) else None)

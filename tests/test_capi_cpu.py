@@ -17,6 +17,89 @@ def _declared_symbols():
     return sorted(set(re.findall(r"\b(scanerf_[a-z0-9_]+)\s*\(", hdr)))
 
 
+_ALIAS = {"int": "I", "unsigned": "U", "float": "F", "size_t": "Z", "int64_t": "L", "long long": "L", "char *": "S"}
+
+
+def _header_code():
+    hdr = open(os.path.join(ROOT, "include", "scanerf_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/|//[^\n]*", "", hdr, flags=re.S)
+    return re.sub(r"^\s*#.*$", "", hdr, flags=re.M)
+
+
+def _alias(decl):
+    """One C declaration (type, optionally followed by its name) -> its letter in _capi.PROTOTYPES."""
+    t = " ".join(decl.replace("const", "").replace("*", " * ").split()).replace(" *", "*").replace("*", " *")
+    if t not in _ALIAS and not t.endswith("*"):
+        t = t.rsplit(" ", 1)[0]   # drop the parameter name
+    if t in _ALIAS:
+        return _ALIAS[t]
+    assert t.endswith("*") or t == "scanerf_stream_t", decl
+    return "P"
+
+
+def _header_prototypes():
+    """include/scanerf_hip.h's functions: name -> (return letter, argument letters)."""
+    out = {}
+    for ret, name, args in re.findall(r"([\w\s*]+?)\b(scanerf_\w+)\s*\(([^)]*)\)\s*;", _header_code()):
+        args = [] if args.strip() in ("", "void") else args.split(",")
+        out[name] = (_alias(ret), "".join(_alias(a) for a in args))
+    return out
+
+
+def test_prototype_table_matches_the_header():
+    """_capi.PROTOTYPES (what lib() types every export with) says what include/scanerf_hip.h says: the same functions, each
+    with the same return type and, position by position, the same argument types."""
+    import scanerf_amd  # noqa
+    from scanerf_amd import _capi
+    hdr = _header_prototypes()
+    assert len(hdr) == len(_declared_symbols())   # every declared name parsed as a prototype
+    assert set(hdr) == set(_capi.PROTOTYPES), sorted(set(hdr) ^ set(_capi.PROTOTYPES))
+    bad = {n: (hdr[n], _capi.PROTOTYPES[n][:2]) for n in hdr if hdr[n] != _capi.PROTOTYPES[n][:2]}
+    assert not bad, bad
+    lib = _capi.lib()
+    with pytest.raises(TypeError, match="scanerf_render_backward_grid"):
+        lib.scanerf_render_backward_grid(*(1, 2))   # ctypes alone would pass the extra argument through
+    with pytest.raises(ctypes.ArgumentError):
+        lib.scanerf_render_backward_grid(1.5)       # a float for an int parameter
+
+
+def test_render_cfg_matches_the_header_struct():
+    import scanerf_amd  # noqa
+    from scanerf_amd import _capi
+    body = re.search(r"typedef\s+struct\s*\w*\s*\{(.*?)\}\s*scanerf_render_cfg\s*;", _header_code(), re.S).group(1)
+    want = []
+    for decl in filter(str.strip, body.split(";")):
+        t, name, n = re.fullmatch(r"\s*(.+?)\s+(\w+)\s*(?:\[(\d+)\])?\s*", decl).groups()
+        want.append((name, _capi.CTYPES[_alias(t)], int(n) if n else None))
+    got = [(name, t._type_ if issubclass(t, ctypes.Array) else t, t._length_ if issubclass(t, ctypes.Array) else None)
+           for name, t in _capi.RenderCfg._fields_]
+    assert got == want
+
+
+def test_every_call_site_passes_the_prototypes_argument_count():
+    """Every `<x>.scanerf_*(...)` call in the package, tests/, tools/ and the repository root that spells its arguments out
+    (no *splat) passes exactly as many as the prototype has -- checked without loading the library."""
+    import ast
+    import scanerf_amd  # noqa
+    from scanerf_amd import _capi
+    paths = [os.path.join(ROOT, f) for f in os.listdir(ROOT) if f.endswith(".py")]
+    for top in (_capi._HERE, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
+        paths += [os.path.join(d, f) for d, _, fs in os.walk(top) for f in fs if f.endswith(".py")]
+    calls, bad = 0, []
+    for path in paths:
+        for node in ast.walk(ast.parse(open(path).read(), path)):
+            if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr.startswith("scanerf_")):
+                continue
+            if any(isinstance(a, ast.Starred) for a in node.args):
+                continue
+            calls += 1
+            proto = _capi.PROTOTYPES.get(node.func.attr)
+            if proto is None or len(node.args) != len(proto[1]) or node.keywords:
+                bad.append(f"{os.path.relpath(path, ROOT)}:{node.lineno} {node.func.attr}: {len(node.args)} arguments")
+    assert calls >= 80, calls
+    assert not bad, bad
+
+
 def test_library_exports_every_declared_symbol():
     import scanerf_amd  # noqa
     from scanerf_amd import _capi
@@ -28,9 +111,12 @@ def test_library_exports_every_declared_symbol():
     assert not missing, missing
     assert set(_capi.SYMBOLS) <= set(declared), sorted(set(_capi.SYMBOLS) - set(declared))
     assert set(_capi.OPTIONAL_SYMBOLS) <= set(declared) and not set(_capi.OPTIONAL_SYMBOLS) & set(_capi.SYMBOLS)
+    assert set(_capi.SYMBOLS) | set(_capi.OPTIONAL_SYMBOLS) == set(declared), sorted(set(declared) - set(_capi.SYMBOLS))
     assert lib.scanerf_abi_version() == 9
     lib.scanerf_last_error.restype = ctypes.c_char_p
     assert isinstance(lib.scanerf_last_error(), bytes)
+    typed = _capi.lib()
+    assert typed.scanerf_abi_version() == 9 and isinstance(typed.scanerf_last_error(), bytes)
 
 
 def test_built_library_carries_its_isa_audit_state():
@@ -50,17 +136,14 @@ def test_argument_validation_without_a_gpu():
     import scanerf_amd  # noqa
     from scanerf_amd import _capi
     lib = _capi.lib()
-    lib.scanerf_last_error.restype = ctypes.c_char_p
-    null = ctypes.c_void_p(0)
+    null = None
     assert lib.scanerf_embedding_bg_forward(null, null, null, null, 10, 16, 1000, 0, null) != 0  # T not a power of two
     assert b"power of two" in lib.scanerf_last_error()
     assert lib.scanerf_embedding_bg_forward(null, null, null, null, 10, 16, 1024, 0, null) != 0  # null pointers
     assert b"null" in lib.scanerf_last_error()
     assert lib.scanerf_embedding_bg_forward(null, null, null, null, 0, 16, 1024, 0, null) == 0   # empty batch is a no-op
     assert lib.scanerf_sample_points_grid(null, null, null, null, null, null, null, null, 0, 64, null) == 0
-    assert lib.scanerf_adam_step(null, null, null, null, ctypes.c_float(1e-3), ctypes.c_float(0.9), ctypes.c_float(0.99),
-                                 ctypes.c_float(1e-15), 0, ctypes.c_int64(5), 9, null) != 0  # rows are 8 wide
-    lib.scanerf_embedding_bwd_workspace_bytes.restype = ctypes.c_size_t
+    assert lib.scanerf_adam_step(null, null, null, null, 1e-3, 0.9, 0.99, 1e-15, 0, 5, 9, null) != 0  # rows are 8 wide
     assert lib.scanerf_embedding_bwd_workspace_bytes(65536 * 128, 16, 2 ** 19) > 8 << 30
     assert lib.scanerf_embedding_bwd_workspace_bytes(1000, 16, 2 ** 24) > 0   # large tables: one level's cursors at a time
     assert lib.scanerf_embedding_bwd_workspace_bytes(1000, 16, 2 ** 28) == 0  # too many buckets per level for the LDS
@@ -147,12 +230,10 @@ def test_round6_entry_points_validate_before_any_launch():
     import scanerf_amd  # noqa
     from scanerf_amd import _capi
     lib = _capi.lib()
-    lib.scanerf_last_error.restype = ctypes.c_char_p
-    null = ctypes.c_void_p(0)
-    f = ctypes.c_float
+    null = None
     rays = lambda B, S1: lib.scanerf_table_grad_scatter_adam_rays(null, null, B, null, null, null, S1, 0, null, null, null, 0, 0, null, null, null,
-                                                                  1 << 24, null, ctypes.c_size_t(0), null, null, null, null, 0, null, f(1e-2), f(0.9),
-                                                                  f(0.99), f(1e-15), 0, 0, null)
+                                                                  1 << 24, null, 0, null, null, null, null, 0, null, 1e-2, 0.9,
+                                                                  0.99, 1e-15, 0, 0, null)
     assert rays(0, 128) == 0
     assert rays(16, 128) != 0 and b"null" in lib.scanerf_last_error()
     assert rays(16, 0) != 0 and b"S1=0" in lib.scanerf_last_error()
@@ -162,5 +243,5 @@ def test_round6_entry_points_validate_before_any_launch():
     assert comp_f(0, 128) == 0 and comp_b(0, 128) == 0
     assert comp_f(4, 128) != 0 and b"null" in lib.scanerf_last_error()
     assert comp_b(4, 513) != 0 and b"S <= 512" in lib.scanerf_last_error()
-    assert lib.scanerf_embedding_bg_backward_binned(null, null, null, null, 100, 16, 1 << 19, 0, null, ctypes.c_size_t(0), 7, null) != 0
+    assert lib.scanerf_embedding_bg_backward_binned(null, null, null, null, 100, 16, 1 << 19, 0, null, 0, 7, null) != 0
     assert b"compact_records=7" in lib.scanerf_last_error()

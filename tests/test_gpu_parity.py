@@ -177,7 +177,6 @@ def test_embedding_bg_forward(S, N):
 
 
 def test_embedding_bg_forward_variants_and_dtypes(S):
-    import ctypes
     from scanerf_amd._capi import check, lib, stream
     rng = np.random.default_rng(5)
     N, L, T = 40000, 16, 2 ** 12
@@ -195,8 +194,7 @@ def test_embedding_bg_forward_variants_and_dtypes(S):
                     continue
                 out = torch.zeros((L, N, 2) if lm else (N, L, 2), device=DEV)
                 check(lib().scanerf_embedding_bg_forward_ex(
-                    ctypes.c_void_p(P.data_ptr()), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(F.data_ptr()),
-                    ctypes.c_void_p(R.data_ptr()), N, L, T, code, variant, lm, stream()), "embed_ex")
+                    P.data_ptr(), out.data_ptr(), F.data_ptr(), R.data_ptr(), N, L, T, code, variant, lm, stream()), "embed_ex")
                 got = out.permute(1, 0, 2).cpu().numpy() if lm else out.cpu().numpy()
                 np.testing.assert_allclose(got, refd, rtol=1e-5, atol=max(tol, 2e-6), err_msg=f"{dt} v{variant} lm{lm}")
 
@@ -319,7 +317,6 @@ def test_h3_backward_primitives(S):
     of the split-f16 arithmetic against float64."""
     from conftest import need_symbol
     need_symbol("scanerf_h3_selftest")
-    import ctypes
     from scanerf_amd import network, render
     from scanerf_amd._capi import check, lib, stream
     rng = np.random.default_rng(21)
@@ -328,7 +325,7 @@ def test_h3_backward_primitives(S):
     dy = rng.normal(size=(64, 32)).astype(np.float32)
     x = (rng.normal(size=(64, 32)) * rng.uniform(0.01, 2.0, (64, 1))).astype(np.float32)
     dx, dw, rs = torch.zeros(2, 64, 32, device=DEV), torch.zeros(64, 64, device=DEV), torch.zeros(64, device=DEV)
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    p = lambda t: t.data_ptr()
     DY, X = g(dy), g(x)
     check(lib().scanerf_h3_selftest(p(pk.workspace), p(DY), p(X), p(dx), p(dw), p(rs), stream()), "h3_selftest")
     W1 = sd["Spatial_MLP.mlp.2.weight"].double().numpy()
@@ -385,7 +382,6 @@ def test_render_forward_invalid_rays_and_table_dtypes(S):
 def test_binned_scatter_matches_oracle_and_atomics(S, layout, log2_T):
     """csrc/scatter.hip: the atomic-free table gradient == the oracle's sequential sum.  T = 2^22: large-table form
     (2^13-entry buckets, one level's cursors in LDS at a time)."""
-    import ctypes
     from scanerf_amd._capi import check, lib, stream, workspace
     rng = np.random.default_rng(11)
     N, L, T = (30011 if log2_T == 13 else 6007), 16, 2 ** log2_T
@@ -403,9 +399,8 @@ def test_binned_scatter_matches_oracle_and_atomics(S, layout, log2_T):
         ws = workspace(DEV, need)
         gf = torch.zeros(L, T, 2, device=DEV)
         check(lib().scanerf_embedding_bg_backward_binned(
-            ctypes.c_void_p(P.data_ptr()), ctypes.c_void_p(gi.data_ptr()), ctypes.c_void_p(gf.data_ptr()),
-            ctypes.c_void_p(R.data_ptr()), N, L, T, layout, ctypes.c_void_p(ws.data_ptr()),
-            ctypes.c_size_t(ws_bytes), ctypes.c_int(-1), stream()), "binned")
+            P.data_ptr(), gi.data_ptr(), gf.data_ptr(), R.data_ptr(), N, L, T, layout, ws.data_ptr(), ws_bytes, -1,
+            stream()), "binned")
         np.testing.assert_allclose(gf.cpu().numpy(), gf_ref, rtol=1e-3, atol=3e-4)
 
 
@@ -1059,7 +1054,6 @@ def _overflow_table_case(tol):
     from scanerf_amd import render
     from scanerf_amd._capi import lib
     from scanerf_amd.tile_model import TileModel
-    import ctypes
     B, S_ = 2000, 64
     res = {}
     for tag in ("full", "small"):
@@ -1068,7 +1062,7 @@ def _overflow_table_case(tol):
             m.features.mul_(30.0)
         P = m.features.data
         M, V = torch.zeros_like(P), torch.zeros_like(P)
-        need = lib().scanerf_render_scatter_workspace_bytes(ctypes.c_int(B), ctypes.c_int(S_), ctypes.c_int(P.shape[1]))
+        need = lib().scanerf_render_scatter_workspace_bytes(B, S_, P.shape[1])
         wsbuf = torch.empty(need if tag == "full" else need // 3, dtype=torch.uint8, device=DEV)
         ws, overflow = _emit_records(m, B, S_, 77, workspace=wsbuf)
         if tag == "small":
@@ -1208,7 +1202,6 @@ def test_rec8_codec_against_its_restatement(S):
     that round up to the next power of two, one-entry records (k = 15)."""
     from conftest import need_symbol
     need_symbol("scanerf_rec8_selftest")
-    import ctypes
     from scanerf_amd._capi import check, lib, stream
     rng = np.random.default_rng(21)
     n = 20000
@@ -1229,9 +1222,9 @@ def test_rec8_codec_against_its_restatement(S):
     k[::7] = 15
     words = torch.zeros(n, 2, dtype=torch.int32, device=DEV)
     out = torch.zeros(n, 8, device=DEV)
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    p = lambda t: t.data_ptr()
     dev = [g(v) if v.dtype == np.float32 else torch.from_numpy(v.astype(np.int32)).to(DEV) for v in (gx, gy, tx, l0, k)]
-    check(lib().scanerf_rec8_selftest(*(p(t) for t in dev), ctypes.c_int(n), p(words), p(out), stream()), "rec8_selftest")
+    check(lib().scanerf_rec8_selftest(*(p(t) for t in dev), n, p(words), p(out), stream()), "rec8_selftest")
     torch.cuda.synchronize()
     o = out.cpu().numpy().astype(np.float64)
     # restatement
@@ -1270,7 +1263,6 @@ def test_forward_counts_the_scatter_plan(S, monkeypatch):
     Same workspace head (counts, totals, starts, format word, flags) as scatter_plan, same outputs; and the training step
     that uses it moves the table bit-identically to the one with the separate plan launch.  Rays that miss (ray_valid = 0),
     a sample count that is not a multiple of 32, the contracted background branch."""
-    import ctypes
     from scanerf_amd import network, render
     from scanerf_amd._capi import lib
     from scanerf_amd.tile_model import TileModel, train_step_fused
@@ -1289,7 +1281,7 @@ def test_forward_counts_the_scatter_plan(S, monkeypatch):
         assert render.forward_plan_supported(B, S_, T)
         m.packed.pack(m.decoder.blob(), network.weight_feature(3000, DEV))
         box = (m.min_bbox.tolist(), m.bbox_size.tolist(), mode, inf)
-        need = lib().scanerf_render_scatter_workspace_bytes(ctypes.c_int(B), ctypes.c_int(S_), ctypes.c_int(T))
+        need = lib().scanerf_render_scatter_workspace_bytes(B, S_, T)
         wa, wb = (torch.zeros(need, dtype=torch.uint8, device=DEV) for _ in range(2))
         render.scatter_plan(o, d, z, m.resolution, T, *box, ray_valid=valid, arith=render._capi.ARITH_T16, workspace=wa)
         out_a, w_a = render.render_forward(o, d, z, dist, m.features, m.resolution, m.packed, *box, ray_valid=valid)
@@ -1297,7 +1289,7 @@ def test_forward_counts_the_scatter_plan(S, monkeypatch):
                                                plan=True, plan_workspace=wb)
         torch.cuda.synchronize()
         assert ws is wb and torch.equal(out_a, out_b) and torch.equal(w_a, w_b)
-        nbins, W = 16 * max(1, T >> 13), lib().scanerf_render_backward_grid(ctypes.c_int(B))
+        nbins, W = 16 * max(1, T >> 13), lib().scanerf_render_backward_grid(B)
         head = ((nbins * W + 2 * nbins + 4) * 4 + 255) & ~255
         assert int(wa[:head].view(torch.int32)[nbins * W:nbins * W + nbins].sum()) > 0      # totals
         assert torch.equal(wa[:head], wb[:head])
@@ -1606,7 +1598,6 @@ def test_large_table_producer_writes_whole_segments(S, layout, log2_T, N):
     bit-equal between the two: over several records per bucket and batch (300 007 points), points on the upper faces (x + 1 in the
     next bucket at T = 2^22), fewer points than one batch per workgroup (777), point-major rows (layout 0: the old producer keeps
     16-byte records there, so equal to the records' rounding) -- and the first moment follows the oracle's sequential scatter."""
-    import ctypes
     from scanerf_amd._capi import check, lib, stream, workspace
     rng = np.random.default_rng(61)
     L, T = 16, 2 ** log2_T
@@ -1628,10 +1619,8 @@ def test_large_table_producer_writes_whole_segments(S, layout, log2_T, N):
         over = torch.zeros(L, T, 2, device=DEV)
         for step in range(2):
             check(lib().scanerf_embedding_bg_backward_binned_adam(
-                ctypes.c_void_p(P.data_ptr()), ctypes.c_void_p(gi.data_ptr()), ctypes.c_void_p(R.data_ptr()), N, L, T, layout,
-                ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws_bytes), ctypes.c_void_p(params.data_ptr()),
-                ctypes.c_void_p(m1.data_ptr()), ctypes.c_void_p(m2.data_ptr()), None, 0, ctypes.c_void_p(over.data_ptr()),
-                ctypes.c_float(1e-2), ctypes.c_float(0.9), ctypes.c_float(0.99), ctypes.c_float(1e-15), step, 2, stream()), "binned_adam")
+                P.data_ptr(), gi.data_ptr(), R.data_ptr(), N, L, T, layout, ws.data_ptr(), ws_bytes, params.data_ptr(),
+                m1.data_ptr(), m2.data_ptr(), None, 0, over.data_ptr(), 1e-2, 0.9, 0.99, 1e-15, step, 2, stream()), "binned_adam")
         assert not bool(over.any())
         out[ws_bytes] = (params.clone(), m1.clone(), m2.clone())
     for a, b in zip(out[need], out[small]):
