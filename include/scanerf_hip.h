@@ -492,6 +492,42 @@ int scanerf_decoder_backward(const float *feats, int ld_feats, const float *dirs
                              const float *g_tint, float *d_feats, int ld_dfeats, float *d_dirs, int ld_ddirs, float *dw_partial,
                              float *grad_blob, long long N, scanerf_stream_t stream);
 
+/* ---- multi-view warp loss (csrc/warp.hip): warp_loss.py:147-660 WarpLoss.__call__ and cuda/view_selection_kernel.cu:19-349,
+ * without the host round trips of the reference (its sample_neighbor_color indexes the images on the CPU every step).
+ *   Rays: rays_o, rays_d [B,3]; ray_q [B,7] = (depth, diffuse[3], specular[3]) of the merged prediction (tile.py:666-690); the point
+ *   is p = rays_o + depth * rays_d (warp_loss.py:548).  ray_valid [B] (NULL = all) marks the rays the loss counts (criterions.py:
+ *   101-110: fore_valid | bg_valid).  Cameras: ks [N,3,3], rts [N,3,4] world-to-camera.  K slots per ray, 1 <= K <=
+ *   scanerf_warp_max_neighbors() and K <= N (the reference's topk(k=10) raises when N < 10: callers pass min(10, N)).
+ * scanerf_warp_select_views -- replaces computeViewcost (view_selection_kernel.cu:19-72) + topk + the 0.176 threshold
+ *   (warp_loss.py:390-413): the K cameras of lowest cost per ray (ties: lower index first), cost in nei_cost [B,K], nei_valid [B,K]
+ *   = cost <= 0.176 (0 for rays outside ray_valid).  No [N,B] cost matrix. */
+int scanerf_warp_max_neighbors(void);
+int scanerf_warp_select_views(const float *rays_o, const float *rays_d, const float *ray_q, const uint8_t *ray_valid,
+                              const float *ks, const float *rts, int N, int H, int W, int K, int B, int *nei_views,
+                              float *nei_cost, uint8_t *nei_valid, scanerf_stream_t stream);
+/* scanerf_warp_project -- replaces proj2neighbor_forward (view_selection_kernel.cu:115-211, warp_loss.py:415-439) and
+ *   sample_neighbor_color (warp_loss.py:441-521): per (ray, slot) grid [B,K,2] = K (R p + t) .xy / (.z + 1e-8) - 0.5,
+ *   proj_depth [B,K] = .z, nei_origin / nei_direction [B,K,3] = the neighbour camera's centre and R^T (x/(z+1e-8), y/(z+1e-8), 1)
+ *   of the camera-space point, nei_color [B,K,3] = bilinear from images [N,H,W,3] f32 with the top-left corner at trunc(grid),
+ *   nei_valid = nei_valid_in AND occlusions [N,H,W] (NULL = all true) at trunc(grid + 0.5).  Invalid slots are zero-filled. */
+int scanerf_warp_project(const float *rays_o, const float *rays_d, const float *ray_q, const float *ks, const float *rts,
+                         const int *nei_views, const uint8_t *nei_valid_in, const float *images, const uint8_t *occlusions, int N,
+                         int H, int W, int K, int B, float *grid, float *proj_depth, float *nei_origin, float *nei_direction,
+                         float *nei_color, uint8_t *nei_valid, scanerf_stream_t stream);
+/* scanerf_warp_loss_grad -- replaces compute_loss (warp_loss.py:332-337, :650-656) with its autograd and proj2neighbor_backward
+ *   (view_selection_kernel.cu:214-349): loss [1] = scale / (n K) * sum over valid slots of score [B,K] * mean_c((clamp(diffuse +
+ *   specular, 0, 1) - nei_color)^2), n = number of valid rays; grad_q [B,7] = dL/d(ray_q), grad_o / grad_d [B,3] = dL/d(rays_o,
+ *   rays_d) through p, grad_rts [N,12] = dL/d(rts) (overwritten).  The colour's gradient reaches grid through the bilinear weights
+ *   and p / rts through the projection Jacobian in the same launch.  grad_rts is summed in a fixed order (per-(ray, slot) partials,
+ *   then per (camera, chunk) and chunk by chunk), not with the reference's float atomics: bit-reproducible.  scratch: scanerf_warp_scratch_floats
+ *   (B, K, N) floats.  grid / nei_color / nei_valid as scanerf_warp_project wrote them. */
+size_t scanerf_warp_scratch_floats(int B, int K, int N);
+int scanerf_warp_loss_grad(const float *rays_o, const float *rays_d, const float *ray_q, const uint8_t *ray_valid, const float *ks,
+                           const float *rts, const int *nei_views, const uint8_t *nei_valid, const float *grid,
+                           const float *nei_color, const float *score, const float *images, int N, int H, int W, int K, int B,
+                           float scale, float *loss, float *grad_q, float *grad_o, float *grad_d, float *grad_rts, float *scratch,
+                           size_t scratch_floats, scanerf_stream_t stream);
+
 #define SCANERF_RAY_OUT 16
 
 #ifdef __cplusplus

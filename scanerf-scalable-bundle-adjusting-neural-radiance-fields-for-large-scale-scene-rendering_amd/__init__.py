@@ -7,6 +7,7 @@ Layout (mirrors the reference's operator surface for this path, nothing else):
   render.py        fused fast path (one launch per render_batch_rays)
   network.py       ShallowMLP mirror + decoder-blob packing
   consensus.py     ADMM camera consensus as an RCCL all-reduce
+  warp.py          multi-view warp loss (warp_loss.py) on csrc/warp.hip
   csrc/            HIP kernels + the C ABI (include/scanerf_hip.h) -> lib/libscanerf_hip.so
 
 The directory name is not a Python identifier; import it through the `scanerf_amd`

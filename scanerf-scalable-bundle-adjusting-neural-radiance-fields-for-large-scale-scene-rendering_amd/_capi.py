@@ -89,6 +89,11 @@ PROTOTYPES = {
     "scanerf_decoder_forward": ("I", "PIPIPPPPPLP", REQ),
     "scanerf_decoder_backward_grid": ("I", "L", REQ),
     "scanerf_decoder_backward": ("I", "PIPIPPPPPPPIPIPPLP", REQ),
+    "scanerf_warp_max_neighbors": ("I", "", REQ),
+    "scanerf_warp_select_views": ("I", "PPPPPPIIIIIPPPP", REQ),
+    "scanerf_warp_project": ("I", "PPPPPPPPPIIIIIPPPPPPP", REQ),
+    "scanerf_warp_scratch_floats": ("Z", "III", REQ),
+    "scanerf_warp_loss_grad": ("I", "PPPPPPPPPPPPIIIIIFPPPPPPZP", REQ),
 }
 SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if required]
 OPTIONAL_SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if not required]

@@ -406,13 +406,15 @@ JSTASH = True               # pose gradients: the forward stashes the encoder's 
 
 def train_step_fused(model, dec_opt, rays_o, rays_d, target, S, global_step, table_lr=1e-2, timer=None,
                      pose_grads=False, fused_scatter=None, compact_rays=None, overlap_plan=False, dec_step=True,
-                     fused_adam=True):
+                     fused_adam=True, warp=None):
     """The same iteration as train_step_ops on the fused kernels: one launch for the render forward,
     one for its adjoint, the atomic-free binned scatter for the table gradient, fused sparse Adam.
     fused_adam (default): the sparse Adam on the table runs in the accumulate's epilogue (no gradient table, model.features.grad
     is NOT set); False keeps accumulate -> model.features.grad -> adam_step_cuda (the binding-surface op).
     pose_grads=True also returns dL/d(rays_o), dL/d(rays_d) (feed them to the pose graph:
-    torch.autograd.backward([rays_o, rays_d], [g_o, g_d]) -- camera_utils.py:65-84 in the reference)."""
+    torch.autograd.backward([rays_o, rays_d], [g_o, g_d]) -- camera_utils.py:65-84 in the reference).
+    warp (warp.WarpLoss, default None): the multi-view warp term joins the loss; its gradient is added to grad_out before the
+    backward (and to the ray gradients with pose_grads), its dL/drts is left in warp.last_grad_rts."""
     B = rays_o.shape[0]
     dev = model.device
     with torch.no_grad():
@@ -482,6 +484,11 @@ def train_step_fused(model, dec_opt, rays_o, rays_d, target, S, global_step, tab
                                                ray_valid=valid, want_weights=False, tile_T=tile_T, xstash=xstash)
     # loss and dL/d(out_ray) in two launches (the torch graph for it was ~60 tiny kernels with host-bound gaps)
     loss, grad_out = render.photometric_loss_grad(out, target, valid, 0.01)
+    wterm = None
+    if warp is not None:
+        with _sec(timer, "warp_loss"):
+            wterm = warp.fused_term(global_step, rays_o, rays_d, out, valid, grad_out,
+                                    lambda o, d: _visibility_render_fore(model, o, d, S, global_step))
     with torch.no_grad():
         # the scatter ends in the Adam epilogue: no gradient table (only the overflow table, never filled per step)
         adam_epilogue = fused_adam
@@ -508,6 +515,8 @@ def train_step_fused(model, dec_opt, rays_o, rays_d, target, S, global_step, tab
         elif pose_grads:
             g_o, g_d = render.ray_gradients(rays_o, rays_d, z, model.features, model.resolution, blob, box[0], box[1],
                                             box[2], dfeat, ray_bufs[0], ray_bufs[1], ray_valid=valid)
+        if pose_grads and wterm is not None:
+            g_o, g_d = g_o + wterm[1], g_d + wterm[2]
         if adam_epilogue and fused:
             with _sec(timer, "table_grad_accumulate_adam", B * S * 16 * 64 + model.features.numel() * 28):
                 render.scatter_accumulate_adam(ws, model.features.data, model.exp_avg, model.exp_avg_sq, table_lr, 0.9, 0.99, 1e-15,
@@ -545,18 +554,36 @@ def train_step_fused(model, dec_opt, rays_o, rays_d, target, S, global_step, tab
         model.decoder.params.grad = gblob
         if dec_step:  # False: the caller steps the optimiser itself (it holds more parameter groups: camera poses)
             dec_opt.step()
+    if wterm is not None:
+        loss = loss + wterm[0]
     return (loss[0], g_o, g_d) if pose_grads else loss[0]
 
 
+# ---- the warp term's visibility render (warp_loss.py:355-378: the tile's renderer on the neighbour rays, no grad) ---------------
+# Fresh sample / output buffers and no plan workspace: the training forward's stashes (xstash, tile_T, jstash, record workspace),
+# which the backward still reads, are left alone.  The decoder re-pack writes what the training step packed (same blob, same mask).
+@torch.no_grad()
+def _visibility_render_fore(model, rays_o, rays_d, S, global_step):
+    out, _, _ = model.render_fore_fused(rays_o, rays_d, S, global_step)
+    return out[:, render.DEPTH], out[:, render.SPECULAR]
+
+
+@torch.no_grad()
+def _visibility_render_fgbg(model, rays_o, rays_d, S_fg, S_bg, global_step, invalid_underground):
+    r = model.render_rays_fused(rays_o, rays_d, S_fg, S_bg, global_step, invalid_underground)
+    return r["pred_depth"][:, 0], r["pred_specular"]
+
+
 def fgbg_gradients(model, rays_o, rays_d, target, S_fg, S_bg, global_step, invalid_underground=False, timer=None,
-                   pose_grads=False, collect=None, collect_rays=False):
+                   pose_grads=False, collect=None, collect_rays=False, warp=None):
     """Loss and parameter gradients of the complete per-tile render of tile.py:639-692 / :880-1015: foreground
     (occupancy-sampled, contract_fore) + T_left * background (inverse-z, contract_bg, infinity), MSE on the merged colour
     over all rays + 0.01 * (l2_reg_specular of both branches) -- two fused forward/backward pairs over the same table and
     decoder.  Returns (loss, grad_table [16,T,2], grad_blob [13994]) (+ dL/d(rays_o), dL/d(rays_d) with pose_grads: t16
     backward on the fp32 table, any table size).  collect: a list that receives (contracted points [N,3], dfeat [16,N,2]) of
     each branch INSTEAD of their scatter into the gradient table (the caller scatters them together: large tables); with
-    collect_rays it receives (z [B,S], dfeat, ray_valid, contract mode) -- the input of render.scatter_table_grad_adam_rays."""
+    collect_rays it receives (z [B,S], dfeat, ray_valid, contract mode) -- the input of render.scatter_table_grad_adam_rays.
+    warp: as in train_step_fused, on the merged prediction (warp.WarpLoss.fgbg_term)."""
     B = rays_o.shape[0]
     dev = model.device
     T = model.features.shape[1]
@@ -585,6 +612,13 @@ def fgbg_gradients(model, rays_o, rays_d, target, S_fg, S_bg, global_step, inval
     # merge and loss on the per-ray outputs (tile.py:666-690; criterions.py:142-144; tile.py:999), two HIP launches
     vf, vbg = branches[0][2], branches[1][2]
     loss, gfg, gbg = render.photometric_loss_grad_fgbg(outs[0], outs[1], target, vf, vbg, 0.01)
+    wterm = None
+    if warp is not None:
+        with _sec(timer, "warp_loss"):
+            wterm = warp.fgbg_term(global_step, rays_o, rays_d, outs[0], outs[1], vf, vbg, gfg, gbg,
+                                   lambda o, d: _visibility_render_fgbg(model, o, d, S_fg, S_bg, global_step, invalid_underground))
+        if wterm is not None:
+            loss = loss + wterm[0]
 
     class _Leaf:  # (what the loop below reads from the former autograd leaves)
         def __init__(self, g):
@@ -621,18 +655,22 @@ def fgbg_gradients(model, rays_o, rays_d, target, S_fg, S_bg, global_step, inval
                     collect.append((pts.contiguous(), dfeat))
                 else:
                     render.scatter_table_grad(pts.contiguous(), dfeat, gtab, model.resolution)
+        if pose_grads and wterm is not None:
+            g_o, g_d = g_o + wterm[1], g_d + wterm[2]
     return (loss[0].detach(), gtab, gblob, g_o, g_d) if pose_grads else (loss[0].detach(), gtab, gblob)
 
 
 def train_step_fgbg(model, dec_opt, rays_o, rays_d, target, S_fg, S_bg, global_step, table_lr=1e-2,
-                    invalid_underground=False, timer=None, pose_grads=False, dec_step=True):
+                    invalid_underground=False, timer=None, pose_grads=False, dec_step=True, warp=None):
     """One complete training iteration of a tile (tile.py:880-1015: foreground + T_left * background, tile.py:639-692) on the
     fused kernels: both branches' forward, ONE loss launch pair for the merged prediction, both branches' backward emitting
     their scatter records, and ONE accumulate + sparse Adam over both record sets (the two gradients meet in one Adam step).
     Falls back to gradient tables + adam_step_cuda where the fused scatter does not apply (tables above 2^21 entries).
     pose_grads=True (fp32 tables, t16 backward): also returns dL/d(rays_o), dL/d(rays_d) of the merged prediction -- the sum of
     the two branches' ray gradients, each formed inside its backward launch from the forward's position Jacobians
-    (-> (loss, g_o, g_d)); dec_step=False: the caller steps the decoder's optimiser (it holds the camera parameters too)."""
+    (-> (loss, g_o, g_d)); dec_step=False: the caller steps the decoder's optimiser (it holds the camera parameters too).
+    warp (warp.WarpLoss, default None): the multi-view warp term on the merged prediction, chained to both branches before their
+    backward (see train_step_fused)."""
     B = rays_o.shape[0]
     dev = model.device
     T = model.features.shape[1]
@@ -647,7 +685,7 @@ def train_step_fgbg(model, dec_opt, rays_o, rays_d, target, S_fg, S_bg, global_s
         parts = [] if binned else None
         by_rays = binned and render.scatter_rays_supported(T, render.backward_arith())
         r = fgbg_gradients(model, rays_o, rays_d, target, S_fg, S_bg, global_step, invalid_underground, timer, pose_grads=pose_grads,
-                           collect=parts, collect_rays=by_rays)
+                           collect=parts, collect_rays=by_rays, warp=warp)
         loss, gtab, gblob = r[:3]
         with torch.no_grad():
             if by_rays:
@@ -700,6 +738,11 @@ def train_step_fgbg(model, dec_opt, rays_o, rays_d, target, S_fg, S_bg, global_s
             outs.append(r[0])
             state.append((tile_T, xs, r[2] if in_fwd else None, js))
         loss, gfg, gbg = render.photometric_loss_grad_fgbg(outs[0], outs[1], target, vf, vb, 0.01)
+        wterm = None
+        if warp is not None:
+            with _sec(timer, "warp_loss"):
+                wterm = warp.fgbg_term(global_step, rays_o, rays_d, outs[0], outs[1], vf, vb, gfg, gbg,
+                                       lambda o, d: _visibility_render_fgbg(model, o, d, S_fg, S_bg, global_step, invalid_underground))
         gblob = torch.zeros(network.PARAMSIZE, device=dev)
         overflow = model.overflow_grad()
         wss = []
@@ -718,6 +761,8 @@ def train_step_fgbg(model, dec_opt, rays_o, rays_d, target, S_fg, S_bg, global_s
                 go_b, gd_b = render.ray_gradients_fused(rays_o, rays_d, model.decoder.blob().detach(), rp, bufs[0], bufs[1], ray_valid=v_)
                 g_o, g_d = (go_b, gd_b) if g_o is None else (g_o + go_b, g_d + gd_b)
             wss.append(ws)
+        if pose_grads and wterm is not None:
+            g_o, g_d = g_o + wterm[1], g_d + wterm[2]
         with _sec(timer, "table_grad_accumulate_adam", B * (S_fg + S_bg) * 16 * 64 + model.features.numel() * 28):
             render.scatter_accumulate_adam2(wss[0], S_fg, wss[1], S_bg, model.features.data, model.exp_avg, model.exp_avg_sq,
                                             table_lr, 0.9, 0.99, 1e-15, model.adam_step, B, half_table=model._half_table,
@@ -726,4 +771,6 @@ def train_step_fgbg(model, dec_opt, rays_o, rays_d, target, S_fg, S_bg, global_s
         model.decoder.params.grad = gblob
         if dec_step:
             dec_opt.step()
+    if wterm is not None:
+        loss = loss + wterm[0]
     return (loss[0], g_o, g_d) if pose_grads else loss[0]

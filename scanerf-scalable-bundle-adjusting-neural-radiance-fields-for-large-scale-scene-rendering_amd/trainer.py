@@ -1,7 +1,8 @@
 """Training harness around the fused kernels: what TILE.create_optimizer / train / train_one_step (tile.py:296-332,
 :818-877, :880-1015) and HashGrid.pruning_grid (hashgrid/__init__.py:138-225) do around the hot path -- learning-rate
 schedules, 2x2 patch ray selection, the coarse-to-fine occupancy pruning schedule, checkpoints -- for one tile on one GPU.
-Data loading, warp / monocular losses and image logging stay outside (out of scope).
+The multi-view warp loss of the default configuration (warp_loss.py, criterions.py:92-97) joins the iteration with
+TileTrainer(warp=warp.WarpLoss(...)).  Data loading, the monocular losses and image logging stay outside.
 """
 import math
 
@@ -163,12 +164,14 @@ class TileTrainer:
     def __init__(self, model, get_batch, total_step=40000, eta_hash=1e-2, eta_decoder=1e-3, grid_log2dim=(4, 5, 6, 7, 8, 9),
                  pruning_th=(0.1, 0.2, 0.3, 0.4), adjust_step=2000, dynamic_start=None, dynamic_end=None, dynamic_step=None,
                  num_sample=128, num_bg_sample=0, finest_resolution=2048, consensus=None, cameras=None, eta_cam=1e-3,
-                 cam_start_step=0, admm=False):
+                 cam_start_step=0, admm=False, warp=None):
         """cameras (cameras.CameraSet): pose refinement on -- get_batch(step) then returns (locs [B,3] int32 (view, px, py),
         target [B,3]) and the rays are generated from the current poses; se3_refine is the optimiser's second parameter
         group with its own schedule (tile.py:316-323).  admm: add the consensus penalty (consensus.py:70-76) to the
-        pose gradient."""
+        pose gradient.  warp (warp.WarpLoss): the multi-view warp term is added to every iteration (criterions.py:92-97); with
+        cameras, its gradient w.r.t. the neighbour cameras' rts is fed to se3_refine as well.  None (default): no warp term."""
         self.model, self.get_batch = model, get_batch
+        self.warp = warp
         self.cameras, self.admm = cameras, admm
         groups = [{"params": model.decoder.parameters(), "lr": eta_decoder, "weight_decay": 1e-6}]
         sches = [Scheduler("decoder", eta_decoder, 0.1 * eta_decoder, total_step, groups=[0])]
@@ -207,15 +210,22 @@ class TileTrainer:
         if self.num_bg_sample > 0:   # the complete iteration (foreground + T_left * background), tile.py:639-692
             loss, g_o, g_d = train_step_fgbg(self.model, self.dec_opt, rays_o.detach(), rays_d.detach(), target, self.num_sample,
                                              self.num_bg_sample, self.global_step, table_lr=self.table_lr, pose_grads=True,
-                                             dec_step=False)
+                                             dec_step=False, **self._warp_kw())
         else:
             loss, g_o, g_d = train_step_fused(self.model, self.dec_opt, rays_o.detach(), rays_d.detach(), target, self.num_sample,
-                                              self.global_step, table_lr=self.table_lr, pose_grads=True, dec_step=False)
+                                              self.global_step, table_lr=self.table_lr, pose_grads=True, dec_step=False,
+                                              **self._warp_kw())
         torch.autograd.backward([rays_o, rays_d], [g_o, g_d])
+        if self.warp is not None and self.warp.last_grad_rts is not None:
+            # the neighbour cameras' share of the warp gradient (proj2neighbor_backward's grad_rts) -> se3_refine
+            torch.autograd.backward(cams.get_rts(), self.warp.last_grad_rts)
         if self.admm and self.consensus is not None and bool(self.consensus.overlap_flags.any()):
             self.consensus.camera_loss(cams.se3_refine).backward()
         self.dec_opt.step()
         return loss
+
+    def _warp_kw(self):
+        return {} if self.warp is None else {"warp": self.warp}
 
     def train_one_step(self):
         if self.cameras is not None:
@@ -228,10 +238,10 @@ class TileTrainer:
         rays_o, rays_d, target = self.get_batch(self.global_step)
         if self.num_bg_sample > 0:
             loss = train_step_fgbg(self.model, self.dec_opt, rays_o, rays_d, target, self.num_sample, self.num_bg_sample,
-                                   self.global_step, table_lr=self.table_lr)
+                                   self.global_step, table_lr=self.table_lr, **self._warp_kw())
         else:
             loss = train_step_fused(self.model, self.dec_opt, rays_o, rays_d, target, self.num_sample, self.global_step,
-                                    table_lr=self.table_lr)
+                                    table_lr=self.table_lr, **self._warp_kw())
         # the reference steps its schedulers AFTER the optimisers: the rate computed at step s is used at step s+1
         self.table_sche.step(self.global_step)
         self.table_lr = self.table_sche.scheduler_list[0].eta
