@@ -371,20 +371,28 @@ def scatter_table_grad_adam(points, dfeat, resolutions, params, exp_avg, exp_avg
         beta2, eps, step, int(compact_records), stream()), "scatter_table_grad_adam")
 
 
-RAYS_SCATTER = True   # (False: tile_model builds contracted points in torch and concatenates the branches, as rounds 1-5 did)
-
-
 def scatter_rays_supported(T, arith_code):
-    """scatter_table_grad_adam_rays applies: tables of at least 2^22 entries per level (one level's counters in the producer's LDS
-    at a time) behind the f32-grade backward (12-byte records)."""
-    return T >= (1 << 22) and compact_record_format(arith_code) == 2 and RAYS_SCATTER
+    """scatter_table_grad_adam_rays applies: tables of 2^22 to 2^24 entries per level behind the f32-grade backward (12-byte
+    records).  Both bounds are csrc/scatter.hip binned_backward's seg_route, which the rays entry requires: one level's
+    counters in the producer's LDS at a time (L * NB * 4 > 64 KiB), and NB <= 2048 buckets of 2^13 entries."""
+    return (1 << 22) <= T <= (1 << 24) and compact_record_format(arith_code) == 2
+
+
+def contracted_points(rays_o, rays_d, z_vals, min_bbox, bbox_size, contract_mode):
+    """[B*S,3] hash-grid coordinates of the samples o + z d (device tensors min_bbox / bbox_size: the 2x box):
+    (p - min) / size * 4 - 2, and for the background branch the L-inf fold p (2 - 1/|p|inf) / |p|inf (contract_bg)."""
+    pts = ((rays_o[:, None, :] + z_vals[:, :, None] * rays_d[:, None, :]).reshape(-1, 3) - min_bbox) / bbox_size * 4.0 - 2.0
+    if contract_mode == BG:
+        linf = pts.abs().amax(-1, keepdim=True)
+        pts = pts * ((2.0 - 1.0 / linf) / linf)
+    return pts.contiguous()
 
 
 def scatter_table_grad_adam_rays(rays_o, rays_d, branches, min_bbox, bbox_size, resolutions, params, exp_avg, exp_avg_sq, lr, beta1,
-                                 beta2, eps, step, half_table=None, overflow_grad=None, fp16_moments=False):
+                                 beta2, eps, step, overflow_grad, half_table=None, fp16_moments=False):
     """The table gradient of one or two render branches over the same rays, scattered and applied by ONE sparse Adam step
     (scanerf_table_grad_scatter_adam_rays; tile.py:639-692, :1010).  branches: [(z [B,S], dfeat [16,B*S,2], ray_valid [B] or None,
-    contract mode FORE / BG), ...] -- no contracted-point tensors, no concatenation.
+    contract mode FORE / BG), ...] -- no contracted-point tensors, no concatenation.  overflow_grad: zero table like params.
     fp16_moments (opt-in): exp_avg / exp_avg_sq are float16 tensors, the update is adam_step_cuda_fp16's (cuda/adam_kernel.cu:98-144)."""
     mdt = torch.float16 if fp16_moments else _f32
     B, T = rays_o.shape[0], params.shape[1]
@@ -526,9 +534,13 @@ class FusedRenderRays(torch.autograd.Function):
         # configs[1]) where the table gradient will go through the fused records -- into a workspace this call OWNS until its
         # backward has run (other render calls may come between the two and use the per-stream one).
         T = table.shape[1]
+        from . import tile_model   # (it imports this module)
+        ctx.route = ctx.compact = None   # (no table gradient wanted: no route)
+        if ctx.needs_input_grad[4]:
+            (ctx.route,), ctx.compact = tile_model.table_grad_route(tile_model.AUTOGRAD, T, B, [S], backward_arith(True, need_rays))
         own_ws = None
-        if (FORWARD_PLAN_IN_AUTOGRAD and ctx.needs_input_grad[4] and T <= (1 << 21) and scatter_supported(B, S, T)
-                and forward_plan_supported(B, S, T) and backward_arith(True, need_rays) in _capi.T16_FAMILY):
+        if (FORWARD_PLAN_IN_AUTOGRAD and ctx.route == tile_model.RECORDS_TABLE and forward_plan_supported(B, S, T)
+                and backward_arith(True, need_rays) in _capi.T16_FAMILY):
             own_ws = torch.empty(lib().scanerf_render_scatter_workspace_bytes(B, S, T),
                                  dtype=torch.uint8, device=dev)
         r = render_forward(rays_o, rays_d, z_vals, dists, table, resolutions, packed, min_bbox, bbox_size, contract_mode,
@@ -555,7 +567,8 @@ class FusedRenderRays(torch.autograd.Function):
         need_table = ctx.needs_input_grad[4]
         grad_out = grad_out.contiguous().to(_f32)
         arith = backward_arith(True, need_rays)
-        fused = need_table and T <= (1 << 21) and scatter_supported(B, S, T)
+        from . import tile_model
+        fused = ctx.route == tile_model.RECORDS_TABLE
         gtab = torch.zeros((16, T, 2), dtype=_f32, device=dev) if need_table else None
         gblob = torch.zeros(_capi.PARAMSIZE, dtype=_f32, device=dev)
         ws = None
@@ -567,13 +580,10 @@ class FusedRenderRays(torch.autograd.Function):
         ntile = (S + 31) // 32
         bufs = (torch.zeros(B, ntile, device=dev), torch.zeros(B, 2, 64, device=dev)) if need_rays else None
         rp = torch.zeros(B, 6, device=dev) if (need_rays and jstash is not None) else None
-        want_dfeat = (need_table and not fused) or (need_rays and jstash is None)
-        if not fused and not want_dfeat:
-            want_dfeat = True   # (the kernel needs somewhere to put the feature gradients)
         dfeat, _ = render_backward(rays_o, rays_d, z_vals, dists, table, resolutions, ctx.packed, wf, *box, out, tile_T,
                                    grad_out, ray_valid=ray_valid, grad_blob=gblob, xstash=xstash, ray_grad_buffers=bufs,
-                                   scatter=(ws, gtab) if fused else None, want_dfeat=want_dfeat, arith=arith, jstash=jstash,
-                                   ray_pos_grad=rp)
+                                   scatter=(ws, gtab) if fused else None, want_dfeat=not fused or (need_rays and jstash is None),
+                                   arith=arith, jstash=jstash, ray_pos_grad=rp)
         g_o = g_d = None
         if need_rays and jstash is not None:
             g_o, g_d = ray_gradients_fused(rays_o, rays_d, blob, rp, bufs[0], bufs[1], ray_valid=ray_valid)
@@ -583,13 +593,9 @@ class FusedRenderRays(torch.autograd.Function):
         if fused:
             scatter_accumulate(ws, gtab, B, S)
         elif need_table:
-            mn = torch.as_tensor(box[0], dtype=_f32, device=dev)
-            sz = torch.as_tensor(box[1], dtype=_f32, device=dev)
-            pts = ((rays_o[:, None, :] + z_vals[:, :, None] * rays_d[:, None, :]).reshape(-1, 3) - mn) / sz * 4.0 - 2.0
-            if box[2] == BG:
-                linf = pts.abs().amax(-1, keepdim=True)
-                pts = pts * ((2.0 - 1.0 / linf) / linf)
-            scatter_table_grad(pts.contiguous(), dfeat, gtab, resolutions)
+            pts = contracted_points(rays_o, rays_d, z_vals, torch.as_tensor(box[0], dtype=_f32, device=dev),
+                                    torch.as_tensor(box[1], dtype=_f32, device=dev), box[2])
+            scatter_table_grad(pts, dfeat, gtab, resolutions, compact_records=ctx.compact)
         if gtab is not None and table.dtype != _f32:
             gtab = gtab.to(table.dtype)
         return (g_o if ctx.needs_input_grad[0] else None, g_d if ctx.needs_input_grad[1] else None, None, None, gtab,

@@ -163,7 +163,6 @@ class TileModel(nn.Module):
         self._center_dev = self.bbox_center.to(device).contiguous()
         self._half_dev = (self.bbox_size / 2.0).to(device).contiguous()
         self.packed = render.PackedDecoder(device)
-        self._side_stream = torch.cuda.Stream(device=device) if str(device).startswith("cuda") else None
         # fused sparse Adam state for the table (cuda/adam_kernel.cu semantics)
         self.exp_avg = torch.zeros_like(self.features, dtype=torch.float16 if self.fp16_moments else torch.float32)
         self.exp_avg_sq = torch.zeros_like(self.exp_avg)
@@ -403,14 +402,176 @@ FORWARD_PLAN = True         # the forward launch counts the backward's record ra
 LEVEL_SKIP = True           # levels whose coarse-to-fine weight is exactly zero are left out of gathers and records (same results)
 JSTASH = True               # pose gradients: the forward stashes the encoder's position Jacobians for the backward
 
+# Table-gradient routes (table_grad_route):
+RECORDS_ADAM = "records_adam"    # the backward kernel emits the records; accumulate + sparse Adam (adam2 for two branches)
+RECORDS_TABLE = "records_table"  # the backward kernel emits the records; accumulate into a gradient table
+RAYS_ADAM = "rays_adam"          # dfeat -> scatter_table_grad_adam_rays (places the samples itself; large tables)
+POINTS_ADAM = "points_adam"      # dfeat at contracted points built in torch -> scatter_table_grad_adam
+POINTS_TABLE = "points_table"    # dfeat at contracted points -> scatter_table_grad into a gradient table (then table_adam)
+_TABLE_ROUTES = (RECORDS_TABLE, POINTS_TABLE)
+# ... and the entry points asking for one
+SINGLE, FGBG_STEP, FGBG_GRADIENTS, AUTOGRAD = "single", "fgbg_step", "fgbg_gradients", "autograd"
+
+
+def table_grad_route(entry, T, B, S, arith, half_table=False, fused_adam=True, fused_scatter=None):
+    """How a training step's feature gradients reach the table -> (routes: one per branch sample count in S, the
+    `compact_records` of a contracted-points scatter).  Pure: no allocation, no launch.  arith: the backward's arithmetic;
+    half_table: a half-precision gather copy is resident.  Each entry point keeps the choice it made before this was one place
+    (tests/test_table_grad_route_cpu.py gives each row's reason):
+      SINGLE: records where fused_scatter (default: T <= 2^21 or LARGE_T_ROUTE "fused") and the workspace allow, f32 included;
+        else rays / points ending in the Adam, or with fused_adam=False points into a gradient table (compact above 2^21 only);
+      FGBG_STEP: records + adam2 as SINGLE but never under f32; above 2^21 (not f32, no half table) ONE rays / points scatter
+        over both branches; else FGBG_GRADIENTS' gradient table;
+      FGBG_GRADIENTS: per branch, records into the table at T <= 2^21 (LARGE_T_ROUTE ignored), else points with -1;
+      AUTOGRAD (only asked when the table needs a gradient): records at T <= 2^21, else points with -1."""
+    # records emitted by the backward kernel need the level's cursors in ITS LDS (256 buckets per level): above 2^21 entries
+    # they outgrow the accumulate's LDS image.  The split pass in front of the accumulate (csrc/scatter.hip k_bin_split) serves
+    # larger tables, but the stand-alone scatter from dfeat (2^13-entry buckets) is still ahead there (T = 2^24, 16 384 rays:
+    # 5.6 against 6.1 ms per step): LARGE_T_ROUTE = "fused" selects the split pass
+    small = T <= (1 << 21)
+    records = all(render.scatter_supported(B, s, T) for s in S)
+    compact = render.compact_record_format(arith)
+    if entry == SINGLE:
+        if fused_scatter is None:
+            fused_scatter = small or LARGE_T_ROUTE == "fused"
+        if fused_scatter and records:
+            route = RECORDS_ADAM if fused_adam else RECORDS_TABLE
+        elif not fused_adam:
+            route, compact = POINTS_TABLE, (-1 if small else compact)
+        else:
+            route = RAYS_ADAM if render.scatter_rays_supported(T, arith) and not half_table else POINTS_ADAM
+        return (route,), compact
+    if entry == FGBG_STEP:
+        if (small or LARGE_T_ROUTE == "fused") and records and arith != render._capi.ARITH_F32:
+            return (RECORDS_ADAM,) * len(S), compact
+        if not small and arith != render._capi.ARITH_F32 and not half_table:
+            return (RAYS_ADAM if render.scatter_rays_supported(T, arith) else POINTS_ADAM,) * len(S), compact
+        entry = FGBG_GRADIENTS
+    if entry == FGBG_GRADIENTS:
+        return tuple(RECORDS_TABLE if small and render.scatter_supported(B, s, T) else POINTS_TABLE for s in S), -1
+    if entry == AUTOGRAD:
+        return (RECORDS_TABLE if small and records else POINTS_TABLE,), -1
+    raise ValueError(f"table_grad_route: unknown entry point {entry!r}")
+
+
+def _forward_plans(B, S, T):
+    """The forward launch can reserve the t16 backward's record ranges itself (its hash indices are the plan's): no separate
+    plan launch (0.25 ms at configs[1])."""
+    return (render.backward_arith(True, False) in render._capi.T16_FAMILY and render.forward_plan_supported(B, S, T)
+            and FORWARD_PLAN)
+
+
+class _Branch:
+    """One render branch of a training step on the fused kernels: the forward with its stashes, the record plan of the
+    table-gradient route, the backward and the ray gradients.  sized=False (fgbg_gradients): only the backward is a timer
+    section, without byte and FLOP counts; workspace: the branch's own record workspace (default: the per-stream one)."""
+
+    def __init__(self, model, rays_o, rays_d, z, dist, valid, mode, infinity, route, compact, timer=None, sized=True,
+                 workspace=None):
+        self.model, self.rays_o, self.rays_d, self.z, self.dist, self.valid = model, rays_o, rays_d, z, dist, valid
+        self.box = (model.min_bbox.tolist(), model.bbox_size.tolist(), mode, infinity)
+        self.route, self.compact, self.timer, self.sized, self.workspace = route, compact, timer, sized, workspace
+        self.records = route in (RECORDS_ADAM, RECORDS_TABLE)
+        self.B, self.S = z.shape
+        self.ws = self.jstash = self.dfeat = None
+
+    def _sec(self, name, *counts):
+        return _sec(self.timer if self.sized else None, name, *counts)
+
+    def forward(self, table, plan=False, jstash=False):
+        """plan: the launch also reserves the backward's record ranges (_forward_plans); jstash: it stashes the encoder's
+        position Jacobians, so that the backward chains the feature gradients to the rays without a second pass over the table."""
+        m, B, S = self.model, self.B, self.S
+        self.table = table
+        self.tile_T = torch.empty((B, render.tile_T_columns(S)), device=m.device)
+        self.xstash = torch.empty((B * S, 32), device=m.device)  # encoder outputs: 1 GB at 65 536 x 128, saves the re-gather
+        if jstash:
+            self.jstash = torch.empty(render.jstash_shape(B, S), dtype=render.JSTASH_DTYPE, device=m.device)
+        with self._sec("render_forward", B * (24 + 20 + S * 16 * 8 * 2 * table.element_size()), B * S * MLP_FLOPS_PER_SAMPLE):
+            r = render.render_forward(self.rays_o, self.rays_d, self.z, self.dist, table, m.resolution, m.packed, *self.box,
+                                      ray_valid=self.valid, want_weights=False, tile_T=self.tile_T, xstash=self.xstash,
+                                      plan=plan, plan_workspace=self.workspace, jstash=self.jstash)
+        if plan:
+            self.ws = r[2]
+        self.out = r[0]
+        return self.out
+
+    def points(self):
+        return render.contracted_points(self.rays_o, self.rays_d, self.z, self.model._min_dev, self.model._size_dev, self.box[2])
+
+    def backward(self, grad_out, weight_feature, grad_blob, grad_table, pose_grads):
+        """The backward of dL/d(out_ray) = grad_out; the record routes emit into grad_table (the gradient table, or the
+        overflow table of a route ending in the sparse Adam), the *_TABLE routes finish into it.  -> (g_o, g_d) with pose_grads."""
+        m, B, S = self.model, self.B, self.S
+        bufs = (torch.zeros(B, (S + 31) // 32, device=m.device), torch.zeros(B, 2, 64, device=m.device)) if pose_grads else None
+        ray_pos = torch.zeros(B, 6, device=m.device) if self.jstash is not None else None
+        if self.records and self.ws is None:   # count + scan of the scatter records (depends on the sample positions only)
+            with self._sec("scatter_plan", B * S * 4):
+                self.ws = render.scatter_plan(self.rays_o, self.rays_d, self.z, m.resolution, m.features.shape[1], *self.box,
+                                              ray_valid=self.valid, arith=render.backward_arith(True, pose_grads),
+                                              workspace=self.workspace, skip_levels=m.packed.skip_levels)
+        # forward recompute + activation gradients + weight gradients = 3x the forward MLP FLOPs (SURVEY.md 8d)
+        counts = (B * (24 + 20 + S * 16 * 8 * 2 * 4 + S * 16 * 8), 3 * B * S * MLP_FLOPS_PER_SAMPLE) if self.sized else ()
+        with _sec(self.timer, "render_backward", *counts):
+            self.dfeat, _ = render.render_backward(
+                self.rays_o, self.rays_d, self.z, self.dist, self.table, m.resolution, m.packed, weight_feature,
+                *self.box, self.out, self.tile_T, grad_out, ray_valid=self.valid, grad_blob=grad_blob, xstash=self.xstash,
+                ray_grad_buffers=bufs, scatter=(self.ws, grad_table) if self.records else None,
+                want_dfeat=not self.records or (pose_grads and self.jstash is None),
+                arith=render.backward_arith(True, pose_grads), jstash=self.jstash, ray_pos_grad=ray_pos)
+        g = None
+        if pose_grads and self.jstash is not None:
+            g = render.ray_gradients_fused(self.rays_o, self.rays_d, m.decoder.blob(), ray_pos, *bufs, ray_valid=self.valid)
+        elif pose_grads:
+            g = render.ray_gradients(self.rays_o, self.rays_d, self.z, m.features, m.resolution, m.decoder.blob(), *self.box[:3],
+                                     self.dfeat, *bufs, ray_valid=self.valid)
+        if self.route == RECORDS_TABLE:
+            with self._sec("table_grad_accumulate", B * S * 16 * 64):
+                render.scatter_accumulate(self.ws, grad_table, B, S)
+        elif self.route == POINTS_TABLE:
+            pts = self.points()
+            with self._sec("table_grad_scatter", B * S * 16 * (8 + 16 * 8)):
+                render.scatter_table_grad(pts, self.dfeat, grad_table, m.resolution, compact_records=self.compact)
+        return g
+
+
+def _table_grad_adam(model, route, compact, rays_o, rays_d, branches, lr, timer):
+    """The routes that end in the fused sparse Adam (no gradient table, no zero-fill, no dense optimiser scan): ONE step over
+    the feature gradients of every branch."""
+    B, S = rays_o.shape[0], sum(b.S for b in branches)
+    over = model.overflow_grad()   # (the workspace-overflow path's zero table, never filled per step)
+    adam = (model.features.data, model.exp_avg, model.exp_avg_sq, lr, 0.9, 0.99, 1e-15, model.adam_step)
+    if route == RECORDS_ADAM:
+        with _sec(timer, "table_grad_accumulate_adam", B * S * 16 * 64 + model.features.numel() * 28):
+            if len(branches) == 1:
+                render.scatter_accumulate_adam(branches[0].ws, *adam, B, S, half_table=model._half_table, overflow_grad=over)
+            else:
+                fg, bg = branches
+                render.scatter_accumulate_adam2(fg.ws, fg.S, bg.ws, bg.S, *adam, B, half_table=model._half_table,
+                                                overflow_grad=over)
+    elif route == RAYS_ADAM:   # (the stand-alone scatter places the samples itself: rays + depths)
+        with _sec(timer, "table_grad_scatter_adam", B * S * 16 * (8 + 16 * 8)):
+            render.scatter_table_grad_adam_rays(rays_o, rays_d, [(b.z, b.dfeat, b.valid, b.box[2]) for b in branches],
+                                                *branches[0].box[:2], model.resolution, *adam, overflow_grad=over,
+                                                fp16_moments=model.fp16_moments)
+    else:
+        if len(branches) == 1:
+            pts, dfeat = branches[0].points(), branches[0].dfeat
+        else:
+            pts, dfeat = torch.cat([b.points() for b in branches], 0), torch.cat([b.dfeat for b in branches], 1).contiguous()
+        with _sec(timer, "table_grad_scatter_adam", B * S * 16 * (8 + 16 * 8)):
+            render.scatter_table_grad_adam(pts, dfeat, model.resolution, *adam, half_table=model._half_table, overflow_grad=over,
+                                           compact_records=compact)
+    model.adam_step += 1
+
 
 def train_step_fused(model, dec_opt, rays_o, rays_d, target, S, global_step, table_lr=1e-2, timer=None,
-                     pose_grads=False, fused_scatter=None, compact_rays=None, overlap_plan=False, dec_step=True,
-                     fused_adam=True, warp=None):
+                     pose_grads=False, fused_scatter=None, compact_rays=None, dec_step=True, fused_adam=True, warp=None):
     """The same iteration as train_step_ops on the fused kernels: one launch for the render forward,
     one for its adjoint, the atomic-free binned scatter for the table gradient, fused sparse Adam.
     fused_adam (default): the sparse Adam on the table runs in the accumulate's epilogue (no gradient table, model.features.grad
     is NOT set); False keeps accumulate -> model.features.grad -> adam_step_cuda (the binding-surface op).
+    fused_scatter: True / False forces the backward's own records on / off (default: table_grad_route).
     pose_grads=True also returns dL/d(rays_o), dL/d(rays_d) (feed them to the pose graph:
     torch.autograd.backward([rays_o, rays_d], [g_o, g_d]) -- camera_utils.py:65-84 in the reference).
     warp (warp.WarpLoss, default None): the multi-view warp term joins the loss; its gradient is added to grad_out before the
@@ -435,53 +596,15 @@ def train_step_fused(model, dec_opt, rays_o, rays_d, target, S, global_step, tab
                 valid = None
             if B == 0:
                 return torch.zeros((), device=dev)
-        wf = model.weight_feature(global_step)
-        blob = model.decoder.blob()
-        model.packed.pack(blob, wf, (network.skip_levels(global_step) if LEVEL_SKIP else 0))
-        ntile = (S + 31) // 32
-        tile_T = torch.empty((B, render.tile_T_columns(S)), device=dev)
-        bwd_arith = render.backward_arith(True, pose_grads)
-        xstash = torch.empty((B * S, 32), device=dev)  # encoder outputs: 1 GB at 65 536 x 128, saves the re-gather
-        box = (model.min_bbox.tolist(), model.bbox_size.tolist(), render.FORE, False)
-        T = model.features.shape[1]
-        if fused_scatter is None:
-            # records emitted by the backward kernel need the level's cursors in ITS LDS (256 buckets per level): above 2^21
-            # entries its buckets (T / 256) outgrow the accumulate's LDS image.  Round 4 put a split pass in front of the
-            # accumulate (csrc/scatter.hip k_bin_split: T = 2^24, 16 384 rays: 9.6 -> 6.1 ms per step on the fused route), but
-            # the stand-alone scatter from dfeat, which emits straight into 2^13-entry buckets, is still ahead there (5.6 ms):
-            # it stays the default above 2^21; LARGE_T_ROUTE = "fused" selects the fused route
-            fused_scatter = T <= (1 << 21) or LARGE_T_ROUTE == "fused"
-        fused = fused_scatter and render.scatter_supported(B, S, T)
-        ws = plan_done = None
-        side = model._side_stream if overlap_plan else None  # (the plan then has no timer section of its own)
-        if fused and side is not None:
-            # the record plan depends on the sample positions only: count + scan on a side stream, under the forward.
-            # Measured: no gain (the forward slows from 3.14 to 3.6 ms, exactly the 0.25 ms of the plan plus contention),
-            # so it is off by default
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                ws = render.scatter_plan(rays_o, rays_d, z, model.resolution, T, *box, ray_valid=valid, arith=bwd_arith, skip_levels=model.packed.skip_levels)
-                plan_done = torch.cuda.Event()
-                plan_done.record(side)
+        model.packed.pack(model.decoder.blob(), model.weight_feature(global_step), (network.skip_levels(global_step) if LEVEL_SKIP else 0))
         # gather table: the fp32 master itself, or its resident bf16/f16 copy (configs[2]: half the gather bytes, fp32 accumulate)
         table = model.gather_table()
-        with _sec(timer, "render_forward", B * (24 + 20 + S * 16 * 8 * 2 * table.element_size()),
-                  B * S * MLP_FLOPS_PER_SAMPLE):
-            # t16 backward on the same grid as the forward: the forward kernel counts the scatter records itself (its hash
-            # indices are the plan's) -- no separate plan launch (0.25 ms at configs[1])
-            jstash = None
-            if (fused and ws is None and bwd_arith in render._capi.T16_FAMILY and render.forward_plan_supported(B, S, T)
-                    and FORWARD_PLAN):
-                # pose refinement: the forward also stashes the encoder's position Jacobians (it has the corner values in
-                # registers), so that the backward can chain the feature gradients to the rays without a second pass over the table
-                if pose_grads and table.dtype == torch.float32 and JSTASH:
-                    jstash = torch.empty(render.jstash_shape(B, S), dtype=render.JSTASH_DTYPE, device=dev)
-                out, _, ws = render.render_forward(rays_o, rays_d, z, dist, table, model.resolution, model.packed, *box,
-                                                   ray_valid=valid, want_weights=False, tile_T=tile_T, xstash=xstash, plan=True,
-                                                   jstash=jstash)
-            else:
-                out, _ = render.render_forward(rays_o, rays_d, z, dist, table, model.resolution, model.packed, *box,
-                                               ray_valid=valid, want_weights=False, tile_T=tile_T, xstash=xstash)
+        T = model.features.shape[1]
+        (route,), compact = table_grad_route(SINGLE, T, B, [S], render.backward_arith(True, pose_grads),
+                                             model._half_table is not None, fused_adam, fused_scatter)
+        br = _Branch(model, rays_o, rays_d, z, dist, valid, render.FORE, False, route, compact, timer)
+        plan = br.records and _forward_plans(B, S, T)
+        out = br.forward(table, plan, jstash=plan and pose_grads and table.dtype == torch.float32 and JSTASH)
     # loss and dL/d(out_ray) in two launches (the torch graph for it was ~60 tiny kernels with host-bound gaps)
     loss, grad_out = render.photometric_loss_grad(out, target, valid, 0.01)
     wterm = None
@@ -490,64 +613,14 @@ def train_step_fused(model, dec_opt, rays_o, rays_d, target, S, global_step, tab
             wterm = warp.fused_term(global_step, rays_o, rays_d, out, valid, grad_out,
                                     lambda o, d: _visibility_render_fore(model, o, d, S, global_step))
     with torch.no_grad():
-        # the scatter ends in the Adam epilogue: no gradient table (only the overflow table, never filled per step)
-        adam_epilogue = fused_adam
-        gtab = model.overflow_grad() if adam_epilogue else torch.zeros_like(model.features)
+        gtab = model.overflow_grad() if fused_adam else torch.zeros_like(model.features)
         gblob = torch.zeros(network.PARAMSIZE, device=dev)
-        ray_bufs = (torch.zeros(B, ntile, device=dev), torch.zeros(B, 2, 64, device=dev)) if pose_grads else None
-        g_o = g_d = None
-        if fused and ws is None:
-            # count + scan of the scatter records (depends on the sample positions only)
-            with _sec(timer, "scatter_plan", B * S * 4):
-                ws = render.scatter_plan(rays_o, rays_d, z, model.resolution, T, *box, ray_valid=valid, arith=bwd_arith, skip_levels=model.packed.skip_levels)
-        elif plan_done is not None:
-            torch.cuda.current_stream().wait_event(plan_done)
-        # forward recompute + activation gradients + weight gradients = 3x the forward MLP FLOPs
-        with _sec(timer, "render_backward", B * (24 + 20 + S * 16 * 8 * 2 * 4 + S * 16 * 8), 3 * B * S * MLP_FLOPS_PER_SAMPLE):
-            ray_pos = torch.zeros(B, 6, device=dev) if jstash is not None else None
-            dfeat, _ = render.render_backward(rays_o, rays_d, z, dist, table, model.resolution, model.packed, wf,
-                                              *box, out, tile_T, grad_out, ray_valid=valid, grad_blob=gblob, xstash=xstash,
-                                              ray_grad_buffers=ray_bufs, scatter=(ws, gtab) if fused else None,
-                                              want_dfeat=(pose_grads and jstash is None) or not fused, arith=bwd_arith,
-                                              jstash=jstash, ray_pos_grad=ray_pos)
-        if pose_grads and jstash is not None:
-            g_o, g_d = render.ray_gradients_fused(rays_o, rays_d, blob, ray_pos, ray_bufs[0], ray_bufs[1], ray_valid=valid)
-        elif pose_grads:
-            g_o, g_d = render.ray_gradients(rays_o, rays_d, z, model.features, model.resolution, blob, box[0], box[1],
-                                            box[2], dfeat, ray_bufs[0], ray_bufs[1], ray_valid=valid)
-        if pose_grads and wterm is not None:
-            g_o, g_d = g_o + wterm[1], g_d + wterm[2]
-        if adam_epilogue and fused:
-            with _sec(timer, "table_grad_accumulate_adam", B * S * 16 * 64 + model.features.numel() * 28):
-                render.scatter_accumulate_adam(ws, model.features.data, model.exp_avg, model.exp_avg_sq, table_lr, 0.9, 0.99, 1e-15,
-                                               model.adam_step, B, S, half_table=model._half_table, overflow_grad=gtab)
-            model.adam_step += 1
-        elif adam_epilogue and render.scatter_rays_supported(T, bwd_arith) and model._half_table is None:
-            # large tables: the stand-alone scatter places the samples itself (rays + depths), same epilogue
-            with _sec(timer, "table_grad_scatter_adam", B * S * 16 * (8 + 16 * 8)):
-                render.scatter_table_grad_adam_rays(rays_o, rays_d, [(z, dfeat, valid, render.FORE)], box[0], box[1], model.resolution,
-                                                    model.features.data, model.exp_avg, model.exp_avg_sq, table_lr, 0.9, 0.99, 1e-15,
-                                                    model.adam_step, overflow_grad=gtab, fp16_moments=model.fp16_moments)
-            model.adam_step += 1
-        elif adam_epilogue:   # (the other record formats: contracted points from torch, stand-alone binned scatter from dfeat)
-            pts = ((rays_o[:, None, :] + z[:, :, None] * rays_d[:, None, :]).reshape(-1, 3) - model._min_dev) \
-                / model._size_dev * 4.0 - 2.0
-            with _sec(timer, "table_grad_scatter_adam", B * S * 16 * (8 + 16 * 8)):
-                render.scatter_table_grad_adam(pts.contiguous(), dfeat, model.resolution, model.features.data, model.exp_avg,
-                                               model.exp_avg_sq, table_lr, 0.9, 0.99, 1e-15, model.adam_step,
-                                               half_table=model._half_table, overflow_grad=gtab,
-                                               compact_records=render.compact_record_format(bwd_arith))
-            model.adam_step += 1
-        elif fused:
-            with _sec(timer, "table_grad_accumulate", B * S * 16 * 64):
-                render.scatter_accumulate(ws, gtab, B, S)
+        g = br.backward(grad_out, model.weight_feature(global_step), gblob, gtab, pose_grads)
+        if g is not None and wterm is not None:
+            g = (g[0] + wterm[1], g[1] + wterm[2])
+        if fused_adam:
+            _table_grad_adam(model, route, compact, rays_o, rays_d, [br], table_lr, timer)
         else:
-            pts = ((rays_o[:, None, :] + z[:, :, None] * rays_d[:, None, :]).reshape(-1, 3) - model._min_dev) \
-                / model._size_dev * 4.0 - 2.0
-            with _sec(timer, "table_grad_scatter", B * S * 16 * (8 + 16 * 8)):
-                render.scatter_table_grad(pts.contiguous(), dfeat, gtab, model.resolution,
-                                          compact_records=render.compact_record_format(bwd_arith) if T > (1 << 21) else -1)
-        if not adam_epilogue:
             model.features.grad = gtab
             with _sec(timer, "sparse_adam", model.features.numel() * 28):
                 model.table_adam(table_lr)
@@ -556,7 +629,7 @@ def train_step_fused(model, dec_opt, rays_o, rays_d, target, S, global_step, tab
             dec_opt.step()
     if wterm is not None:
         loss = loss + wterm[0]
-    return (loss[0], g_o, g_d) if pose_grads else loss[0]
+    return (loss[0], *g) if pose_grads else loss[0]
 
 
 # ---- the warp term's visibility render (warp_loss.py:355-378: the tile's renderer on the neighbour rays, no grad) ---------------
@@ -574,90 +647,72 @@ def _visibility_render_fgbg(model, rays_o, rays_d, S_fg, S_bg, global_step, inva
     return r["pred_depth"][:, 0], r["pred_specular"]
 
 
-def fgbg_gradients(model, rays_o, rays_d, target, S_fg, S_bg, global_step, invalid_underground=False, timer=None,
-                   pose_grads=False, collect=None, collect_rays=False, warp=None):
-    """Loss and parameter gradients of the complete per-tile render of tile.py:639-692 / :880-1015: foreground
-    (occupancy-sampled, contract_fore) + T_left * background (inverse-z, contract_bg, infinity), MSE on the merged colour
-    over all rays + 0.01 * (l2_reg_specular of both branches) -- two fused forward/backward pairs over the same table and
-    decoder.  Returns (loss, grad_table [16,T,2], grad_blob [13994]) (+ dL/d(rays_o), dL/d(rays_d) with pose_grads: t16
-    backward on the fp32 table, any table size).  collect: a list that receives (contracted points [N,3], dfeat [16,N,2]) of
-    each branch INSTEAD of their scatter into the gradient table (the caller scatters them together: large tables); with
-    collect_rays it receives (z [B,S], dfeat, ray_valid, contract mode) -- the input of render.scatter_table_grad_adam_rays.
-    warp: as in train_step_fused, on the merged prediction (warp.WarpLoss.fgbg_term)."""
+def _fgbg_pass(model, rays_o, rays_d, target, S_fg, S_bg, global_step, invalid_underground, timer, pose_grads, warp, routes,
+               compact):
+    """Both branches of a tile's render on `routes` (table_grad_route): forward, the merged loss (+ the warp term), backward
+    -> (loss [1], (fg, bg) _Branch, grad_blob, gradient table or None, (g_o, g_d) or None).  On the records + adam2 route the
+    steps' timer sections, gather_table(), the forward's record plans and the background's own record workspace; elsewhere
+    fgbg_gradients' reference: the fp32 master, only the backward timed."""
     B = rays_o.shape[0]
     dev = model.device
     T = model.features.shape[1]
-    if pose_grads and render.backward_arith(True, True) not in render._capi.T16_FAMILY:
+    fused = routes[0] == RECORDS_ADAM
+    if pose_grads and not fused and render.backward_arith(True, True) not in render._capi.T16_FAMILY:
         raise RuntimeError("scanerf: fgbg pose gradients need the t16 backward (render.set_arith)")
-    g_o = g_d = None
     with torch.no_grad():
-        wf = model.weight_feature(global_step)
-        model.packed.pack(model.decoder.blob(), wf, (network.skip_levels(global_step) if LEVEL_SKIP else 0))
-        box = (model.min_bbox.tolist(), model.bbox_size.tolist())
-        branches = []
-        z, dist = model.sample(rays_o, rays_d, S_fg)
-        branches.append((z, dist, torch.all(z != -1, dim=-1), render.FORE, False))
+        model.packed.pack(model.decoder.blob(), model.weight_feature(global_step), (network.skip_levels(global_step) if LEVEL_SKIP else 0))
+        table = model.gather_table() if fused else model.features
+        with _sec(timer if fused else None, "sample_points_grid", B * (24 + 2 * 4 * S_fg)):
+            z, dist = model.sample(rays_o, rays_d, S_fg)
+        vf = render.ray_valid(z) if fused else torch.all(z != -1, dim=-1)
         zb, db, vb = model.inverse_z_sampling(rays_o, rays_d, S_bg, invalid_underground)
-        branches.append((zb, db, vb, render.BG, True))
-        outs, state = [], []
-        for z_, d_, v_, mode, inf in branches:
-            S = z_.shape[1]
-            tile_T = torch.empty((B, render.tile_T_columns(S)), device=dev)
-            xs = torch.empty((B * S, 32), device=dev)
-            js = torch.empty(render.jstash_shape(B, S), dtype=render.JSTASH_DTYPE, device=dev) if pose_grads else None
-            out, _ = render.render_forward(rays_o, rays_d, z_, d_, model.features, model.resolution, model.packed, *box, mode, inf,
-                                           ray_valid=v_, want_weights=False, tile_T=tile_T, xstash=xs, jstash=js)
-            outs.append(out)
-            state.append((tile_T, xs, js))
+        ws_bg = None
+        if fused:   # the background branch's own record workspace (both plans live until the one accumulate)
+            need_bg = render.lib().scanerf_render_scatter_workspace_bytes(B, S_bg, T)
+            if getattr(model, "_ws_bg", None) is None or model._ws_bg.numel() < need_bg:
+                model._ws_bg = torch.empty(need_bg, dtype=torch.uint8, device=dev)
+            ws_bg = model._ws_bg
+        branches = (_Branch(model, rays_o, rays_d, z, dist, vf, render.FORE, False, routes[0], compact, timer, fused),
+                    _Branch(model, rays_o, rays_d, zb, db, vb, render.BG, True, routes[1], compact, timer, fused, ws_bg))
+        for b in branches:
+            b.forward(table, plan=fused and _forward_plans(B, b.S, T), jstash=pose_grads)
     # merge and loss on the per-ray outputs (tile.py:666-690; criterions.py:142-144; tile.py:999), two HIP launches
-    vf, vbg = branches[0][2], branches[1][2]
-    loss, gfg, gbg = render.photometric_loss_grad_fgbg(outs[0], outs[1], target, vf, vbg, 0.01)
+    loss, gfg, gbg = render.photometric_loss_grad_fgbg(branches[0].out, branches[1].out, target, vf, vb, 0.01)
     wterm = None
     if warp is not None:
         with _sec(timer, "warp_loss"):
-            wterm = warp.fgbg_term(global_step, rays_o, rays_d, outs[0], outs[1], vf, vbg, gfg, gbg,
+            wterm = warp.fgbg_term(global_step, rays_o, rays_d, branches[0].out, branches[1].out, vf, vb, gfg, gbg,
                                    lambda o, d: _visibility_render_fgbg(model, o, d, S_fg, S_bg, global_step, invalid_underground))
-        if wterm is not None:
-            loss = loss + wterm[0]
-
-    class _Leaf:  # (what the loop below reads from the former autograd leaves)
-        def __init__(self, g):
-            self.grad = g
-    fg, bg = _Leaf(gfg), _Leaf(gbg)
     with torch.no_grad():
-        gtab = torch.zeros_like(model.features) if collect is None else None
+        gtab = torch.zeros_like(model.features) if routes[0] in _TABLE_ROUTES else None
         gblob = torch.zeros(network.PARAMSIZE, device=dev)
-        for (z_, d_, v_, mode, inf), out, leaf, (tile_T, xs, js) in zip(branches, outs, (fg, bg), state):
-            S = z_.shape[1]
-            fused = T <= (1 << 21) and render.scatter_supported(B, S, T) and collect is None  # (see train_step_fused)
-            ws = render.scatter_plan(rays_o, rays_d, z_, model.resolution, T, *box, mode, inf, ray_valid=v_, skip_levels=model.packed.skip_levels) if fused else None
-            bufs = (torch.zeros(B, (S + 31) // 32, device=dev), torch.zeros(B, 2, 64, device=dev)) if pose_grads else None
-            rp = torch.zeros(B, 6, device=dev) if pose_grads else None
-            with _sec(timer, "render_backward"):
-                dfeat, _ = render.render_backward(rays_o, rays_d, z_, d_, model.features, model.resolution, model.packed, wf, *box,
-                                                  mode, inf, out, tile_T, leaf.grad.contiguous(), ray_valid=v_, grad_blob=gblob,
-                                                  xstash=xs, scatter=(ws, gtab) if fused else None, want_dfeat=not fused,
-                                                  ray_grad_buffers=bufs, jstash=js, ray_pos_grad=rp)
-            if pose_grads:
-                go_b, gd_b = render.ray_gradients_fused(rays_o, rays_d, model.decoder.blob().detach(), rp, bufs[0], bufs[1], ray_valid=v_)
-                g_o, g_d = (go_b, gd_b) if g_o is None else (g_o + go_b, g_d + gd_b)
-            if fused:
-                render.scatter_accumulate(ws, gtab, B, S)
-            elif collect is not None and collect_rays:
-                collect.append((z_, dfeat, v_, mode))   # (scatter_table_grad_adam_rays places the samples itself)
-            else:
-                pts = (rays_o[:, None, :] + z_[:, :, None] * rays_d[:, None, :]).reshape(-1, 3)
-                pts = (pts - model._min_dev) / model._size_dev * 4.0 - 2.0
-                if mode == render.BG:
-                    linf = pts.abs().amax(-1, keepdim=True)
-                    pts = pts * ((2.0 - 1.0 / linf) / linf)
-                if collect is not None:
-                    collect.append((pts.contiguous(), dfeat))
-                else:
-                    render.scatter_table_grad(pts.contiguous(), dfeat, gtab, model.resolution)
-        if pose_grads and wterm is not None:
-            g_o, g_d = g_o + wterm[1], g_d + wterm[2]
-    return (loss[0].detach(), gtab, gblob, g_o, g_d) if pose_grads else (loss[0].detach(), gtab, gblob)
+        if fused:
+            gtab = model.overflow_grad()
+        g = None
+        for b, grad_out in zip(branches, (gfg, gbg)):
+            gb = b.backward(grad_out, model.weight_feature(global_step), gblob, gtab, pose_grads)
+            if gb is not None:
+                g = gb if g is None else (g[0] + gb[0], g[1] + gb[1])
+        if g is not None and wterm is not None:
+            g = (g[0] + wterm[1], g[1] + wterm[2])
+    if wterm is not None:
+        loss = loss + wterm[0]
+    return loss, branches, gblob, gtab, g
+
+
+def fgbg_gradients(model, rays_o, rays_d, target, S_fg, S_bg, global_step, invalid_underground=False, timer=None,
+                   pose_grads=False, warp=None):
+    """Loss and parameter gradients of the complete per-tile render of tile.py:639-692 / :880-1015: foreground
+    (occupancy-sampled, contract_fore) + T_left * background (inverse-z, contract_bg, infinity), MSE on the merged colour
+    over all rays + 0.01 * (l2_reg_specular of both branches) -- two fused forward/backward pairs over the same table and
+    decoder, each branch's table gradient into ONE gradient table.  Returns (loss, grad_table [16,T,2], grad_blob [13994])
+    (+ dL/d(rays_o), dL/d(rays_d) with pose_grads: t16 backward on the fp32 table, any table size).
+    warp: as in train_step_fused, on the merged prediction (warp.WarpLoss.fgbg_term)."""
+    routes, compact = table_grad_route(FGBG_GRADIENTS, model.features.shape[1], rays_o.shape[0], [S_fg, S_bg],
+                                       render.backward_arith())
+    loss, _, gblob, gtab, g = _fgbg_pass(model, rays_o, rays_d, target, S_fg, S_bg, global_step, invalid_underground, timer,
+                                         pose_grads, warp, routes, compact)
+    return (loss[0].detach(), gtab, gblob, *g) if pose_grads else (loss[0].detach(), gtab, gblob)
 
 
 def train_step_fgbg(model, dec_opt, rays_o, rays_d, target, S_fg, S_bg, global_step, table_lr=1e-2,
@@ -665,112 +720,26 @@ def train_step_fgbg(model, dec_opt, rays_o, rays_d, target, S_fg, S_bg, global_s
     """One complete training iteration of a tile (tile.py:880-1015: foreground + T_left * background, tile.py:639-692) on the
     fused kernels: both branches' forward, ONE loss launch pair for the merged prediction, both branches' backward emitting
     their scatter records, and ONE accumulate + sparse Adam over both record sets (the two gradients meet in one Adam step).
-    Falls back to gradient tables + adam_step_cuda where the fused scatter does not apply (tables above 2^21 entries).
+    Above 2^21 entries the two branches' dfeat go through ONE stand-alone scatter ending in the sparse Adam instead, and where
+    neither applies through gradient tables + adam_step_cuda (table_grad_route).
     pose_grads=True (fp32 tables, t16 backward): also returns dL/d(rays_o), dL/d(rays_d) of the merged prediction -- the sum of
     the two branches' ray gradients, each formed inside its backward launch from the forward's position Jacobians
     (-> (loss, g_o, g_d)); dec_step=False: the caller steps the decoder's optimiser (it holds the camera parameters too).
     warp (warp.WarpLoss, default None): the multi-view warp term on the merged prediction, chained to both branches before their
     backward (see train_step_fused)."""
-    B = rays_o.shape[0]
-    dev = model.device
-    T = model.features.shape[1]
-    fused = (T <= (1 << 21) or LARGE_T_ROUTE == "fused") and render.scatter_supported(B, S_fg, T) \
-        and render.scatter_supported(B, S_bg, T) and render.backward_arith() != render._capi.ARITH_F32
+    routes, compact = table_grad_route(FGBG_STEP, model.features.shape[1], rays_o.shape[0], [S_fg, S_bg],
+                                       render.backward_arith(), model._half_table is not None)
     if pose_grads and model.gather_table().dtype != torch.float32:
         raise RuntimeError("scanerf: train_step_fgbg(pose_grads=True) gathers from the fp32 table")
-    if not fused:
-        # tables above 2^21 entries (the reference's default is 2^24): the two branches' feature gradients go through ONE
-        # stand-alone binned scatter that ends in the sparse Adam (no gradient table, no zero-fill, no dense optimiser scan)
-        binned = T > (1 << 21) and render.backward_arith() != render._capi.ARITH_F32 and model._half_table is None
-        parts = [] if binned else None
-        by_rays = binned and render.scatter_rays_supported(T, render.backward_arith())
-        r = fgbg_gradients(model, rays_o, rays_d, target, S_fg, S_bg, global_step, invalid_underground, timer, pose_grads=pose_grads,
-                           collect=parts, collect_rays=by_rays, warp=warp)
-        loss, gtab, gblob = r[:3]
-        with torch.no_grad():
-            if by_rays:
-                with _sec(timer, "table_grad_scatter_adam", B * (S_fg + S_bg) * 16 * (8 + 16 * 8)):
-                    render.scatter_table_grad_adam_rays(rays_o, rays_d, parts, model.min_bbox.tolist(), model.bbox_size.tolist(),
-                                                        model.resolution, model.features.data, model.exp_avg, model.exp_avg_sq, table_lr,
-                                                        0.9, 0.99, 1e-15, model.adam_step, overflow_grad=model.overflow_grad(),
-                                                        fp16_moments=model.fp16_moments)
-                model.adam_step += 1
-            elif binned:
-                pts = torch.cat([p_ for p_, _ in parts], 0)
-                dfe = torch.cat([f_ for _, f_ in parts], 1).contiguous()
-                with _sec(timer, "table_grad_scatter_adam", pts.shape[0] * 16 * (8 + 16 * 8)):
-                    render.scatter_table_grad_adam(pts, dfe, model.resolution, model.features.data, model.exp_avg, model.exp_avg_sq,
-                                                   table_lr, 0.9, 0.99, 1e-15, model.adam_step, overflow_grad=model.overflow_grad(),
-                                                   compact_records=render.compact_record_format(render.backward_arith()))
-                model.adam_step += 1
-            else:
-                model.features.grad = gtab
-                model.table_adam(table_lr)
-            model.decoder.params.grad = gblob
-            if dec_step:
-                dec_opt.step()
-        return (loss, r[3], r[4]) if pose_grads else loss
+    loss, branches, gblob, gtab, g = _fgbg_pass(model, rays_o, rays_d, target, S_fg, S_bg, global_step, invalid_underground,
+                                                timer, pose_grads, warp, routes, compact)
     with torch.no_grad():
-        wf = model.weight_feature(global_step)
-        model.packed.pack(model.decoder.blob(), wf, (network.skip_levels(global_step) if LEVEL_SKIP else 0))
-        box = (model.min_bbox.tolist(), model.bbox_size.tolist())
-        table = model.gather_table()
-        with _sec(timer, "sample_points_grid", B * (24 + 2 * 4 * S_fg)):
-            z, dist = model.sample(rays_o, rays_d, S_fg)
-        vf = render.ray_valid(z)
-        zb, db, vb = model.inverse_z_sampling(rays_o, rays_d, S_bg, invalid_underground)
-        branches = ((z, dist, vf, render.FORE, False, S_fg), (zb, db, vb, render.BG, True, S_bg))
-        need_bg = render.lib().scanerf_render_scatter_workspace_bytes(B, S_bg, T)
-        if getattr(model, "_ws_bg", None) is None or model._ws_bg.numel() < need_bg:
-            model._ws_bg = torch.empty(need_bg, dtype=torch.uint8, device=dev)  # the background branch's own record workspace
-        outs, state = [], []
-        for (z_, d_, v_, mode, inf, S), wsbuf in zip(branches, (None, model._ws_bg)):
-            tile_T = torch.empty((B, render.tile_T_columns(S)), device=dev)
-            xs = torch.empty((B * S, 32), device=dev)
-            # (the forward launch reserves the backward's record ranges as well where the two kernels share a grid)
-            in_fwd = (render.backward_arith(True, False) in render._capi.T16_FAMILY and render.forward_plan_supported(B, S, T)
-                      and FORWARD_PLAN)
-            js = torch.empty(render.jstash_shape(B, S), dtype=render.JSTASH_DTYPE, device=dev) if pose_grads else None
-            with _sec(timer, "render_forward", B * (24 + 20 + S * 16 * 8 * 2 * table.element_size()), B * S * MLP_FLOPS_PER_SAMPLE):
-                r = render.render_forward(rays_o, rays_d, z_, d_, table, model.resolution, model.packed, *box, mode, inf,
-                                          ray_valid=v_, want_weights=False, tile_T=tile_T, xstash=xs, plan=in_fwd, plan_workspace=wsbuf,
-                                          jstash=js)
-            outs.append(r[0])
-            state.append((tile_T, xs, r[2] if in_fwd else None, js))
-        loss, gfg, gbg = render.photometric_loss_grad_fgbg(outs[0], outs[1], target, vf, vb, 0.01)
-        wterm = None
-        if warp is not None:
-            with _sec(timer, "warp_loss"):
-                wterm = warp.fgbg_term(global_step, rays_o, rays_d, outs[0], outs[1], vf, vb, gfg, gbg,
-                                       lambda o, d: _visibility_render_fgbg(model, o, d, S_fg, S_bg, global_step, invalid_underground))
-        gblob = torch.zeros(network.PARAMSIZE, device=dev)
-        overflow = model.overflow_grad()
-        wss = []
-        g_o = g_d = None
-        for (z_, d_, v_, mode, inf, S), out, g, (tile_T, xs, ws, js), wsbuf in zip(branches, outs, (gfg, gbg), state, (None, model._ws_bg)):
-            if ws is None:
-                with _sec(timer, "scatter_plan", B * S * 4):
-                    ws = render.scatter_plan(rays_o, rays_d, z_, model.resolution, T, *box, mode, inf, ray_valid=v_, workspace=wsbuf, skip_levels=model.packed.skip_levels)
-            bufs = (torch.zeros(B, (S + 31) // 32, device=dev), torch.zeros(B, 2, 64, device=dev)) if pose_grads else None
-            rp = torch.zeros(B, 6, device=dev) if pose_grads else None
-            with _sec(timer, "render_backward", B * (24 + 20 + S * 16 * 8 * 2 * 4 + S * 16 * 8), 3 * B * S * MLP_FLOPS_PER_SAMPLE):
-                render.render_backward(rays_o, rays_d, z_, d_, table, model.resolution, model.packed, wf, *box, mode, inf, out,
-                                       tile_T, g, ray_valid=v_, grad_blob=gblob, xstash=xs, scatter=(ws, overflow), want_dfeat=False,
-                                       ray_grad_buffers=bufs, jstash=js, ray_pos_grad=rp)
-            if pose_grads:
-                go_b, gd_b = render.ray_gradients_fused(rays_o, rays_d, model.decoder.blob().detach(), rp, bufs[0], bufs[1], ray_valid=v_)
-                g_o, g_d = (go_b, gd_b) if g_o is None else (g_o + go_b, g_d + gd_b)
-            wss.append(ws)
-        if pose_grads and wterm is not None:
-            g_o, g_d = g_o + wterm[1], g_d + wterm[2]
-        with _sec(timer, "table_grad_accumulate_adam", B * (S_fg + S_bg) * 16 * 64 + model.features.numel() * 28):
-            render.scatter_accumulate_adam2(wss[0], S_fg, wss[1], S_bg, model.features.data, model.exp_avg, model.exp_avg_sq,
-                                            table_lr, 0.9, 0.99, 1e-15, model.adam_step, B, half_table=model._half_table,
-                                            overflow_grad=overflow)
-        model.adam_step += 1
+        if routes[0] in _TABLE_ROUTES:
+            model.features.grad = gtab
+            model.table_adam(table_lr)
+        else:
+            _table_grad_adam(model, routes[0], compact, rays_o, rays_d, branches, table_lr, timer)
         model.decoder.params.grad = gblob
         if dec_step:
             dec_opt.step()
-    if wterm is not None:
-        loss = loss + wterm[0]
-    return (loss[0], g_o, g_d) if pose_grads else loss[0]
+    return (loss[0], *g) if pose_grads else loss[0]

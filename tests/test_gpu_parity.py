@@ -1194,6 +1194,55 @@ def test_train_step_large_table_adam_epilogue(S, monkeypatch):
     assert int((out[True][2] != 0).sum()) > 1000
 
 
+def test_train_step_fgbg_beyond_the_rays_scatter(S):
+    """T = 2^25 entries per level: past the rays scatter's segment producer (csrc/scatter.hip seg_route, NB <= 2048), so
+    train_step_fgbg takes the contracted points + scatter_table_grad_adam over both branches (12-byte records).  Against the
+    gradient-table route on the same model (fgbg_gradients -> adam_step_cuda, 16-byte records): the same loss and decoder, the
+    moments and the table up to the record rounding.  Device memory, about 50 GiB at the peak: the table and its two moments
+    12 GiB, the overflow and gradient tables and a snapshot 12 GiB, the two routes' results 16 GiB, the comparison 8 GiB."""
+    from scanerf_amd import render
+    from scanerf_amd.tile_model import FGBG_STEP, POINTS_ADAM, TileModel, fgbg_gradients, table_grad_route, train_step_fgbg
+    torch.manual_seed(25)
+    B, Sf, Sb = 1024, 32, 32
+    assert table_grad_route(FGBG_STEP, 1 << 25, B, [Sf, Sb], render.backward_arith()) == ((POINTS_ADAM,) * 2, 2)
+    o = torch.rand(B, 3, device=DEV) * 7.8 - 3.9
+    d = torch.nn.functional.normalize(torch.randn(B, 3, device=DEV), dim=-1)
+    tgt = torch.rand(B, 3, device=DEV)
+    m = TileModel([-4, -4, -4], [8, 8, 8], DEV, log2_T=25, seed=4)
+    with torch.no_grad():
+        m.features.mul_(1000.0)
+    f0, p0 = m.features.detach().clone(), m.decoder.params.detach().clone()
+    res = {}
+    for fused in (True, False):
+        with torch.no_grad():   # (one model, reset between the two routes: a second 2^25 table is 4 GiB of host randn)
+            m.features.copy_(f0)
+            m.decoder.params.copy_(p0)
+            m.exp_avg.zero_()
+            m.exp_avg_sq.zero_()
+            m.adam_step = 0
+        opt = torch.optim.Adam(m.decoder.parameters(), lr=1e-3, betas=(0.9, 0.99), eps=1e-15)
+        if fused:
+            loss = train_step_fgbg(m, opt, o, d, tgt, Sf, Sb, 6000, invalid_underground=True)
+        else:
+            loss, gtab, gblob = fgbg_gradients(m, o, d, tgt, Sf, Sb, 6000, invalid_underground=True)
+            with torch.no_grad():
+                m.features.grad = gtab
+                m.table_adam(1e-2)
+                m.features.grad = None
+                m.decoder.params.grad = gblob
+                opt.step()
+            del gtab
+        res[fused] = (float(loss), m.exp_avg.clone(), m.features.detach().clone(), m.decoder.params.detach().clone())
+    assert np.isfinite(res[True][0]) and res[True][0] == res[False][0]
+    assert torch.equal(res[True][3], res[False][3])
+    m1, m0 = res[True][1], res[False][1]
+    assert int((m0 != 0).sum()) > 1000
+    assert float((m1 - m0).abs().max()) <= 1e-4 * float(m0.abs().max())
+    assert int(((m1 != 0) != (m0 != 0)).sum()) <= 2e-4 * int((m0 != 0).sum())
+    dfe = (res[True][2] - res[False][2]).abs() / res[False][2].abs().max()
+    assert int((dfe > 1e-4).sum()) <= 2e-3 * int((m0 != 0).sum())
+
+
 def test_rec8_codec_against_its_restatement(S):
     """The 8-byte scatter records (csrc/scatter_common.h Rec8: the t16 backward's stream): pack on the device, unpack as the
     accumulate does, against a numpy restatement of the format -- bit-exact fields; and the decoded contributions against the
