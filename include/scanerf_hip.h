@@ -528,6 +528,24 @@ int scanerf_warp_loss_grad(const float *rays_o, const float *rays_d, const float
                            float scale, float *loss, float *grad_q, float *grad_o, float *grad_d, float *grad_rts, float *scratch,
                            size_t scratch_floats, scanerf_stream_t stream);
 
+/* ---- monocular prior losses (csrc/mono.hip): mono_loss.py DepthConsistencyLoss + DepthSmoothLoss (criterions.py:99-105,170-183)
+ *   and their gradient w.r.t. the per-ray rendered depth, in one call.  depth [B] = the merged pred_depth (tile.py:666-690);
+ *   ray_valid [B] (NULL = all): fore_valid | bg_valid; locs [B,3] int32 (view, px, py), integer pixel coordinates; a ray whose
+ *   locs fall outside [0,N) x [0,W) x [0,H) counts as invalid.  Views are grouped by locs[:,0] (any ray order).
+ *   Depth consistency (mono_depth [N,H,W], NULL or w_depth = 0: off): per view the scale / shift (h0, h1) of depth onto mono_depth
+ *   from f64 moments (h = 0 when det = 0); L_depth = sum m (h0 p + h1 - t)^2 / sum m over all views (0 when no ray is valid);
+ *   dL/dp = 2 m h0 (h0 p + h1 - t) / sum m (the gradient through h is 0 analytically).
+ *   Depth smoothness (mono_normal [N,H,W,3], NULL or w_smooth = 0: off; needs kinv [N,9] = K^-1 row-major and B % 4 == 0): rays
+ *   4k..4k+3 are a 2x2 patch (r = 2 dy + dx) of one view; valid iff all four rays are valid, share a view and n_r . mean(n) > 0.9;
+ *   L_smooth = mean over valid patches of 0.25 sum |normalize(mean n) . normalize(edge)| (0, zero gradient, when none).
+ *   loss [3] = (w_depth L_depth + w_smooth L_smooth, L_depth, L_smooth); grad_depth [B] = d loss[0] / d depth (overwritten).
+ *   No allocation, no host synchronisation, no float atomics (every sum in a fixed order: bit-reproducible).  scratch:
+ *   scanerf_mono_scratch_floats(B, N) floats, 8-byte aligned. */
+size_t scanerf_mono_scratch_floats(int B, int N);
+int scanerf_mono_loss_grad(const float *depth, const uint8_t *ray_valid, const int32_t *locs, const float *mono_depth,
+                           const float *mono_normal, const float *kinv, int N, int H, int W, int B, float w_depth, float w_smooth,
+                           float *loss, float *grad_depth, float *scratch, size_t scratch_floats, scanerf_stream_t stream);
+
 #define SCANERF_RAY_OUT 16
 
 #ifdef __cplusplus

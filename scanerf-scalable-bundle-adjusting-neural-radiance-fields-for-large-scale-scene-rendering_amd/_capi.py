@@ -94,6 +94,8 @@ PROTOTYPES = {
     "scanerf_warp_project": ("I", "PPPPPPPPPIIIIIPPPPPPP", REQ),
     "scanerf_warp_scratch_floats": ("Z", "III", REQ),
     "scanerf_warp_loss_grad": ("I", "PPPPPPPPPPPPIIIIIFPPPPPPZP", REQ),
+    "scanerf_mono_scratch_floats": ("Z", "II", REQ),
+    "scanerf_mono_loss_grad": ("I", "PPPPPPIIIIFFPPPZP", REQ),
 }
 SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if required]
 OPTIONAL_SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if not required]

@@ -9,8 +9,9 @@ Two execution paths over the same parameters:
              gradient of the table, fused sparse Adam kernel on the table;
   * "fused": one HIP launch for render forward and one for backward (render.py).
 
-Scope is the foreground branch on synthetic rays; data loading, warp/mono losses, pose
-refinement and pruning schedules belong to the trainer.
+Scope is the foreground branch on synthetic rays; data loading, pose refinement and pruning schedules belong to the
+trainer.  The warp and monocular loss terms join the fused steps through their hooks (warp.WarpLoss,
+mono.MonoLoss: warp=, mono= / locs=).
 """
 import math
 
@@ -566,7 +567,8 @@ def _table_grad_adam(model, route, compact, rays_o, rays_d, branches, lr, timer)
 
 
 def train_step_fused(model, dec_opt, rays_o, rays_d, target, S, global_step, table_lr=1e-2, timer=None,
-                     pose_grads=False, fused_scatter=None, compact_rays=None, dec_step=True, fused_adam=True, warp=None):
+                     pose_grads=False, fused_scatter=None, compact_rays=None, dec_step=True, fused_adam=True, warp=None,
+                     mono=None, locs=None):
     """The same iteration as train_step_ops on the fused kernels: one launch for the render forward,
     one for its adjoint, the atomic-free binned scatter for the table gradient, fused sparse Adam.
     fused_adam (default): the sparse Adam on the table runs in the accumulate's epilogue (no gradient table, model.features.grad
@@ -575,7 +577,14 @@ def train_step_fused(model, dec_opt, rays_o, rays_d, target, S, global_step, tab
     pose_grads=True also returns dL/d(rays_o), dL/d(rays_d) (feed them to the pose graph:
     torch.autograd.backward([rays_o, rays_d], [g_o, g_d]) -- camera_utils.py:65-84 in the reference).
     warp (warp.WarpLoss, default None): the multi-view warp term joins the loss; its gradient is added to grad_out before the
-    backward (and to the ray gradients with pose_grads), its dL/drts is left in warp.last_grad_rts."""
+    backward (and to the ray gradients with pose_grads), its dL/drts is left in warp.last_grad_rts.
+    mono (mono.MonoLoss, default None) with locs [B,3] int32 (view, px, py) of the rays: the monocular depth / smoothness terms
+    join the loss after the warp term; their depth gradient is added to grad_out before the backward.  The terms need the
+    uncompacted batch (2x2 patches, per-view groups): mono turns valid-ray compaction off at the steps where a term is added
+    (compact_rays=True with mono raises)."""
+    _check_mono(mono, locs)
+    if mono is not None and compact_rays:
+        raise ValueError("train_step_fused: compact_rays=True cannot be combined with mono (the terms need the uncompacted batch)")
     B = rays_o.shape[0]
     dev = model.device
     with torch.no_grad():
@@ -583,7 +592,8 @@ def train_step_fused(model, dec_opt, rays_o, rays_d, target, S, global_step, tab
             z, dist = model.sample(rays_o, rays_d, S)
         valid = render.ray_valid(z)  # all(z != -1) per ray (hashgrid/__init__.py:419)
         if compact_rays is None:  # a fully occupied sampler grid cannot produce invalid rays from inside the tile
-            compact_rays = not getattr(model, "_occ_full", False) and not pose_grads
+            compact_rays = (not getattr(model, "_occ_full", False) and not pose_grads
+                            and not (mono is not None and mono.active(global_step)))
         if compact_rays:
             # valid-ray compaction (hashgrid/__init__.py:419-421: the reference renders rays_o[valid] only) in one HIP launch
             # (csrc/compact.hip: wave ballot + popcount prefix sums): the fused backward runs its waves in lock step, so an
@@ -612,6 +622,10 @@ def train_step_fused(model, dec_opt, rays_o, rays_d, target, S, global_step, tab
         with _sec(timer, "warp_loss"):
             wterm = warp.fused_term(global_step, rays_o, rays_d, out, valid, grad_out,
                                     lambda o, d: _visibility_render_fore(model, o, d, S, global_step))
+    mterm = None
+    if mono is not None:
+        with _sec(timer, "mono_loss"):
+            mterm = mono.fused_term(global_step, locs, out, valid, grad_out)
     with torch.no_grad():
         gtab = model.overflow_grad() if fused_adam else torch.zeros_like(model.features)
         gblob = torch.zeros(network.PARAMSIZE, device=dev)
@@ -629,7 +643,14 @@ def train_step_fused(model, dec_opt, rays_o, rays_d, target, S, global_step, tab
             dec_opt.step()
     if wterm is not None:
         loss = loss + wterm[0]
+    if mterm is not None:
+        loss = loss + mterm
     return (loss[0], *g) if pose_grads else loss[0]
+
+
+def _check_mono(mono, locs):
+    if mono is not None and locs is None:
+        raise ValueError("scanerf: mono needs locs [B,3] int32 (view, px, py) of the batch's rays")
 
 
 # ---- the warp term's visibility render (warp_loss.py:355-378: the tile's renderer on the neighbour rays, no grad) ---------------
@@ -648,8 +669,9 @@ def _visibility_render_fgbg(model, rays_o, rays_d, S_fg, S_bg, global_step, inva
 
 
 def _fgbg_pass(model, rays_o, rays_d, target, S_fg, S_bg, global_step, invalid_underground, timer, pose_grads, warp, routes,
-               compact):
-    """Both branches of a tile's render on `routes` (table_grad_route): forward, the merged loss (+ the warp term), backward
+               compact, mono=None, locs=None):
+    """Both branches of a tile's render on `routes` (table_grad_route): forward, the merged loss (+ the warp, then the monocular
+    terms), backward
     -> (loss [1], (fg, bg) _Branch, grad_blob, gradient table or None, (g_o, g_d) or None).  On the records + adam2 route the
     steps' timer sections, gather_table(), the forward's record plans and the background's own record workspace; elsewhere
     fgbg_gradients' reference: the fp32 master, only the backward timed."""
@@ -683,6 +705,10 @@ def _fgbg_pass(model, rays_o, rays_d, target, S_fg, S_bg, global_step, invalid_u
         with _sec(timer, "warp_loss"):
             wterm = warp.fgbg_term(global_step, rays_o, rays_d, branches[0].out, branches[1].out, vf, vb, gfg, gbg,
                                    lambda o, d: _visibility_render_fgbg(model, o, d, S_fg, S_bg, global_step, invalid_underground))
+    mterm = None
+    if mono is not None:
+        with _sec(timer, "mono_loss"):
+            mterm = mono.fgbg_term(global_step, locs, branches[0].out, branches[1].out, vf, vb, gfg, gbg)
     with torch.no_grad():
         gtab = torch.zeros_like(model.features) if routes[0] in _TABLE_ROUTES else None
         gblob = torch.zeros(network.PARAMSIZE, device=dev)
@@ -697,26 +723,30 @@ def _fgbg_pass(model, rays_o, rays_d, target, S_fg, S_bg, global_step, invalid_u
             g = (g[0] + wterm[1], g[1] + wterm[2])
     if wterm is not None:
         loss = loss + wterm[0]
+    if mterm is not None:
+        loss = loss + mterm
     return loss, branches, gblob, gtab, g
 
 
 def fgbg_gradients(model, rays_o, rays_d, target, S_fg, S_bg, global_step, invalid_underground=False, timer=None,
-                   pose_grads=False, warp=None):
+                   pose_grads=False, warp=None, mono=None, locs=None):
     """Loss and parameter gradients of the complete per-tile render of tile.py:639-692 / :880-1015: foreground
     (occupancy-sampled, contract_fore) + T_left * background (inverse-z, contract_bg, infinity), MSE on the merged colour
     over all rays + 0.01 * (l2_reg_specular of both branches) -- two fused forward/backward pairs over the same table and
     decoder, each branch's table gradient into ONE gradient table.  Returns (loss, grad_table [16,T,2], grad_blob [13994])
     (+ dL/d(rays_o), dL/d(rays_d) with pose_grads: t16 backward on the fp32 table, any table size).
-    warp: as in train_step_fused, on the merged prediction (warp.WarpLoss.fgbg_term)."""
+    warp: as in train_step_fused, on the merged prediction (warp.WarpLoss.fgbg_term).
+    mono, locs: as in train_step_fused, on the merged depth d_fg + T_left d_bg (mono.MonoLoss.fgbg_term)."""
+    _check_mono(mono, locs)
     routes, compact = table_grad_route(FGBG_GRADIENTS, model.features.shape[1], rays_o.shape[0], [S_fg, S_bg],
                                        render.backward_arith())
     loss, _, gblob, gtab, g = _fgbg_pass(model, rays_o, rays_d, target, S_fg, S_bg, global_step, invalid_underground, timer,
-                                         pose_grads, warp, routes, compact)
+                                         pose_grads, warp, routes, compact, mono, locs)
     return (loss[0].detach(), gtab, gblob, *g) if pose_grads else (loss[0].detach(), gtab, gblob)
 
 
 def train_step_fgbg(model, dec_opt, rays_o, rays_d, target, S_fg, S_bg, global_step, table_lr=1e-2,
-                    invalid_underground=False, timer=None, pose_grads=False, dec_step=True, warp=None):
+                    invalid_underground=False, timer=None, pose_grads=False, dec_step=True, warp=None, mono=None, locs=None):
     """One complete training iteration of a tile (tile.py:880-1015: foreground + T_left * background, tile.py:639-692) on the
     fused kernels: both branches' forward, ONE loss launch pair for the merged prediction, both branches' backward emitting
     their scatter records, and ONE accumulate + sparse Adam over both record sets (the two gradients meet in one Adam step).
@@ -726,13 +756,15 @@ def train_step_fgbg(model, dec_opt, rays_o, rays_d, target, S_fg, S_bg, global_s
     the two branches' ray gradients, each formed inside its backward launch from the forward's position Jacobians
     (-> (loss, g_o, g_d)); dec_step=False: the caller steps the decoder's optimiser (it holds the camera parameters too).
     warp (warp.WarpLoss, default None): the multi-view warp term on the merged prediction, chained to both branches before their
-    backward (see train_step_fused)."""
+    backward (see train_step_fused).
+    mono (mono.MonoLoss, default None) with locs [B,3] int32: the monocular terms on the merged depth, after the warp term."""
+    _check_mono(mono, locs)
     routes, compact = table_grad_route(FGBG_STEP, model.features.shape[1], rays_o.shape[0], [S_fg, S_bg],
                                        render.backward_arith(), model._half_table is not None)
     if pose_grads and model.gather_table().dtype != torch.float32:
         raise RuntimeError("scanerf: train_step_fgbg(pose_grads=True) gathers from the fp32 table")
     loss, branches, gblob, gtab, g = _fgbg_pass(model, rays_o, rays_d, target, S_fg, S_bg, global_step, invalid_underground,
-                                                timer, pose_grads, warp, routes, compact)
+                                                timer, pose_grads, warp, routes, compact, mono, locs)
     with torch.no_grad():
         if routes[0] in _TABLE_ROUTES:
             model.features.grad = gtab

@@ -2,7 +2,8 @@
 :818-877, :880-1015) and HashGrid.pruning_grid (hashgrid/__init__.py:138-225) do around the hot path -- learning-rate
 schedules, 2x2 patch ray selection, the coarse-to-fine occupancy pruning schedule, checkpoints -- for one tile on one GPU.
 The multi-view warp loss of the default configuration (warp_loss.py, criterions.py:92-97) joins the iteration with
-TileTrainer(warp=warp.WarpLoss(...)).  Data loading, the monocular losses and image logging stay outside.
+TileTrainer(warp=warp.WarpLoss(...)), the monocular depth and depth-smoothness priors (mono_loss.py, criterions.py:99-105) with
+TileTrainer(mono=mono.MonoLoss(...)).  Data loading and image logging stay outside.
 """
 import math
 
@@ -158,20 +159,23 @@ class TileTrainer:
     """One tile's optimisation state and iteration (tile.py:296-332, :866-877, :880-1015) on the fused kernels.
 
     get_batch(step) -> (rays_o [B,3], rays_d [B,3], target [B,3]) supplies the rays (the reference draws 2x2 patches
-    per view: sample_patch_ray_idx).  The table is stepped by the fused sparse Adam kernel with the scheduled
+    per view: sample_patch_ray_idx); with mono set and no cameras it returns (rays_o, rays_d, target, locs [B,3] int32) --
+    the rays' (view, px, py), which the monocular terms read their maps at (cameras.pixel_locs).  The table is stepped by the fused sparse Adam kernel with the scheduled
     learning rate; the decoder by torch Adam with weight_decay 1e-6 (tile.py:308)."""
 
     def __init__(self, model, get_batch, total_step=40000, eta_hash=1e-2, eta_decoder=1e-3, grid_log2dim=(4, 5, 6, 7, 8, 9),
                  pruning_th=(0.1, 0.2, 0.3, 0.4), adjust_step=2000, dynamic_start=None, dynamic_end=None, dynamic_step=None,
                  num_sample=128, num_bg_sample=0, finest_resolution=2048, consensus=None, cameras=None, eta_cam=1e-3,
-                 cam_start_step=0, admm=False, warp=None):
+                 cam_start_step=0, admm=False, warp=None, mono=None):
         """cameras (cameras.CameraSet): pose refinement on -- get_batch(step) then returns (locs [B,3] int32 (view, px, py),
         target [B,3]) and the rays are generated from the current poses; se3_refine is the optimiser's second parameter
         group with its own schedule (tile.py:316-323).  admm: add the consensus penalty (consensus.py:70-76) to the
         pose gradient.  warp (warp.WarpLoss): the multi-view warp term is added to every iteration (criterions.py:92-97); with
-        cameras, its gradient w.r.t. the neighbour cameras' rts is fed to se3_refine as well.  None (default): no warp term."""
+        cameras, its gradient w.r.t. the neighbour cameras' rts is fed to se3_refine as well.  None (default): no warp term.
+        mono (mono.MonoLoss): the monocular depth / smoothness terms are added after the warp term (criterions.py:99-105), at
+        the batch's locs; with cameras they reach the poses through the ray gradients.  None (default): no monocular term."""
         self.model, self.get_batch = model, get_batch
-        self.warp = warp
+        self.warp, self.mono = warp, mono
         self.cameras, self.admm = cameras, admm
         groups = [{"params": model.decoder.parameters(), "lr": eta_decoder, "weight_decay": 1e-6}]
         sches = [Scheduler("decoder", eta_decoder, 0.1 * eta_decoder, total_step, groups=[0])]
@@ -210,11 +214,11 @@ class TileTrainer:
         if self.num_bg_sample > 0:   # the complete iteration (foreground + T_left * background), tile.py:639-692
             loss, g_o, g_d = train_step_fgbg(self.model, self.dec_opt, rays_o.detach(), rays_d.detach(), target, self.num_sample,
                                              self.num_bg_sample, self.global_step, table_lr=self.table_lr, pose_grads=True,
-                                             dec_step=False, **self._warp_kw())
+                                             dec_step=False, **self._warp_kw(locs))
         else:
             loss, g_o, g_d = train_step_fused(self.model, self.dec_opt, rays_o.detach(), rays_d.detach(), target, self.num_sample,
                                               self.global_step, table_lr=self.table_lr, pose_grads=True, dec_step=False,
-                                              **self._warp_kw())
+                                              **self._warp_kw(locs))
         torch.autograd.backward([rays_o, rays_d], [g_o, g_d])
         if self.warp is not None and self.warp.last_grad_rts is not None:
             # the neighbour cameras' share of the warp gradient (proj2neighbor_backward's grad_rts) -> se3_refine
@@ -224,8 +228,11 @@ class TileTrainer:
         self.dec_opt.step()
         return loss
 
-    def _warp_kw(self):
-        return {} if self.warp is None else {"warp": self.warp}
+    def _warp_kw(self, locs=None):
+        kw = {} if self.warp is None else {"warp": self.warp}
+        if self.mono is not None:
+            kw.update(mono=self.mono, locs=locs)
+        return kw
 
     def train_one_step(self):
         if self.cameras is not None:
@@ -235,13 +242,19 @@ class TileTrainer:
             self.sche.step(self.global_step, self.dec_opt)
             self.global_step += 1
             return loss
-        rays_o, rays_d, target = self.get_batch(self.global_step)
+        batch = self.get_batch(self.global_step)
+        rays_o, rays_d, target = batch[:3]
+        locs = None
+        if self.mono is not None:
+            if len(batch) != 4:
+                raise ValueError("TileTrainer(mono=...): get_batch must return (rays_o, rays_d, target, locs)")
+            locs = batch[3]
         if self.num_bg_sample > 0:
             loss = train_step_fgbg(self.model, self.dec_opt, rays_o, rays_d, target, self.num_sample, self.num_bg_sample,
-                                   self.global_step, table_lr=self.table_lr, **self._warp_kw())
+                                   self.global_step, table_lr=self.table_lr, **self._warp_kw(locs))
         else:
             loss = train_step_fused(self.model, self.dec_opt, rays_o, rays_d, target, self.num_sample, self.global_step,
-                                    table_lr=self.table_lr, **self._warp_kw())
+                                    table_lr=self.table_lr, **self._warp_kw(locs))
         # the reference steps its schedulers AFTER the optimisers: the rate computed at step s is used at step s+1
         self.table_sche.step(self.global_step)
         self.table_lr = self.table_sche.scheduler_list[0].eta
