@@ -1,11 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- training rays/s of the per-tile volume-rendering hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--path fused|ops] [--rays B] [--arith f32|h3|t16|t16s] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--path fused|ops] [--rays B] [--arith f32|h3|t16|t16s] [--dump-outputs DIR] [--full]
 
 `value` / `ms_per_step` are measured under the fastest F32-EQUIVALENT decoder arithmetic (render.FP32_EQUIV_ARITH; gradient
-error against the oracle ~5e-6 relative L2, reported live as `arith_evidence`); the reduced-precision "t16" step and the
-other arithmetics are timed beside it under their own keys.
+error against the oracle ~5e-6 relative L2, reported by `--full` as `arith_evidence`); with `--full` the reduced-precision "t16"
+step and the other arithmetics are timed beside it under their own keys.
+
+A plain run does what the headline needs and no more: set up, warm up, time the steps, write --dump-outputs, print the line (with
+`roofline`, computed from the timed steps' own section times).  `--full` adds everything else the benchmark measures or checks,
+each after the headline is measured: the other arithmetics' step times, the consensus exchange timed alone (`consensus_ms`), the
+live fabric-ceiling probe, the side legs (`side_legs`: op-by-op route, autograd route, stand-alone decoder, configs[4] render
+frame, the reference's default T = 2^24 iteration), the CPU baseline and the arithmetic evidence against the oracle
+(`--no-side-legs`, `--no-cpu-baseline`, `--arith-side-off` leave parts of it out).  The line says which it was (`"full"`).
 
 One "step" = one full training iteration of one tile on a synthetic ray batch
 (BASELINE.json configs[1]: L=16, T=2^19 fp32 table, 2-hidden x 64 decoder, 65 536 rays x
@@ -63,9 +70,13 @@ def parse():
     ap.add_argument("--rays", type=int, default=65536)
     ap.add_argument("--samples", type=int, default=128)
     ap.add_argument("--log2-T", type=int, default=19, help="hash-table entries per level (configs[1]: 19; the reference's default.yaml: 24)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else the benchmark measures or checks (see the module docstring); "
+                         "a plain run times the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline and arith_evidence")
     ap.add_argument("--no-side-legs", action="store_true",
-                    help="skip the two extra timings of the default run (ops_path_ms_per_step, render_ms_per_frame)")
+                    help="with --full: skip the side legs (ops_path_ms_per_step, autograd route, decoder_op, render_ms_per_frame, "
+                         "reference_default_*)")
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="launcher / collective rehearsal on gloo + CPU tensors: no kernels, no measurement")
     ap.add_argument("--tiles-per-gpu", type=int, default=1,
@@ -80,7 +91,8 @@ def parse():
     ap.add_argument("--infer-arith", default="t16", choices=["t16", "h3", "f32"],
                     help="decoder arithmetic of the render-time inference ops (configs4-render; hashgrid.lib.HASHGRID.INFER_ARITH): 16-sample "
                          "tiles (default), round 4's 32-sample-tile kernel, or the single-pass f32 kernel")
-    ap.add_argument("--arith-side-off", action="store_true", help="skip the side timings of the other arithmetics (profiling passes)")
+    ap.add_argument("--arith-side-off", action="store_true",
+                    help="with --full: skip the side timings of the other arithmetics (profiling passes)")
     ap.add_argument("--pose-grads", action="store_true",
                     help="with --workload configs1 / configs1-fgbg: the iteration also returns dL/d(rays_o), dL/d(rays_d) (the "
                          "reference's default: CAMOPT.ENABLE)")
@@ -456,7 +468,7 @@ def decoder_op_leg(dev, N, n=5):
 
 
 def side_legs(args, dev, rays_o, rays_d, target, S, step0):
-    """Two more timings inside the default run, so that they are on the driver's clock too (rank 0, N = 1, configs[1] only;
+    """More timings of the `--full` run, so that they are on the driver's clock too (rank 0, N = 1, configs[1] only;
     `--no-side-legs` skips them):
       ops_path_ms_per_step -- the same training iteration through the binding-surface ops one by one (`--path ops`: sampler,
         `embedding_bg_forward/backward_cuda` via the autograd wrapper, the decoder op of csrc/decoder.hip (what network.ShallowMLP
@@ -912,13 +924,14 @@ def main():
             outs.update(grad_rays_o=seeded_rows(res[1], DUMP_SAMPLE // 4), grad_rays_d=seeded_rows(res[2], DUMP_SAMPLE // 4))
         outs.update(decoder_params=mi.decoder.params.reshape(-1), table_sample=seeded_rows(mi.features.reshape(-1), DUMP_SAMPLE))
         dump_outputs(args.dump_outputs, outs)
-    # consensus exchange timed on its own (it runs once per SYN_ITERS steps)
-    sync()
-    c0 = time.perf_counter()
-    for _ in range(10):
-        admm.exchange(se3)
-    sync()
-    consensus_ms = (time.perf_counter() - c0) / 10 * 1e3
+    consensus_ms = None
+    if args.full:   # consensus exchange timed on its own (it runs once per SYN_ITERS steps)
+        sync()
+        c0 = time.perf_counter()
+        for _ in range(10):
+            admm.exchange(se3)
+        sync()
+        consensus_ms = (time.perf_counter() - c0) / 10 * 1e3
 
     t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
     if world > 1:
@@ -932,7 +945,7 @@ def main():
     if occ:
         dtype_label = "bf16 gather table, fp32 master + accumulate; " + dtype_label
     side_ms = {}
-    if fused and not occ and not fgbg and not args.arith and not args.arith_side_off:
+    if args.full and fused and not occ and not fgbg and not args.arith and not args.arith_side_off:
         for other in ("t16", "h3", "f32"):
             if other == arith:
                 continue
@@ -978,18 +991,22 @@ def main():
                        "path": path, "arith": arith if fused else "ops", "rays_per_step": B, "valid_ray_fraction": valid_frac, "samples": S,
                        "tiles_per_gpu": ntile, "parallelism": f"tile-per-gpu x{world}", "syn_iters": SYN_ITERS},
             "pose_grads": bool(args.pose_grads),
-            # the same step under the other arithmetics (ms): t16 = reduced-precision gradient products + 13-bit records;
-            # h3 = round 1's 32-sample-tile split kernel; f32 = exact f32-input MFMA
-            "t16_ms_per_step": side_ms.get("t16"), "h3_ms_per_step": side_ms.get("h3"), "f32_arith_ms_per_step": side_ms.get("f32"),
-            "consensus_ms": consensus_ms,
-            "consensus_frac_of_iteration": consensus_ms / (SYN_ITERS * ms_per_step),
             # which library produced these numbers: the ISA audit's verdict on the loaded file (tools/isa_audit.py), its compiler, and
             # whether it is the product build (no environment switches) or an experiments build (make EXP=1)
             "library": library_state(),
+            "full": bool(args.full),
         }
+        if args.full:
+            line.update({
+                # the same step under the other arithmetics (ms): t16 = reduced-precision gradient products + 13-bit records;
+                # h3 = round 1's 32-sample-tile split kernel; f32 = exact f32-input MFMA
+                "t16_ms_per_step": side_ms.get("t16"), "h3_ms_per_step": side_ms.get("h3"), "f32_arith_ms_per_step": side_ms.get("f32"),
+                "consensus_ms": consensus_ms,
+                "consensus_frac_of_iteration": consensus_ms / (SYN_ITERS * ms_per_step),
+            })
         if timer and timer.count:
             line["roofline"] = roofline(timer, arith if fused else "f32", args, B, S, valid_frac, fgbg, ms_per_step)
-        if timer and timer.count and world == 1 and "fabric_requests" in line.get("roofline", {}):
+        if args.full and timer and timer.count and world == 1 and "fabric_requests" in line.get("roofline", {}):
             try:   # the ceiling of roofline.fabric_requests, measured live beside the committed micro-benchmarks' 57 G/s
                 live = fabric_ceiling_live(dev)
                 fr = line["roofline"]["fabric_requests"]
@@ -997,8 +1014,8 @@ def main():
                 fr["frac_at_live_ceiling"] = fr["per_step"] / (live * 1e9) * 1e3 / ms_per_step
             except (RuntimeError, AttributeError) as e:
                 print(f"bench.py: fabric ceiling probe skipped: {e}", file=sys.stderr)
-        if (world == 1 and fused and args.workload == "configs1" and not args.no_side_legs and not args.arith and not args.pose_grads
-                and ntile == 1 and args.scatter == "auto"):
+        if (args.full and world == 1 and fused and args.workload == "configs1" and not args.no_side_legs and not args.arith
+                and not args.pose_grads and ntile == 1 and args.scatter == "auto"):
             del models, dec_opts, model, dec_opt
             torch.cuda.empty_cache()
             try:   # (the headline above is already measured: a failing side leg must not discard it)
@@ -1006,7 +1023,7 @@ def main():
             except Exception as e:  # noqa: BLE001
                 line["side_legs_error"] = f"{type(e).__name__}: {e}"[:400]
                 print(f"bench.py: side legs failed: {e}", file=sys.stderr)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(S)
             if fused and not occ and not fgbg:
                 line["arith_evidence"] = arith_evidence(S)

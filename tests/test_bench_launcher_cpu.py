@@ -103,3 +103,16 @@ def test_roofline_fields_recompute_from_the_committed_counter_file():
     # another configuration than the profiled one: no counter fields
     r2 = bench.roofline(_FakeTimer(secs), "t16s", _args(pose_grads=True), 65536, 128, 1.0, False, 9.8)
     assert r2["traffic"] is None and "frac_counter" not in r2["kernels"]["render_backward"]
+
+
+def test_full_is_off_by_default_and_reaches_every_rank(monkeypatch):
+    # a plain run times the headline only; --full is passed through to the launched ranks like every other flag
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--full"])
+    assert bench.parse().full is True
+    r = _run("--gpus", "2", "--steps", "4", "--dry-run-cpu", "--full")
+    assert r.returncode == 0, r.stderr
+    assert json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])["n_gpus"] == 2

@@ -44,7 +44,7 @@ for f in glob.glob(f"{d}/p*/**/*counter_collection.csv", recursive=True):
     for (k, c), (v, n) in acc.items():
         kern[k][c] = v / n
 SCLK = 2.1e9
-out = {"_source": "rocprofv3 --kernel-trace --stats and --pmc passes (separate; tools/profile_bench.sh) of `python3 bench.py --gpus 1 --no-cpu-baseline --no-side-legs`: per-launch averages, MI355X, configs[1]",
+out = {"_source": "rocprofv3 --kernel-trace --stats and --pmc passes (separate; tools/profile_bench.sh) of `python3 bench.py --full --gpus 1 --no-cpu-baseline --no-side-legs`: per-launch averages, MI355X, configs[1]",
        "_corrections": "FETCH_SIZE / WRITE_SIZE: reported KB x 1024 (MI355X_MICROARCH.md); FETCH_SIZE tallies the 128-B requests of 16-B/lane streams as 64 B: traffic_bytes = fetch_bytes x 2 + write_bytes for the kernels marked fetch_x2 (record stream of the accumulate, x-stash of the backward), fetch_bytes + write_bytes otherwise; SQ_* are sums over the launch; mfma_busy assumes SCLK 2.1 GHz under load",
        "kernels": {}}
 for k, v in sorted(kern.items(), key=lambda kv: -kv[1].get("avg_us", 0)):

@@ -5,8 +5,9 @@
 out=$GRAFT_REPO_ROOT/gpurun_out/$1
 shift
 mkdir -p $out
+# --full: the kernel table and the JSON list the other arithmetics' kernels (their side timings) beside the headline's
+B="python3 $(cd "$(dirname "$0")/.." && pwd)/bench.py --full --gpus 1 --no-cpu-baseline --no-side-legs"
 cd /tmp && export TMPDIR=/tmp
-B="python3 $GRAFT_REPO_ROOT/bench.py --gpus 1 --no-cpu-baseline --no-side-legs"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- $B --steps 10 --warmup 2 "$@" > $out/stats.log 2>&1 || echo "stats pass failed"
 python3 $GRAFT_REPO_ROOT/tools/summarize_prof.py stats $out/stats > $out/kernel_stats.txt 2>&1
 i=0

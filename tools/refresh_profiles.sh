@@ -4,7 +4,7 @@
 out=$GRAFT_REPO_ROOT/gpurun_out/refresh
 mkdir -p $out
 cd $GRAFT_REPO_ROOT
-b() { name=$1; shift; timeout -k 10 280 python bench.py "$@" > $out/$name.log 2>&1; tail -1 $out/$name.log > $out/$name.json; echo "$name: $(python3 -c "import json,sys; d=json.load(open('$out/$name.json')); print(d['ms_per_step'], d['value'])" 2>&1 | tail -1)"; }
+b() { name=$1; shift; timeout -k 10 280 python bench.py --full "$@" > $out/$name.log 2>&1; tail -1 $out/$name.log > $out/$name.json; echo "$name: $(python3 -c "import json,sys; d=json.load(open('$out/$name.json')); print(d['ms_per_step'], d['value'])" 2>&1 | tail -1)"; }
 b bench_configs1
 b bench_configs1_pose --pose-grads --no-cpu-baseline
 b bench_fgbg --workload configs1-fgbg --no-cpu-baseline
