@@ -204,7 +204,7 @@ static void sample_sparse_ray(const float o[3], const float d[3], int S, float *
         }
         dda_step(&s);
     }
-    if (count == 0) return;
+    if (!count) return;
 
     dda_init(&s, og, d, bound, side, tsize);
     int left = S, seg = 0;
@@ -261,7 +261,7 @@ ORC_API int orc_sample_insideout_block(const float *rays_o, const float *rays_d,
         float interval = (b.y - b.x) / (float)(S - 1);
         for (int k = 0; k < S; ++k) z_vals[(size_t)i * S + k] = b.x + (float)k * interval;
         float inv_near = 1.0f / b.y, inv_far = 1.0f / far_;
-        float inv_bound = inv_far - inv_near;
+        const float inv_bound = inv_far - inv_near;
         float step = 1.0f / (float)(S_bg - 1);
         for (int k = 0; k < S_bg; ++k)
             z_vals_bg[(size_t)i * S_bg + k] = 1.0f / (step * (float)k * inv_bound + inv_near);
@@ -663,7 +663,8 @@ ORC_API void orc_render_sample_points(const float *rays_o, const float *rays_d, 
                 dda_step(&s);
             }
             if (num_seg == 0) { tsx = by; step++; continue; }
-            int num = 0, count = 0;
+            int num = 0;
+            int count = 0;
             dda_init(&s, og, d, ts, side, tsize);
             while (!dda_terminate(&s)) {
                 dda_next(&s);
@@ -1004,7 +1005,7 @@ ORC_API void orc_ray_firsthit_block(const float *rays_o, const float *rays_d, co
 {
     for (int i = 0; i < B; ++i) {
         const float *o = rays_o + 3 * i, *d = rays_d + 3 * i;
-        float dis = 10000000.0f;
+        float dis = 1e7f;
         int last = -1;
         for (int k = 0; k < nb; ++k) {
             const int b = tracing_blocks[(size_t)i * nb + k];

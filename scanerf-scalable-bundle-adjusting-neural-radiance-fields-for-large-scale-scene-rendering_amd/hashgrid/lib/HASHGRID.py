@@ -35,14 +35,21 @@ INFER_ARITH = "t16"
 _INFER_FLAGS = {"t16": 0, "h3": 8, "f32": 16}   # include/scanerf_hip.h SCANERF_INFER_H3 / SCANERF_INFER_F32
 
 
+def _in_domain(points):
+    """Every point in [-2, 2]^3, the encoder's stated domain (scanerf_hip.h, Domain), for which the binned route is defined (in
+    every record format).  This drop-in binding goes beyond that precondition as the reference's kernel does: it extrapolates
+    points outside, and so does the atomic kernel they are sent to."""
+    return bool(points.detach().abs().amax() <= 2.0)
+
+
 def embedding_bg_backward_cuda(points, grad_in, grad_points, grad_features, features, resolutions):
     """hashgrid.h:45-51: accumulates into grad_points [N,3] and grad_features [L,T,2].
     The table gradient goes through the atomic-free binned scatter (csrc/scatter.hip) when the
-    shape allows; TABLE_GRAD_ROUTE = "atomics" (module attribute) forces the reference-style atomic kernel; RECORD_FORMAT
+    shape allows and every point lies in [-2, 2]^3 (one reduction and host read); TABLE_GRAD_ROUTE = "atomics" (module attribute) forces the reference-style atomic kernel; RECORD_FORMAT
     (-1 = default: 12-byte records for 16-level point-major rows, 0 = 16-byte, 2 = 12-byte) is the op's `compact_records`."""
     N, (L, T) = points.shape[0], features.shape[:2]
     need = 0
-    if grad_features is not None and N >= 4096 and TABLE_GRAD_ROUTE != "atomics":
+    if grad_features is not None and N >= 4096 and TABLE_GRAD_ROUTE != "atomics" and _in_domain(points):
         need = lib().scanerf_embedding_bwd_workspace_bytes(N, L, T)
     if need:
         ws = workspace(points.device, need)
