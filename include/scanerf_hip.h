@@ -548,6 +548,46 @@ int scanerf_mono_loss_grad(const float *depth, const uint8_t *ray_valid, const i
                            const float *mono_normal, const float *kinv, int N, int H, int W, int B, float w_depth, float w_smooth,
                            float *loss, float *grad_depth, float *scratch, size_t scratch_floats, scanerf_stream_t stream);
 
+/* ---- ray / triangle-mesh tracer (csrc/mesh.hip): the reference's third compiled module, fastMesh (fastMesh/binding.cpp:
+ *   build / fisrtHit / firstEnter / getSceneBound).  A uniform grid of 2^log2dim cells per axis (4 <= log2dim <= 7; the reference's
+ *   LOG2DIM is 6) over the cube [min_corner, min_corner + 2^log2dim * cell]; scene_info [4] f32 DEVICE = (min_corner, cell), cell =
+ *   largest extent of the vertex bounds / 2^log2dim.  vertices [V,3] f32, faces [F,3] i32.  Cell index n = (x << 2 log2dim) |
+ *   (y << log2dim) | z.  A face is registered in every cell its axis-aligned box overlaps (tile_structure.h:43-82); faces with a vertex
+ *   index outside [0,V) are left out.
+ * Build (replaces break_into_tiles, tile_structure.h:13-106, a host loop; here on the device, without atomics, bit-reproducible):
+ *   scanerf_mesh_count_cells: counts [F] = number of cells of each face;
+ *   scanerf_mesh_emit_keys: keys [n_keys] i64 = (cell << 32) | face for every (face, cell) pair, face f's from offsets [F] (the
+ *     exclusive scan of counts); sorted by the caller they are cell_faces in the reference's order (ascending face inside a cell);
+ *   scanerf_mesh_cell_boxes: cell_box [n_cells,6] = min xyz, max xyz over the vertices of the faces of each occupied cell (what
+ *     singleRay_firstEnter recomputes per ray, fastMesh_kernel.cu:157-184); start_num [n_cells,2] i32 = (start, count) into
+ *     cell_faces [n_entries] i32;
+ *   scanerf_mesh_gather_triangles: tris [n_entries,9] = (A, B - A, C - A) per cell_faces entry (optional: first_hit without its two
+ *     indirections).
+ * Traces (replace firstHit_cuda / firstEnter_cuda, fastMesh_kernel.cu:195-329): rays_o, rays_d [B,3] (not assumed normalised: t in
+ *   units of |d|), out [B] f32, 0 = nothing found.  bitmask [2^(3 log2dim) / 64] u64, rank [same] u32 = set bits in all earlier words.
+ *   The ray is clipped to the grid cube first (origins outside the grid are valid).  lds != 0 stages bitmask and rank into the LDS
+ *   (log2dim <= 6).
+ *   scanerf_mesh_first_hit: nearest intersection t > 0, two-sided, edges inclusive; the candidate is carried across cells (the
+ *     reference returns at the first cell with any hit, :284-290).  tris != NULL: pre-gathered triangles; else vertices / faces /
+ *     cell_faces.
+ *   scanerf_mesh_first_enter: the first occupied cell in ray order whose cell_box the ray hits: the slab entry distance (clamped
+ *     at 0, so a ray that starts inside that box gives 0 = nothing, as the reference, :181-186). */
+int scanerf_mesh_count_cells(const float *vertices, const int32_t *faces, int V, int F, int log2dim, const float *scene_info,
+                             int32_t *counts, scanerf_stream_t stream);
+int scanerf_mesh_emit_keys(const float *vertices, const int32_t *faces, int V, int F, int log2dim, const float *scene_info,
+                           const int64_t *offsets, int64_t *keys, long long n_keys, scanerf_stream_t stream);
+int scanerf_mesh_cell_boxes(const float *vertices, const int32_t *faces, const int32_t *start_num, const int32_t *cell_faces,
+                            int n_cells, float *cell_box, scanerf_stream_t stream);
+int scanerf_mesh_gather_triangles(const float *vertices, const int32_t *faces, const int32_t *cell_faces, long long n_entries,
+                                  float *tris, scanerf_stream_t stream);
+int scanerf_mesh_first_hit(const float *rays_o, const float *rays_d, int B, const float *vertices, const int32_t *faces,
+                           const float *tris, const uint64_t *bitmask, const uint32_t *rank, const int32_t *start_num,
+                           const int32_t *cell_faces, const float *scene_info, int log2dim, int lds, float *out,
+                           scanerf_stream_t stream);
+int scanerf_mesh_first_enter(const float *rays_o, const float *rays_d, int B, const uint64_t *bitmask, const uint32_t *rank,
+                             const int32_t *start_num, const float *cell_box, const float *scene_info, int log2dim, int lds,
+                             float *out, scanerf_stream_t stream);
+
 #define SCANERF_RAY_OUT 16
 
 #ifdef __cplusplus

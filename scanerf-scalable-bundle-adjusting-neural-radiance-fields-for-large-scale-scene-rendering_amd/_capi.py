@@ -96,6 +96,12 @@ PROTOTYPES = {
     "scanerf_warp_loss_grad": ("I", "PPPPPPPPPPPPIIIIIFPPPPPPZP", REQ),
     "scanerf_mono_scratch_floats": ("Z", "II", REQ),
     "scanerf_mono_loss_grad": ("I", "PPPPPPIIIIFFPPPZP", REQ),
+    "scanerf_mesh_count_cells": ("I", "PPIIIPPP", REQ),
+    "scanerf_mesh_emit_keys": ("I", "PPIIIPPPLP", REQ),
+    "scanerf_mesh_cell_boxes": ("I", "PPPPIPP", REQ),
+    "scanerf_mesh_gather_triangles": ("I", "PPPLPP", REQ),
+    "scanerf_mesh_first_hit": ("I", "PPIPPPPPPPPIIPP", REQ),
+    "scanerf_mesh_first_enter": ("I", "PPIPPPPPIIPP", REQ),
 }
 SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if required]
 OPTIONAL_SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if not required]

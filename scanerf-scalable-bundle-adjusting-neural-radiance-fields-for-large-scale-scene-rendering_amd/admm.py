@@ -42,11 +42,18 @@ class AdmmDriver:
 
     trainers: this rank's TileTrainer objects (each with .cameras = CameraSet over its visible views and .consensus =
     ConsensusState over the same views' global camera ids).  Every rank must construct the driver with the same
-    total_step / syn_start / syn_iters: the exchanges are collectives."""
+    total_step / syn_start / syn_iters: the exchanges are collectives.
+    fmesh (fastmesh.FastMesh): the ONE scene-mesh tracer of this process (admm_trainer.py:205,290), handed to every tile of the
+    rank that has none of its own; a tile still calls fmesh.set(center, size) with its own box before it uses the tracer."""
 
     def __init__(self, trainers, total_step, syn_iters=100, syn_start=0, confidence=None, log_dir=None, group=None,
-                 depth_hooks=None):
+                 depth_hooks=None, fmesh=None):
         self.trainers = list(trainers)
+        self.fmesh = fmesh
+        if fmesh is not None:
+            for t in self.trainers:
+                if getattr(t, "fmesh", None) is None:
+                    t.fmesh = fmesh
         self.stretches = syn_schedule(total_step, syn_start, syn_iters)
         self.confidence = confidence
         self.log_dir, self.group = log_dir, group

@@ -1,0 +1,284 @@
+"""`FastMesh`: the reference's ray / mesh tracer module (fastMesh/__init__.py:9-133) with its method names and return
+conventions, on the HIP tracer of csrc/mesh.hip.
+
+The acceleration structure -- a uniform grid of 2^log2dim cells per axis with a bitmask, a per-word rank, per-cell face
+lists and per-cell boxes -- is built on the device from the [V,3] float32 / [F,3] int32 arrays of formats.read_ply (the
+reference builds it in a host loop, fastMesh/include/tile_structure.h:13-106).  The build uses no atomics on floats and no
+data-dependent order: two builds of one mesh give the same arrays bit for bit.
+
+Two deliberate differences from the reference's kernels:
+  * rays are clipped to the grid cube first, so origins outside the mesh bounds are traced correctly;
+  * first_hit carries its nearest candidate across cells; the reference returns at the first cell with any hit, even one that
+    lies beyond that cell, which hides nearer surfaces behind large triangles.
+There is no CPU path: CPU tensors raise.
+"""
+import torch
+
+from . import formats
+from ._capi import check, dev_ptr, lib, stream
+from .cuda import background_sampling_cuda, ray_aabb_intersection
+
+_f32, _i32, _i64 = torch.float32, torch.int32, torch.int64
+
+CHUNK = 1 << 20            # rays per launch of the composite methods: their temporaries stay at a few MB for any frame size
+PREGATHER_MAX_BYTES = 256 << 20   # pre-gathered triangles (36 B per face-list entry) are kept up to this size
+
+
+def _require_gpu(t, name):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"scanerf: {name} must live on the GPU (no CPU path exists); got "
+                           f"{t.device if isinstance(t, torch.Tensor) else type(t).__name__}")
+
+
+class FastMesh:
+    """FastMesh(path): read a PLY mesh and build the tracer on the current GPU (or `device`)."""
+
+    def __init__(self, path, device=None, log2dim=6, pregather=None):
+        vertices, faces = formats.read_ply(path)
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self._build(torch.from_numpy(vertices).to(device), torch.from_numpy(faces).to(device), log2dim, pregather)
+
+    @classmethod
+    def from_arrays(cls, vertices, faces, device, log2dim=6, pregather=None):
+        """vertices [V,3] float32, faces [F,3] int32 (numpy arrays or tensors) -> FastMesh on `device`.
+        pregather: keep (A, B - A, C - A) per face-list entry for first_hit (36 B per entry); None = when they fit in
+        PREGATHER_MAX_BYTES; False = the indexed form (12 B per face and per vertex)."""
+        self = cls.__new__(cls)
+        self._build(torch.as_tensor(vertices).to(device), torch.as_tensor(faces).to(device), log2dim, pregather)
+        return self
+
+    # ---- structure ------------------------------------------------------------------------------------------------------------
+    def _build(self, vertices, faces, log2dim, pregather):
+        _require_gpu(vertices, "vertices")
+        _require_gpu(faces, "faces")
+        if not 4 <= int(log2dim) <= 7:
+            raise ValueError(f"scanerf: FastMesh log2dim must be 4..7, got {log2dim}")
+        v = vertices.to(_f32).reshape(-1, 3).contiguous()
+        f = faces.to(_i32).reshape(-1, 3).contiguous()
+        if v.shape[0] == 0 or f.shape[0] == 0:
+            raise ValueError("scanerf: FastMesh needs a mesh with vertices and faces")
+        dev, L = v.device, int(log2dim)
+        side = 1 << L
+        mn, mx = v.amin(0), v.amax(0)
+        cell = (mx - mn).amax() / side
+        self.device, self.log2dim = dev, L
+        self.vertices, self.faces = v, f
+        self.scene_info = torch.cat([mn, cell[None]]).contiguous()      # (min_corner, cell): what the kernels read
+        self.scene_bound = torch.cat([mn, mx]).contiguous()             # getSceneBound(): min and max corner of the vertices
+        V, F = v.shape[0], f.shape[0]
+        l = lib()
+        counts = torch.empty(F, dtype=_i32, device=dev)
+        check(l.scanerf_mesh_count_cells(dev_ptr(v, _f32, "vertices"), dev_ptr(f, _i32, "faces"), V, F, L,
+                                         dev_ptr(self.scene_info, _f32, "scene_info"), dev_ptr(counts, _i32, "counts"), stream()),
+              "mesh_count_cells")
+        ends = torch.cumsum(counts, 0, dtype=_i64)
+        total = int(ends[-1])
+        if total <= 0:
+            raise ValueError("scanerf: FastMesh: no face lies inside the vertex bounds (degenerate mesh or bad indices)")
+        if total >= 1 << 31:
+            raise ValueError(f"scanerf: FastMesh: {total} (face, cell) pairs do not fit 31 bits; use a smaller log2dim")
+        offsets = (ends - counts).contiguous()
+        keys = torch.empty(total, dtype=_i64, device=dev)
+        check(l.scanerf_mesh_emit_keys(dev_ptr(v, _f32, "vertices"), dev_ptr(f, _i32, "faces"), V, F, L,
+                                       dev_ptr(self.scene_info, _f32, "scene_info"), dev_ptr(offsets, _i64, "offsets"),
+                                       dev_ptr(keys, _i64, "keys"), total, stream()), "mesh_emit_keys")
+        keys = torch.sort(keys)[0]            # distinct keys: the order does not depend on the sort's stability
+        cells = keys >> 32
+        self.cell_faces = (keys & 0xFFFFFFFF).to(_i32).contiguous()
+        occupied, per_cell = torch.unique_consecutive(cells, return_counts=True)
+        starts = torch.cumsum(per_cell, 0) - per_cell
+        self.start_num = torch.stack([starts, per_cell], 1).to(_i32).contiguous()
+        n_words = (side ** 3) // 64
+        word, bit = occupied >> 6, occupied & 63
+        # distinct bits of one word add up to their OR; integer adds are exact in any order
+        self.bitmask = torch.zeros(n_words, dtype=_i64, device=dev).index_add_(0, word, torch.ones_like(bit) << bit)
+        per_word = torch.zeros(n_words, dtype=_i64, device=dev).index_add_(0, word, torch.ones_like(bit))
+        self.rank = (torch.cumsum(per_word, 0) - per_word).to(_i32).contiguous()
+        self.num_cells = int(occupied.shape[0])
+        self.cell_box = torch.empty(self.num_cells, 6, dtype=_f32, device=dev)
+        check(l.scanerf_mesh_cell_boxes(dev_ptr(v, _f32, "vertices"), dev_ptr(f, _i32, "faces"),
+                                        dev_ptr(self.start_num, _i32, "start_num"), dev_ptr(self.cell_faces, _i32, "cell_faces"),
+                                        self.num_cells, dev_ptr(self.cell_box, _f32, "cell_box"), stream()), "mesh_cell_boxes")
+        self.tris = None
+        if pregather is None:
+            pregather = total * 36 <= PREGATHER_MAX_BYTES
+        if pregather:
+            self.tris = torch.empty(total, 9, dtype=_f32, device=dev)
+            check(l.scanerf_mesh_gather_triangles(dev_ptr(v, _f32, "vertices"), dev_ptr(f, _i32, "faces"),
+                                                  dev_ptr(self.cell_faces, _i32, "cell_faces"), total,
+                                                  dev_ptr(self.tris, _f32, "tris"), stream()), "mesh_gather_triangles")
+        self.lds = False          # stage bitmask + rank into the LDS (log2dim <= 6): measured slower on frames (DESIGN.md 4.10 of the
+                                  # current document); the switch stays for measurement
+        self.bbox_center = self.bbox_size = None
+
+    def set(self, bbox_center, bbox_size):
+        """The tile box render_mask / compute_bgdepth* test against (tile.py: fmesh.set(center, size); full side lengths)."""
+        self.bbox_center = torch.as_tensor(bbox_center, dtype=_f32).to(self.device).contiguous()
+        self.bbox_size = torch.as_tensor(bbox_size, dtype=_f32).to(self.device).contiguous()
+
+    def get_sceneinfo(self):
+        """getSceneBound(): [6] = min corner, max corner of the vertices."""
+        return self.scene_bound
+
+    # ---- the two traces -----------------------------------------------------------------------------------------------------
+    def _rays(self, rays_o, rays_d):
+        _require_gpu(rays_o, "rays_o")
+        _require_gpu(rays_d, "rays_d")
+        o, d = rays_o.detach().to(_f32).contiguous(), rays_d.detach().to(_f32).contiguous()
+        if o.dim() != 2 or o.shape[1] != 3 or o.shape != d.shape:
+            raise RuntimeError(f"scanerf: rays must be [B,3], got {tuple(o.shape)} and {tuple(d.shape)}")
+        return o, d
+
+    def first_hit(self, rays_o, rays_d, out=None):
+        """[B] distance (in units of |rays_d|) to the nearest triangle along each ray, two-sided, t > 0; 0 where none."""
+        o, d = self._rays(rays_o, rays_d)
+        B = o.shape[0]
+        if out is None:
+            out = torch.empty(B, dtype=_f32, device=o.device)
+        pre = self.tris is not None
+        check(lib().scanerf_mesh_first_hit(
+            dev_ptr(o, _f32, "rays_o"), dev_ptr(d, _f32, "rays_d"), B, dev_ptr(self.vertices, _f32, "vertices"),
+            dev_ptr(self.faces, _i32, "faces"), dev_ptr(self.tris, _f32, "tris") if pre else None,
+            dev_ptr(self.bitmask, _i64, "bitmask"), dev_ptr(self.rank, _i32, "rank"), dev_ptr(self.start_num, _i32, "start_num"),
+            dev_ptr(self.cell_faces, _i32, "cell_faces"), dev_ptr(self.scene_info, _f32, "scene_info"), self.log2dim,
+            int(self.lds), dev_ptr(out, _f32, "out"), stream()), "mesh_first_hit")
+        return out
+
+    def first_enter(self, rays_o, rays_d, out=None):
+        """[B] the reference's conservative occluder distance: entry of the ray into the box of the first occupied cell (in ray
+        order) whose box it hits.  The entry is clamped at 0, so a ray that STARTS inside that box returns 0.0 = "nothing",
+        exactly as a ray that meets no cell: render_mask relies on depth == 0 meaning visible (fastMesh_kernel.cu:181-191)."""
+        o, d = self._rays(rays_o, rays_d)
+        B = o.shape[0]
+        if out is None:
+            out = torch.empty(B, dtype=_f32, device=o.device)
+        check(lib().scanerf_mesh_first_enter(
+            dev_ptr(o, _f32, "rays_o"), dev_ptr(d, _f32, "rays_d"), B, dev_ptr(self.bitmask, _i64, "bitmask"),
+            dev_ptr(self.rank, _i32, "rank"), dev_ptr(self.start_num, _i32, "start_num"), dev_ptr(self.cell_box, _f32, "cell_box"),
+            dev_ptr(self.scene_info, _f32, "scene_info"), self.log2dim, int(self.lds), dev_ptr(out, _f32, "out"), stream()),
+              "mesh_first_enter")
+        return out
+
+    # ---- the reference's methods --------------------------------------------------------------------------------------------
+    def _box(self):
+        if self.bbox_center is None:
+            raise RuntimeError("scanerf: FastMesh.set(bbox_center, bbox_size) first")
+        return self.bbox_center, self.bbox_size
+
+    def _bounds(self, o, d):
+        center, size = self._box()
+        bounds = torch.full((o.shape[0], 2), -1.0, dtype=_f32, device=o.device)
+        ray_aabb_intersection(o, d, center, size, bounds)
+        return bounds
+
+    @torch.no_grad()
+    def render_depth(self, rays_o, rays_d):
+        """[B,1] first_hit depth."""
+        return self.first_hit(rays_o, rays_d)[:, None]
+
+    @torch.no_grad()
+    def render_mask(self, rays_o, rays_d, trust_mesh=False):
+        """[B,1] bool, True = the tile box is visible along the ray: the occluder (first_enter, or first_hit with trust_mesh)
+        lies beyond the ray's entry into the box, or there is none (depth == 0), or the origin is inside the box."""
+        o, d = self._rays(rays_o, rays_d)
+        center, size = self._box()
+        mask = torch.empty(o.shape[0], 1, dtype=torch.bool, device=o.device)
+        for i in range(0, o.shape[0], CHUNK):
+            oc, dc = o[i:i + CHUNK], d[i:i + CHUNK]
+            depth = (self.first_hit if trust_mesh else self.first_enter)(oc, dc)[:, None]
+            near = self._bounds(oc, dc)[:, :1]
+            inside = torch.all(torch.abs(oc - center) < (size / 2.0), dim=-1, keepdim=True)
+            mask[i:i + CHUNK] = ((depth > near) & (near != -1)) | (depth == 0) | inside
+        return mask
+
+    def _bgdepth(self, o, d):
+        """-> exit bounds [b,2], valid = the ray meets the box, first_hit from the box exit [b,1]."""
+        bounds = self._bounds(o, d)
+        valid = bounds[:, 1] != -1
+        start = torch.where(valid[:, None], o + bounds[:, 1:] * d, o)
+        return bounds, valid, self.first_hit(start, d)[:, None]
+
+    @torch.no_grad()
+    def compute_bgdepth_batch(self, rays_o, rays_d):
+        """-> bg_z [B,1], has_bg [B], bounds [B,2]: the first mesh hit BEHIND the tile box, measured from the ray origin
+        (box exit distance + first_hit from the exit point); 1000 + exit for rays whose own first_hit finds nothing ("no
+        background").  Unlike the reference (which moves the caller's rays_o to the exit points in place and is therefore
+        called on a clone, fastMesh/__init__.py:64,80) the inputs are left alone."""
+        o, d = self._rays(rays_o, rays_d)
+        B = o.shape[0]
+        bg_z = torch.empty(B, 1, dtype=_f32, device=o.device)
+        has_bg = torch.empty(B, dtype=torch.bool, device=o.device)
+        bounds = torch.empty(B, 2, dtype=_f32, device=o.device)
+        for i in range(0, B, CHUNK):
+            oc, dc = o[i:i + CHUNK], d[i:i + CHUNK]
+            depth_z = self.first_hit(oc, dc)[:, None]
+            b, valid, z = self._bgdepth(oc, dc)
+            z = torch.where(depth_z == 0, torch.full_like(z, 1000.0), z)
+            has_bg[i:i + CHUNK] = (z[:, 0] > 0) & valid
+            bg_z[i:i + CHUNK] = torch.where(valid[:, None], z + b[:, 1:], z)
+            bounds[i:i + CHUNK] = b
+        return bg_z, has_bg, bounds
+
+    @torch.no_grad()
+    def background_sampling(self, rays_o, rays_d, num_sample, sample_range):
+        """-> z_vals [B,num_sample], valid [B]: background_sampling_cuda between the box exit and the background depth."""
+        o, d = self._rays(rays_o, rays_d)
+        bg_z, valid, bounds = self.compute_bgdepth_batch(o, d)
+        z_vals = torch.full((o.shape[0], num_sample), -1.0, dtype=_f32, device=o.device)
+        background_sampling_cuda(o, d, bounds[:, 1:].contiguous(), bg_z, z_vals, num_sample, float(sample_range))
+        return z_vals, valid
+
+    @torch.no_grad()
+    def compute_bgdepth(self, poses, H, W):
+        """poses: cameras.CameraSet -> [N_cam,H,W] background depth per pixel (0 = no background), one camera at a time."""
+        dev = poses.device
+        n = poses.num_camera
+        out = torch.zeros(n, H, W, dtype=_f32, device=dev)
+        px = torch.arange(W, device=dev, dtype=_i32)[None, :].expand(H, W)
+        py = torch.arange(H, device=dev, dtype=_i32)[:, None].expand(H, W)
+        for idx in range(n):
+            locs = torch.stack([torch.full_like(px, idx), px, py], -1).reshape(-1, 3).contiguous()
+            o, d = poses.get_rays(locs)
+            o, d = self._rays(o, d)
+            for i in range(0, H * W, CHUNK):
+                b, valid, z = self._bgdepth(o[i:i + CHUNK], d[i:i + CHUNK])
+                no_bg = z <= 0
+                z = torch.where(valid[:, None], z + b[:, 1:], z)
+                out[idx].view(-1)[i:i + CHUNK] = torch.where(no_bg, torch.zeros_like(z), z)[:, 0]
+        return out
+
+    def sample_points(self, rays_o, rays_d, start, num_sample):
+        """fastMesh_kernel.cu:23-122 has no live caller in the reference (its only user, background_sampling_v2, is commented
+        out, fastMesh/__init__.py:88-94); the surface exists, the op does not."""
+        raise NotImplementedError("FastMesh.sample_points is dead code in the reference (no caller); use background_sampling")
+
+
+class fastMesh:
+    """The reference's pybind class (fastMesh/binding.cpp:7-20: build, fisrtHit [sic], firstEnter, getSceneBound, sample_points)
+    on FastMesh, for a checkout that keeps its own fastMesh/__init__.py: `from scanerf_amd.fastmesh import fastMesh` in place of
+    `from .lib.fastMesh import fastMesh`.  depth [B,1] float32 is written in place, as the reference's kernels do."""
+
+    def __init__(self):
+        self.mesh = None
+
+    def build(self, path):
+        self.mesh = FastMesh(path)
+
+    def _depth(self, depth, B):
+        if not isinstance(depth, torch.Tensor) or depth.numel() != B:
+            raise RuntimeError(f"scanerf: depth must be a [B,1] float32 tensor with B={B}")
+        dev_ptr(depth, _f32, "depth")
+        return depth.view(-1)
+
+    def fisrtHit(self, rays_o, rays_d, depth):
+        self.mesh.first_hit(rays_o, rays_d, out=self._depth(depth, rays_o.shape[0]))
+
+    def firstEnter(self, rays_o, rays_d, depth):
+        self.mesh.first_enter(rays_o, rays_d, out=self._depth(depth, rays_o.shape[0]))
+
+    def getSceneBound(self):
+        return self.mesh.get_sceneinfo()
+
+    def sample_points(self, rays_o, rays_d, start, z_vals):
+        self.mesh.sample_points(rays_o, rays_d, start, z_vals.shape[-1])

@@ -149,6 +149,13 @@ class HashGrid(nn.Module):
         return inverse_z_samples(rays_o, rays_d, self.bbox_center, self.bbox_size / 2.0, num_sample, invalid_underground,
                                  floor_y=(self.bbox_center - self.bbox_size / 4.0)[1])
 
+    @torch.no_grad()
+    def background_sampling(self, fmesh, rays_o, rays_d, num_samples):
+        """:296-303: samples between the box exit and the mesh behind it (fastmesh.FastMesh.background_sampling), sample_range =
+        max(bbox_size) / 10; dists = forward differences, 1e-6 last."""
+        from ..tile_model import mesh_background_samples
+        return mesh_background_samples(fmesh, rays_o, rays_d, num_samples, self._converted("bbox_size", "list"))
+
     # ---- compositing in torch (:344-366; used by the op-by-op route) ---------------------------------------------------------
     def cal_integrate_weight(self, sigma, z_vals, dists, rays_d, infinity=True):
         from ..tile_model import composite_weights
@@ -202,7 +209,9 @@ class HashGrid(nn.Module):
     def render_bg_rays(self, rays_o, rays_d, num_sample, decoder, mode, occlusion_mask=None, infinity=True, **kwargs):
         if kwargs["bg_mode"] == "IZ":
             z_vals, dists, valid = self.inverse_z_sampling(rays_o.detach(), rays_d.detach(), num_sample, kwargs["invalid_underground"])
-        else:   # "BS" needs the mesh tracer (fastMesh: out of scope)
+        elif kwargs["bg_mode"] == "BS" and kwargs.get("fmesh") is not None:
+            z_vals, dists, valid = self.background_sampling(kwargs["fmesh"], rays_o.detach(), rays_d.detach(), num_sample)
+        else:   # "BS" without a mesh tracer (fastmesh.FastMesh, passed as fmesh=): nothing to sample with
             return None, False
         if occlusion_mask is not None:
             valid = valid & occlusion_mask[..., 0]

@@ -27,6 +27,18 @@ def camera_inside(cam_center, bbox_center, box_size):
 
 
 @torch.no_grad()
+def mesh_occlusion_masks(fmesh, get_rays, H, W, n_cam, trust_mesh=False):
+    """tile.py:233-241: the occlusion mask of every training camera of a tile from the scene mesh, at tile construction.
+    fmesh: fastmesh.FastMesh with set(bbox_center, bbox_size) done; get_rays(view) -> rays_o, rays_d [H*W,3] in pixel order.
+    -> [n_cam,H,W,1] bool on the mesh's device, True = the tile is visible through the pixel (FastMesh.render_mask)."""
+    masks = torch.empty(n_cam, H, W, 1, dtype=torch.bool, device=fmesh.device)
+    for i in range(n_cam):
+        rays_o, rays_d = get_rays(i)
+        masks[i] = fmesh.render_mask(rays_o.reshape(-1, 3), rays_d.reshape(-1, 3), trust_mesh=trust_mesh).reshape(H, W, 1)
+    return masks
+
+
+@torch.no_grad()
 def render_depth_rays(model, rays_o, rays_d, S_fg, S_bg, global_step, batch_size=2 ** 16):
     """tile.py:714-722 on the fused kernels: merged fg + T_left * bg depth per ray, zeros where nothing renders."""
     depth = torch.zeros_like(rays_o[..., :1])

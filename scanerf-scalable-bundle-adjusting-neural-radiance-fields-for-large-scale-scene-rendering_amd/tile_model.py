@@ -72,6 +72,26 @@ def inverse_z_samples(rays_o, rays_d, box_center, box_half, num_sample, invalid_
     return z, d, valid
 
 
+@torch.no_grad()
+def mesh_background_samples(fmesh, rays_o, rays_d, num_sample, bbox_size):
+    """Background samples of BG_MODE "BS" (hashgrid/__init__.py:296-303): fmesh.background_sampling (fastmesh.FastMesh: between
+    the ray's exit from the box fmesh.set() was given and the mesh behind it) with sample_range = max(bbox_size) / 10, bbox_size the
+    HashGrid's (2x) box as host floats; dists = forward differences with 1e-6 last; valid = the ray has a background."""
+    z, valid = fmesh.background_sampling(rays_o, rays_d, num_sample, max(bbox_size) / 10)
+    d = torch.cat([z[:, 1:] - z[:, :-1], torch.full((z.shape[0], 1), 1e-6, device=z.device)], -1).contiguous()
+    return z, d, valid
+
+
+def _bg_samples(model, rays_o, rays_d, S_bg, invalid_underground, bg_mode, fmesh):
+    if bg_mode == "IZ":
+        return model.inverse_z_sampling(rays_o, rays_d, S_bg, invalid_underground)
+    if bg_mode != "BS":
+        raise ValueError(f"scanerf: bg_mode must be 'IZ' or 'BS', got {bg_mode!r}")
+    if fmesh is None:
+        raise ValueError("scanerf: bg_mode='BS' needs fmesh (fastmesh.FastMesh)")
+    return mesh_background_samples(fmesh, rays_o, rays_d, S_bg, model.bbox_size.tolist())
+
+
 class Decoder(nn.Module):
     """sigma / diffuse / tint / SH-conditioned specular decoder of the reference's ShallowMLP (network.py:151-190).
     The parameters ARE the render-time blob (rendering.py:101-112: per layer [bias, W^T]), one flat tensor: the fused
@@ -266,11 +286,14 @@ class TileModel(nn.Module):
                                  floor_y=(self._center_dev - self._size_dev / 4.0)[1])
 
     @torch.no_grad()
-    def render_rays_fused(self, rays_o, rays_d, S_fg, S_bg, global_step, invalid_underground=False, occlusion_mask=None):
+    def render_rays_fused(self, rays_o, rays_d, S_fg, S_bg, global_step, invalid_underground=False, occlusion_mask=None,
+                          bg_mode="IZ", fmesh=None):
         """tile.py:639-692 on the fused kernels: foreground (occupancy-sampled, contract_fore) and
         background (inverse-z, contract_bg, infinity) renders, merged with the foreground's T_left.
         occlusion_mask [B,1] bool (tile.py:655,661): both branches' valid sets are ANDed with it
-        (hashgrid/__init__.py:420-421,479-480); a masked ray renders as zeros with T_left = 1, as every invalid ray."""
+        (hashgrid/__init__.py:420-421,479-480); a masked ray renders as zeros with T_left = 1, as every invalid ray.
+        bg_mode "BS" with fmesh (fastmesh.FastMesh): the background is sampled between the box exit and the mesh behind it
+        (mesh_background_samples) instead of in inverse depth; nothing else changes."""
         self.packed.pack(self.decoder.blob(), network.weight_feature(global_step, self.device), (network.skip_levels(global_step) if LEVEL_SKIP else 0))
         table = self.gather_table()
         box = (self.min_bbox.tolist(), self.bbox_size.tolist())
@@ -280,7 +303,7 @@ class TileModel(nn.Module):
             vf = vf & occlusion_mask[..., 0]
         fg, wfg = render.render_forward(rays_o, rays_d, z, dist, table, self.resolution, self.packed, *box, render.FORE,
                                         False, ray_valid=vf)
-        zb, db, vb = self.inverse_z_sampling(rays_o, rays_d, S_bg, invalid_underground)
+        zb, db, vb = _bg_samples(self, rays_o, rays_d, S_bg, invalid_underground, bg_mode, fmesh)
         if occlusion_mask is not None:
             vb = vb & occlusion_mask[..., 0]
         bg, wbg = render.render_forward(rays_o, rays_d, zb, db, table, self.resolution, self.packed, *box, render.BG,
@@ -669,7 +692,7 @@ def _visibility_render_fgbg(model, rays_o, rays_d, S_fg, S_bg, global_step, inva
 
 
 def _fgbg_pass(model, rays_o, rays_d, target, S_fg, S_bg, global_step, invalid_underground, timer, pose_grads, warp, routes,
-               compact, mono=None, locs=None):
+               compact, mono=None, locs=None, bg_mode="IZ", fmesh=None, occlusion_mask=None):
     """Both branches of a tile's render on `routes` (table_grad_route): forward, the merged loss (+ the warp, then the monocular
     terms), backward
     -> (loss [1], (fg, bg) _Branch, grad_blob, gradient table or None, (g_o, g_d) or None).  On the records + adam2 route the
@@ -687,7 +710,10 @@ def _fgbg_pass(model, rays_o, rays_d, target, S_fg, S_bg, global_step, invalid_u
         with _sec(timer if fused else None, "sample_points_grid", B * (24 + 2 * 4 * S_fg)):
             z, dist = model.sample(rays_o, rays_d, S_fg)
         vf = render.ray_valid(z) if fused else torch.all(z != -1, dim=-1)
-        zb, db, vb = model.inverse_z_sampling(rays_o, rays_d, S_bg, invalid_underground)
+        zb, db, vb = _bg_samples(model, rays_o, rays_d, S_bg, invalid_underground, bg_mode, fmesh)
+        if occlusion_mask is not None:   # as render_rays_fused: both branches' valid sets
+            vf &= occlusion_mask[..., 0].to(vf.dtype)   # (in place: render.ray_valid's flags keep their padded buffer)
+            vb = vb & occlusion_mask[..., 0]
         ws_bg = None
         if fused:   # the background branch's own record workspace (both plans live until the one accumulate)
             need_bg = render.lib().scanerf_render_scatter_workspace_bytes(B, S_bg, T)
@@ -729,24 +755,26 @@ def _fgbg_pass(model, rays_o, rays_d, target, S_fg, S_bg, global_step, invalid_u
 
 
 def fgbg_gradients(model, rays_o, rays_d, target, S_fg, S_bg, global_step, invalid_underground=False, timer=None,
-                   pose_grads=False, warp=None, mono=None, locs=None):
+                   pose_grads=False, warp=None, mono=None, locs=None, bg_mode="IZ", fmesh=None, occlusion_mask=None):
     """Loss and parameter gradients of the complete per-tile render of tile.py:639-692 / :880-1015: foreground
     (occupancy-sampled, contract_fore) + T_left * background (inverse-z, contract_bg, infinity), MSE on the merged colour
     over all rays + 0.01 * (l2_reg_specular of both branches) -- two fused forward/backward pairs over the same table and
     decoder, each branch's table gradient into ONE gradient table.  Returns (loss, grad_table [16,T,2], grad_blob [13994])
     (+ dL/d(rays_o), dL/d(rays_d) with pose_grads: t16 backward on the fp32 table, any table size).
     warp: as in train_step_fused, on the merged prediction (warp.WarpLoss.fgbg_term).
-    mono, locs: as in train_step_fused, on the merged depth d_fg + T_left d_bg (mono.MonoLoss.fgbg_term)."""
+    mono, locs: as in train_step_fused, on the merged depth d_fg + T_left d_bg (mono.MonoLoss.fgbg_term).
+    bg_mode, fmesh, occlusion_mask: as in train_step_fgbg."""
     _check_mono(mono, locs)
     routes, compact = table_grad_route(FGBG_GRADIENTS, model.features.shape[1], rays_o.shape[0], [S_fg, S_bg],
                                        render.backward_arith())
     loss, _, gblob, gtab, g = _fgbg_pass(model, rays_o, rays_d, target, S_fg, S_bg, global_step, invalid_underground, timer,
-                                         pose_grads, warp, routes, compact, mono, locs)
+                                         pose_grads, warp, routes, compact, mono, locs, bg_mode, fmesh, occlusion_mask)
     return (loss[0].detach(), gtab, gblob, *g) if pose_grads else (loss[0].detach(), gtab, gblob)
 
 
 def train_step_fgbg(model, dec_opt, rays_o, rays_d, target, S_fg, S_bg, global_step, table_lr=1e-2,
-                    invalid_underground=False, timer=None, pose_grads=False, dec_step=True, warp=None, mono=None, locs=None):
+                    invalid_underground=False, timer=None, pose_grads=False, dec_step=True, warp=None, mono=None, locs=None,
+                    bg_mode="IZ", fmesh=None, occlusion_mask=None):
     """One complete training iteration of a tile (tile.py:880-1015: foreground + T_left * background, tile.py:639-692) on the
     fused kernels: both branches' forward, ONE loss launch pair for the merged prediction, both branches' backward emitting
     their scatter records, and ONE accumulate + sparse Adam over both record sets (the two gradients meet in one Adam step).
@@ -757,14 +785,18 @@ def train_step_fgbg(model, dec_opt, rays_o, rays_d, target, S_fg, S_bg, global_s
     (-> (loss, g_o, g_d)); dec_step=False: the caller steps the decoder's optimiser (it holds the camera parameters too).
     warp (warp.WarpLoss, default None): the multi-view warp term on the merged prediction, chained to both branches before their
     backward (see train_step_fused).
-    mono (mono.MonoLoss, default None) with locs [B,3] int32: the monocular terms on the merged depth, after the warp term."""
+    mono (mono.MonoLoss, default None) with locs [B,3] int32: the monocular terms on the merged depth, after the warp term.
+    bg_mode "BS" with fmesh (fastmesh.FastMesh): the background branch samples between the box exit and the mesh behind it
+    (BG_MODE "BS", hashgrid/__init__.py:296-303) instead of in inverse depth; nothing else changes.  occlusion_mask [B,1] bool:
+    ANDed into both branches' valid sets, as in render_rays_fused.  With the defaults the step is what it was without them."""
     _check_mono(mono, locs)
     routes, compact = table_grad_route(FGBG_STEP, model.features.shape[1], rays_o.shape[0], [S_fg, S_bg],
                                        render.backward_arith(), model._half_table is not None)
     if pose_grads and model.gather_table().dtype != torch.float32:
         raise RuntimeError("scanerf: train_step_fgbg(pose_grads=True) gathers from the fp32 table")
     loss, branches, gblob, gtab, g = _fgbg_pass(model, rays_o, rays_d, target, S_fg, S_bg, global_step, invalid_underground,
-                                                timer, pose_grads, warp, routes, compact, mono, locs)
+                                                timer, pose_grads, warp, routes, compact, mono, locs, bg_mode, fmesh,
+                                                occlusion_mask)
     with torch.no_grad():
         if routes[0] in _TABLE_ROUTES:
             model.features.grad = gtab

@@ -166,15 +166,22 @@ class TileTrainer:
     def __init__(self, model, get_batch, total_step=40000, eta_hash=1e-2, eta_decoder=1e-3, grid_log2dim=(4, 5, 6, 7, 8, 9),
                  pruning_th=(0.1, 0.2, 0.3, 0.4), adjust_step=2000, dynamic_start=None, dynamic_end=None, dynamic_step=None,
                  num_sample=128, num_bg_sample=0, finest_resolution=2048, consensus=None, cameras=None, eta_cam=1e-3,
-                 cam_start_step=0, admm=False, warp=None, mono=None):
+                 cam_start_step=0, admm=False, warp=None, mono=None, fmesh=None, bg_mode="IZ", occlusions=None):
         """cameras (cameras.CameraSet): pose refinement on -- get_batch(step) then returns (locs [B,3] int32 (view, px, py),
         target [B,3]) and the rays are generated from the current poses; se3_refine is the optimiser's second parameter
         group with its own schedule (tile.py:316-323).  admm: add the consensus penalty (consensus.py:70-76) to the
         pose gradient.  warp (warp.WarpLoss): the multi-view warp term is added to every iteration (criterions.py:92-97); with
         cameras, its gradient w.r.t. the neighbour cameras' rts is fed to se3_refine as well.  None (default): no warp term.
         mono (mono.MonoLoss): the monocular depth / smoothness terms are added after the warp term (criterions.py:99-105), at
-        the batch's locs; with cameras they reach the poses through the ray gradients.  None (default): no monocular term."""
+        the batch's locs; with cameras they reach the poses through the ray gradients.  None (default): no monocular term.
+        fmesh (fastmesh.FastMesh, one per process: admm.py) with bg_mode "BS": the background branch (num_bg_sample > 0) samples
+        between the tile box and the scene mesh behind it (cfg BG_MODE, tile.py:661).  occlusions [N_cam,H,W,1] bool
+        (occlusion.mesh_occlusion_masks, tile.py:233-251): each batch's rows are gathered at its locs (the cameras' batches, or the
+        4th element of get_batch's tuple) and passed as occlusion_mask.  Defaults: the iteration is what it was without them."""
         self.model, self.get_batch = model, get_batch
+        self.fmesh, self.bg_mode, self.occlusions = fmesh, bg_mode, occlusions
+        if bg_mode == "BS" and fmesh is None:
+            raise ValueError("TileTrainer(bg_mode='BS') needs fmesh (fastmesh.FastMesh)")
         self.warp, self.mono = warp, mono
         self.cameras, self.admm = cameras, admm
         groups = [{"params": model.decoder.parameters(), "lr": eta_decoder, "weight_decay": 1e-6}]
@@ -214,7 +221,7 @@ class TileTrainer:
         if self.num_bg_sample > 0:   # the complete iteration (foreground + T_left * background), tile.py:639-692
             loss, g_o, g_d = train_step_fgbg(self.model, self.dec_opt, rays_o.detach(), rays_d.detach(), target, self.num_sample,
                                              self.num_bg_sample, self.global_step, table_lr=self.table_lr, pose_grads=True,
-                                             dec_step=False, **self._warp_kw(locs))
+                                             dec_step=False, **self._warp_kw(locs), **self._mesh_kw(locs))
         else:
             loss, g_o, g_d = train_step_fused(self.model, self.dec_opt, rays_o.detach(), rays_d.detach(), target, self.num_sample,
                                               self.global_step, table_lr=self.table_lr, pose_grads=True, dec_step=False,
@@ -234,6 +241,20 @@ class TileTrainer:
             kw.update(mono=self.mono, locs=locs)
         return kw
 
+    def _mesh_kw(self, locs=None):
+        """The mesh's share of a foreground + background iteration: the "BS" sampler and the batch's occlusion-mask rows."""
+        kw = {}
+        if self.bg_mode != "IZ":
+            # the tracer is shared by the rank's tiles: point it at THIS tile's box (tile.py:149-150), no copy, no synchronisation
+            self.fmesh.set(self.model._center_dev, self.model._half_dev)
+            kw.update(bg_mode=self.bg_mode, fmesh=self.fmesh)
+        if self.occlusions is not None:
+            if locs is None:
+                raise ValueError("TileTrainer(occlusions=...): get_batch must return (rays_o, rays_d, target, locs)")
+            v, px, py = locs.long().unbind(-1)
+            kw["occlusion_mask"] = self.occlusions[v, py, px]
+        return kw
+
     def train_one_step(self):
         if self.cameras is not None:
             loss = self._train_one_step_poses()
@@ -249,9 +270,11 @@ class TileTrainer:
             if len(batch) != 4:
                 raise ValueError("TileTrainer(mono=...): get_batch must return (rays_o, rays_d, target, locs)")
             locs = batch[3]
+        elif self.occlusions is not None and len(batch) == 4:
+            locs = batch[3]
         if self.num_bg_sample > 0:
             loss = train_step_fgbg(self.model, self.dec_opt, rays_o, rays_d, target, self.num_sample, self.num_bg_sample,
-                                   self.global_step, table_lr=self.table_lr, **self._warp_kw(locs))
+                                   self.global_step, table_lr=self.table_lr, **self._warp_kw(locs), **self._mesh_kw(locs))
         else:
             loss = train_step_fused(self.model, self.dec_opt, rays_o, rays_d, target, self.num_sample, self.global_step,
                                     table_lr=self.table_lr, **self._warp_kw(locs))

@@ -1,0 +1,138 @@
+"""CPU checks around the mesh tracer (scanerf_amd.fastmesh, csrc/mesh.hip): the float64 yardstick the GPU tests compare the
+kernels with (tests/fastmesh_reference.py) is consistent with itself, the divergence from the reference's first-hit rule is a
+fact of the fixture, and the new surface validates and refuses without a GPU."""
+import numpy as np
+import pytest
+import torch
+
+import fastmesh_reference as FR
+
+
+@pytest.fixture(scope="module")
+def terrain():
+    V, F, rays = FR.terrain_fixture()
+    return V, F, rays, FR.build_grid(V, F, 6)
+
+
+def _differs(a, b):
+    return np.abs(a - b) > 1e-9 * np.maximum(np.abs(b), 1.0)
+
+
+def test_fixture_is_the_one_the_numbers_were_measured_on(terrain):
+    V, F, rays, g = terrain
+    assert V.shape == (2497, 3) and F.shape == (4752, 3)
+    assert len(g["cells"]) == 10484 and len(g["cell_faces"]) == 45034
+    assert [len(rays[k][0]) for k in ("inside", "outside", "axial")] == [4096, 2048, 512]
+    assert int(g["rank"][-1]) + bin(int(g["bitmask"][-1])).count("1") == 10484
+    t64, grazing = FR.nearest_hit(*rays["inside"], V, F)
+    assert 0.4 < (t64 > 0).mean() < 0.6            # "about half hit"
+    assert grazing.mean() <= 0.01
+    o, d = rays["axial"]
+    assert np.all((d == 0).sum(1) == 2)
+
+
+@pytest.mark.parametrize("name", ["inside", "outside", "axial"])
+def test_carried_candidate_equals_brute_force_and_early_return_does_not(terrain, name):
+    """The float64 DDA walk with the candidate carried across cells equals the brute-force nearest hit on every ray; the
+    reference's rule (return at the first cell with any hit, fastMesh_kernel.cu:284-290) does not, on the two general ray sets."""
+    V, F, rays, g = terrain
+    o, d = rays[name]
+    t64, _ = FR.nearest_hit(o, d, V, F)
+    carried, early, _ = FR.walk(o, d, V, F, g)
+    assert not _differs(carried, t64).any()
+    wrong = _differs(early, t64)
+    if name != "axial":
+        assert wrong.sum() >= 1
+        assert np.all(early[wrong] > t64[wrong])    # never nearer than the truth: it reports a surface BEHIND the nearest one
+
+
+def test_early_return_misses_the_box_over_the_sloping_plane():
+    V, F, (o, d), top = FR.sloping_plane_fixture()
+    g = FR.build_grid(V, F, 6)
+    assert len(g["cells"]) > 64 ** 3 // 4           # the two triangles' box is the whole cube: registered far from their surface
+    t64, grazing = FR.nearest_hit(o, d, V, F)
+    assert not grazing.any() and np.allclose(o[:, 2] + t64 * d[:, 2], top)   # every ray's nearest hit is the box's top
+    carried, early, _ = FR.walk(o, d, V, F, g)
+    assert not _differs(carried, t64).any()
+    assert _differs(early, t64).mean() > 0.5
+
+
+def test_first_enter_definition_agrees_with_a_walk_in_cell_order(terrain):
+    """first_enter's definition orders the cells by slab entry, without a DDA; a float64 DDA that takes the first occupied cell in
+    walk order whose box the ray hits gives the same answer on every ray."""
+    V, F, rays, g = terrain
+    for name in ("inside", "outside", "axial"):
+        o, d = rays[name]
+        fe = FR.first_enter(o, d, V, F, 6, g)
+        _, _, walked = FR.walk(o, d, V, F, g)
+        assert not _differs(walked, fe).any(), name
+        assert (fe > 0).mean() > 0.4
+
+
+def test_entry_points_validate_without_a_gpu():
+    import scanerf_amd  # noqa
+    from scanerf_amd import _capi
+    lib = _capi.lib()
+    n = None
+    hit = lambda B, L=6, lds=0: lib.scanerf_mesh_first_hit(n, n, B, n, n, n, n, n, n, n, n, L, lds, n, n)
+    enter = lambda B, L=6, lds=0: lib.scanerf_mesh_first_enter(n, n, B, n, n, n, n, n, L, lds, n, n)
+    assert hit(0) == 0 and enter(0) == 0                                   # empty batch: a no-op
+    assert hit(16) != 0 and b"null" in lib.scanerf_last_error()
+    assert enter(16) != 0 and b"null" in lib.scanerf_last_error()
+    assert hit(16, 3) != 0 and b"log2dim=3" in lib.scanerf_last_error()
+    assert enter(16, 8) != 0 and b"log2dim=8" in lib.scanerf_last_error()
+    assert lib.scanerf_mesh_count_cells(n, n, 8, 0, 6, n, n, n) != 0 and b"F=0" in lib.scanerf_last_error()
+    assert lib.scanerf_mesh_count_cells(n, n, 8, 4, 6, n, n, n) != 0 and b"null" in lib.scanerf_last_error()
+    assert lib.scanerf_mesh_count_cells(n, n, 8, 4, 9, n, n, n) != 0 and b"log2dim=9" in lib.scanerf_last_error()
+    assert lib.scanerf_mesh_emit_keys(n, n, 8, 4, 6, n, n, n, 10, n) != 0 and b"null" in lib.scanerf_last_error()
+    assert lib.scanerf_mesh_cell_boxes(n, n, n, n, 0, n, n) == 0
+    assert lib.scanerf_mesh_cell_boxes(n, n, n, n, 5, n, n) != 0 and b"null" in lib.scanerf_last_error()
+    assert lib.scanerf_mesh_gather_triangles(n, n, n, 0, n, n) == 0
+    assert lib.scanerf_mesh_gather_triangles(n, n, n, 5, n, n) != 0 and b"null" in lib.scanerf_last_error()
+    assert lib.scanerf_abi_version() == 9                                   # additions only
+
+
+def test_fastmesh_refuses_cpu_tensors_and_dead_ops():
+    import scanerf_amd  # noqa
+    from scanerf_amd.fastmesh import FastMesh
+    V, F, _, _ = FR.sloping_plane_fixture()
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        FastMesh.from_arrays(V, F, "cpu")
+    fm = FastMesh.__new__(FastMesh)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        fm.first_hit(torch.zeros(4, 3), torch.ones(4, 3))
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        fm.render_mask(torch.zeros(4, 3), torch.ones(4, 3))
+    with pytest.raises(NotImplementedError, match="dead code"):
+        fm.sample_points(None, None, None, 8)
+    for name in ("set", "get_sceneinfo", "render_depth", "render_mask", "compute_bgdepth_batch", "background_sampling",
+                 "compute_bgdepth", "sample_points", "from_arrays"):   # fastMesh/__init__.py:9-133
+        assert callable(getattr(FastMesh, name)), name
+
+
+def test_bs_without_a_tracer_still_renders_nothing():
+    """render_bg_rays(bg_mode="BS") without fmesh keeps returning (None, False); the training steps refuse the combination."""
+    import scanerf_amd  # noqa
+    from scanerf_amd import tile_model
+    from scanerf_amd.hashgrid.grid import HashGrid
+    hg = HashGrid.__new__(HashGrid)
+    o = torch.zeros(4, 3)
+    assert hg.render_bg_rays(o, o, 8, None, 0, bg_mode="BS", global_step=0, invalid_underground=False) == (None, False)
+    assert hg.render_bg_rays(o, o, 8, None, 0, bg_mode="BS", fmesh=None, global_step=0, invalid_underground=False) == (None, False)
+    with pytest.raises(ValueError, match="needs fmesh"):
+        tile_model._bg_samples(None, o, o, 8, False, "BS", None)
+    with pytest.raises(ValueError, match="bg_mode"):
+        tile_model._bg_samples(None, o, o, 8, False, "XX", None)
+
+
+def test_trainer_arguments():
+    import scanerf_amd  # noqa
+    from scanerf_amd import trainer
+    import inspect
+    sig = inspect.signature(trainer.TileTrainer.__init__).parameters
+    assert sig["fmesh"].default is None and sig["bg_mode"].default == "IZ" and sig["occlusions"].default is None
+    for fn in (scanerf_amd.tile_model.train_step_fgbg, scanerf_amd.tile_model.fgbg_gradients):
+        p = inspect.signature(fn).parameters
+        assert p["bg_mode"].default == "IZ" and p["fmesh"].default is None and p["occlusion_mask"].default is None
+    p = inspect.signature(scanerf_amd.tile_model.TileModel.render_rays_fused).parameters
+    assert p["bg_mode"].default == "IZ" and p["fmesh"].default is None
