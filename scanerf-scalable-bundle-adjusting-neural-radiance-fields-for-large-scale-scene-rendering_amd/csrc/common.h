@@ -80,6 +80,18 @@ inline int tune_int(const char *, int dflt) { return dflt; }
 inline bool tune_set(const char *) { return false; }
 #endif
 
+// Launch of a kernel that needs more dynamic LDS than the 64 KB a kernel gets unasked: reserve it, then launch.  `op` names the
+// operation in the error text.  Returns 0 or SCANERF_REQUIRE's code; the launch itself is checked by the caller (check_launch).
+template <typename... Params, typename... Args>
+inline int launch_with_lds(void (*kernel)(Params...), int blocks, int threads, size_t lds_bytes, hipStream_t st, const char *op,
+                           const Args &...args)
+{
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    SCANERF_REQUIRE(e == hipSuccess, "%s: cannot reserve %zu B of LDS: %s", op, lds_bytes, hipGetErrorString(e));
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds_bytes, st, args...);
+    return 0;
+}
+
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 // Grid for memory-bound 1-thread-per-item kernels: enough blocks to fill 256 CUs several

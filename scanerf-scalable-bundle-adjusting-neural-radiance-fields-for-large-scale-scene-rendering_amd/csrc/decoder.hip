@@ -15,13 +15,15 @@
 //             8 waves = two per SIMD, weight-gradient blocks owned by waves and summed over the 8 waves' tiles through LDS
 //             staging, the workgroup's power-of-two gradient scale) with the compositing adjoint replaced by the incoming
 //             per-sample gradients and the record emission by a plain [N,32] store; optionally dL/d(view direction) through
-//             the degree-3 harmonics and the normalisation.
+//             the degree-3 harmonics and the normalisation.  What the two kernels do alike is in render_bwd_t16_device.h
+//             (its head lists what is still written out in both); the partial rows are summed by render_bwd.hip's k_reduce_dw.
 // Inputs and outputs are addressed by (pointer, row stride in floats), so the concatenated x [N,35] and its gradient are
 // read / written in place (no slicing copies).
 #include <stdlib.h>
 
+#include "render_bwd_common.h"
+#include "render_bwd_t16_device.h"
 #include "render_h3.h"
-#include "render_t16.h"
 
 using namespace scanerf;
 
@@ -156,83 +158,6 @@ struct BL {   // LDS carve (the t16s images of render_common.h S16_*)
     static_assert(kStage % 16 == 0, "LDS carve alignment");
 };
 
-__device__ __forceinline__ int fresh(int v)
-{
-    asm volatile("" : "+v"(v));
-    return v;
-}
-__device__ __forceinline__ T16Lane fresh_lane(const T16Lane &L)
-{
-    T16Lane r;
-    r.lo16 = fresh(L.lo16);
-    r.w1 = fresh(L.w1);
-    r.r1 = fresh(L.r1);
-    r.r2 = fresh(L.r2);
-    r.pos8 = fresh(L.pos8);
-    r.trp = fresh(L.trp);
-    return r;
-}
-template <int N>
-__device__ __forceinline__ void zero4(v4f (&v)[N])
-{
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = v4f{ 0, 0, 0, 0 };
-}
-__device__ __forceinline__ t16_h4 lo4(const t16_h8 &v) { return __builtin_shufflevector(v, v, 0, 1, 2, 3); }
-
-// Weight-gradient blocks owned by this wave (render_bwd_t16.hip wgrad, SPLIT form): acc[i] += sum over the 4 tile pairs of
-// dY[yb] X[xb0 + i]^T, both operands hi + lo, read back transposed from the pairs' staging images.
-template <int NX, bool ROWSUM, int XSTRIDE = 1>
-__device__ __forceinline__ void wgrad(v4f *acc, float &rowsum, const char *stage, const T16Lane &L, int yb, int x_mat_off, int xb0)
-{
-    constexpr int kWave = 2 * T16_STAGE_WAVE, kLo = 2 * T16_STAGE_MAT;
-#pragma unroll
-    for (int P = 0; P < 4; ++P) {
-        const char *pm = stage + P * 2 * kWave;
-        const t16_h8 a = t16_stage_get(pm, L, yb);
-        t16_h8 b[NX];
-#pragma unroll
-        for (int i = 0; i < NX; ++i) b[i] = t16_stage_get(pm + x_mat_off, L, xb0 + i * XSTRIDE);
-        if (ROWSUM) rowsum = t16_sum8(a, rowsum);
-        const t16_h8 alo = t16_stage_get(pm + kLo, L, yb);
-        if (ROWSUM) rowsum = t16_sum8(alo, rowsum);
-#pragma unroll
-        for (int i = 0; i < NX; ++i) {
-            const t16_h8 blo = t16_stage_get(pm + x_mat_off + kLo, L, xb0 + i * XSTRIDE);
-            acc[i] = t16_mfma(alo, b[i], acc[i]);
-            acc[i] = t16_mfma(a, blo, acc[i]);
-            acc[i] = t16_mfma(a, b[i], acc[i]);
-        }
-        __builtin_amdgcn_sched_barrier(0);   // (bounds the operands in flight)
-    }
-}
-__device__ __forceinline__ void stage_put2(char *mat, const T16Lane &L, int b, const T16HL &v)
-{
-    t16_stage_put(mat, L, b, __builtin_shufflevector(v.hi, v.hi, 0, 1, 2, 3));
-    t16_stage_put(mat, L, b + 1, __builtin_shufflevector(v.hi, v.hi, 4, 5, 6, 7));
-    t16_stage_put(mat + 2 * T16_STAGE_MAT, L, b, __builtin_shufflevector(v.lo, v.lo, 0, 1, 2, 3));
-    t16_stage_put(mat + 2 * T16_STAGE_MAT, L, b + 1, __builtin_shufflevector(v.lo, v.lo, 4, 5, 6, 7));
-}
-__device__ __forceinline__ v4f gauss_deriv(const v4f &u)   // G'(u) = -100 u G(u)
-{
-    v4f d;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) d[g] = -100.0f * u[g] * gauss_fast(u[g]);
-    return d;
-}
-__device__ __forceinline__ void stage_act(char *stX, const T16Lane &L, const v4f u[4])
-{
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        v4f a0, a1;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            a0[g] = gauss_fast(u[2 * t][g]);
-            a1[g] = gauss_fast(u[2 * t + 1][g]);
-        }
-        stage_put2(stX, L, 2 * t, t16_split(a0, a1));
-    }
-}
 // the SH k-step (input k-step 1 of the D0 pairs) walked transposed: dSH = W_D0[:, 32:48]^T dv0.  Input blocks 2 and 3 of
 // s16_chain's numbering: rows m of block 2 = SH[m] (m < 4), SH[8 + m - 4] (4 <= m < 8); of block 3 = SH[4 + m], SH[12 + m - 4];
 // rows 8..15 meet zero weights.  So lane group q = 0 ends up with SH[0..3] / SH[4..7], q = 1 with SH[8..11] / SH[12..15].
@@ -470,51 +395,37 @@ __global__ void __launch_bounds__(kThreads, 2) k_decoder_bwd_s16(DecArgs a)
             stage_act(stX, L, kv1);                              // X operand of the rgb layer's weight gradient: c1 = G(v1)
         }
         __syncthreads();  // ---- A1
-        if (wv == 0) wgrad<1, true>(gW_nar, gB_nar, stage, L, 0, 0, 2);
-        else if (wv == 1) { float dummy = 0.0f; wgrad<1, false>(gW_nar, dummy, stage, L, 0, 0, 3); }
-        else if (wv < 6) { float dummy = 0.0f; wgrad<1, false>(gW_nar, dummy, stage, L, 0, T16_STAGE_MAT, wv - 2); }
+        if (wv == 0) wgrad<1, true, 1, true>(gW_nar, gB_nar, stage, L, 0, 0, 2);
+        else if (wv == 1) { float dummy = 0.0f; wgrad<1, false, 1, true>(gW_nar, dummy, stage, L, 0, 0, 3); }
+        else if (wv < 6) { float dummy = 0.0f; wgrad<1, false, 1, true>(gW_nar, dummy, stage, L, 0, T16_STAGE_MAT, wv - 2); }
         T16HL dyS[2];
         {   // dv1 = (W_rgb^T gs3) * G'(v1)
             v4f dc[4];
-            zero4(dc);
-            s16_chain_narrow<4>(dc, lds, S16T_D2, L.lo16, narS);
-#pragma unroll
-            for (int b = 0; b < 4; ++b) dc[b] *= gauss_deriv(kv1[b]);
+            chain_narrow_rgb(dc, lds, L, narS, kv1);
             dyS[0] = t16_split(dc[0], dc[1]);
             dyS[1] = t16_split(dc[2], dc[3]);
         }
         __syncthreads();  // ---- B1
         // ================= Directional_MLP.mlp.2 (64 -> 64) =================
         L = fresh_lane(L);
-        stage_put2(stY, L, 0, dyS[0]);
-        stage_put2(stY, L, 2, dyS[1]);
+        stage_dy(stY, L, dyS);
         stage_act(stX, L, kv0);
         __syncthreads();  // ---- A2
-        if (cb == 0) wgrad<2, true>(gW_D1, gB_D1, stage, L, rb, T16_STAGE_MAT, 0);
-        else { float dummy = 0.0f; wgrad<2, false>(gW_D1, dummy, stage, L, rb, T16_STAGE_MAT, 2); }
+        wgrad_layer<2>(gW_D1, gB_D1, stage, L, rb, cb);
         {
             v4f dc[4];
-            zero4(dc);
-            s16_chain<4, 2, 2>(dc, lds, T16_D1, L.trp, dyS);
-#pragma unroll
-            for (int b = 0; b < 4; ++b) dc[b] *= gauss_deriv(kv0[b]);   // dv0
+            chain_gauss(dc, lds, T16_D1, L.trp, dyS, kv0);   // dv0
             dyS[0] = t16_split(dc[0], dc[1]);
             dyS[1] = t16_split(dc[2], dc[3]);
         }
         __syncthreads();  // ---- B2
         // ================= Directional_MLP.mlp.0 (H[32:64] and the 16 harmonics of the sample's direction) =================
         L = fresh_lane(L);
-        stage_put2(stY, L, 0, dyS[0]);
-        stage_put2(stY, L, 2, dyS[1]);
+        stage_dy(stY, L, dyS);
         stage_put2(stX, L, 0, t16_split(khh[2], khh[3]));
-        {   // the SH part of the layer's input: 16 more "units" (block 2 of X), this sample's own
-            const T16HL shS = t16_split(shmine, zero);
-            t16_stage_put(stX, L, 2, lo4(shS.hi));
-            t16_stage_put(stX + kLo, L, 2, lo4(shS.lo));
-        }
+        stage_sh(stX, L, shmine);   // this sample's own
         __syncthreads();  // ---- A3
-        if (cb == 0) wgrad<2, true, 2>(gW_D0, gB_D0, stage, L, rb, T16_STAGE_MAT, 0);   // x = H[32:48] and SH
-        else { float dummy = 0.0f; wgrad<1, false>(gW_D0, dummy, stage, L, rb, T16_STAGE_MAT, 1); }   // x = H[48:64]
+        wgrad_dir0(gW_D0, gB_D0, stage, L, rb, cb);
         if (DIRGRAD) {
             // dL/dSH = W_D0[:, 32:48]^T dv0 -> through the harmonics and the normalisation -> dL/d(direction) of this sample
             v4f dsh[2];
@@ -559,17 +470,14 @@ __global__ void __launch_bounds__(kThreads, 2) k_decoder_bwd_s16(DecArgs a)
         }
         {
             v4f dH[4];
-            zero4(dH);
-            s16_chain<2, 2, 2>(&dH[2], lds, T16_D0, L.trp, dyS);        // dH[32:64] = W_D0[:, :32]^T dv0
-            s16_chain_narrow<2>(&dH[0], lds, S16T_HEAD, L.lo16, narS);  // dH[0:32] = heads^T gh
+            chain_dH(dH, lds, L.trp, L.lo16, dyS, narS);
             dyS[0] = t16_split(dH[0], dH[1]);
             dyS[1] = t16_split(dH[2], dH[3]);
         }
         __syncthreads();  // ---- B3
         // ================= Spatial_MLP.mlp.2 (64 -> 64, linear) =================
         L = fresh_lane(L);
-        stage_put2(stY, L, 0, dyS[0]);
-        stage_put2(stY, L, 2, dyS[1]);
+        stage_dy(stY, L, dyS);
         {   // u0 = W0 x + b0 again
             const T16HL xB = t16_split(xa, xb);
 #pragma unroll
@@ -578,26 +486,20 @@ __global__ void __launch_bounds__(kThreads, 2) k_decoder_bwd_s16(DecArgs a)
         }
         stage_act(stX, L, ku0);
         __syncthreads();  // ---- A4
-        if (cb == 0) wgrad<2, true>(gW_L1, gB_L1, stage, L, rb, T16_STAGE_MAT, 0);
-        else { float dummy = 0.0f; wgrad<2, false>(gW_L1, dummy, stage, L, rb, T16_STAGE_MAT, 2); }
+        wgrad_layer<2>(gW_L1, gB_L1, stage, L, rb, cb);
         {
             v4f dc[4];
-            zero4(dc);
-            s16_chain<4, 2, 2>(dc, lds, T16_L1, L.trp, dyS);
-#pragma unroll
-            for (int b = 0; b < 4; ++b) dc[b] *= gauss_deriv(ku0[b]);   // du0
+            chain_gauss(dc, lds, T16_L1, L.trp, dyS, ku0);   // du0
             dyS[0] = t16_split(dc[0], dc[1]);
             dyS[1] = t16_split(dc[2], dc[3]);
         }
         __syncthreads();  // ---- B4
         // ================= Spatial_MLP.mlp.0 (32 -> 64) =================
         L = fresh_lane(L);
-        stage_put2(stY, L, 0, dyS[0]);
-        stage_put2(stY, L, 2, dyS[1]);
+        stage_dy(stY, L, dyS);
         stage_put2(stX, L, 0, t16_split(xa, xb));
         __syncthreads();  // ---- A5
-        if (cb == 0) wgrad<1, true>(gW_L0, gB_L0, stage, L, rb, T16_STAGE_MAT, 0);
-        else { float dummy = 0.0f; wgrad<1, false>(gW_L0, dummy, stage, L, rb, T16_STAGE_MAT, 1); }
+        wgrad_layer<1>(gW_L0, gB_L0, stage, L, rb, cb);
         s16_chain<2, 2, 1>(dx, lds, T16_L0, L.trp, dyS);
         if (live) {   // dL/d(decoder inputs) of this lane's 8 positions (the layer-0 image carries weight_feature: no factor left)
             float *o = a.d_feats + n * a.ld_dfeats + 16 * (q & 1) + 4 * (q >> 1);
@@ -668,28 +570,6 @@ __global__ void __launch_bounds__(kThreads, 2) k_decoder_bwd_s16(DecArgs a)
     }
 }
 
-// grad_blob[e] += sum over the workgroups' partial rows (fixed order: deterministic); first-layer weights carry the folded
-// weight_feature (render_bwd.hip k_reduce_dw, same form)
-__global__ void __launch_bounds__(1024) k_decoder_reduce_dw(const float *__restrict__ partial, int nrows, const float *__restrict__ wf,
-                                                            float *__restrict__ grad_blob)
-{
-    __shared__ float part[16][64];
-    const int c = threadIdx.x & 63, r = threadIdx.x >> 6;
-    const int e = blockIdx.x * 64 + c;
-    float s = 0.0f;
-    if (e < SCANERF_PARAMSIZE)
-        for (int w = r; w < nrows; w += 16) s += partial[(size_t)w * SCANERF_PARAMSIZE + e];
-    part[r][c] = s;
-    __syncthreads();
-    if (r == 0 && e < SCANERF_PARAMSIZE) {
-        float t = 0.0f;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) t += part[q][c];
-        if (e >= BLOB_S0 + 64 && e < BLOB_S1) t *= wf[(e - 64) / 64];
-        grad_blob[e] += t;
-    }
-}
-
 int decoder_grid(long long N)
 {
     const long long groups = (((N + 15) >> 4) + kWaves - 1) / kWaves;
@@ -750,18 +630,10 @@ SCANERF_API int scanerf_decoder_backward(const float *feats, int ld_feats, const
     hipError_t me = hipMemsetAsync(dw_partial, 0, (size_t)blocks * SCANERF_PARAMSIZE * sizeof(float), st);
     SCANERF_REQUIRE(me == hipSuccess, "decoder_backward: memset failed: %s", hipGetErrorString(me));
     const size_t lds_bytes = BL::kBytes;
-#define SCANERF_LAUNCH_DEC(DG)                                                                                                  \
-    {                                                                                                                          \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decoder_bwd_s16<DG>),                             \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);                        \
-        SCANERF_REQUIRE(e == hipSuccess, "decoder_backward: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e)); \
-        hipLaunchKernelGGL((k_decoder_bwd_s16<DG>), dim3(blocks), dim3(kThreads), lds_bytes, st, a);                           \
-    }
-    if (d_dirs) SCANERF_LAUNCH_DEC(true)
-    else SCANERF_LAUNCH_DEC(false)
-#undef SCANERF_LAUNCH_DEC
+    if (int e = launch_with_lds(d_dirs ? &k_decoder_bwd_s16<true> : &k_decoder_bwd_s16<false>, blocks, kThreads, lds_bytes, st,
+                                "decoder_backward", a))
+        return e;
     if (int e = check_launch("decoder_backward")) return e;
-    hipLaunchKernelGGL(k_decoder_reduce_dw, dim3(ceil_div(SCANERF_PARAMSIZE, 64)), dim3(1024), 0, st, dw_partial, blocks,
-                       weight_feature, grad_blob);
+    launch_reduce_dw(dw_partial, blocks, weight_feature, grad_blob, st);
     return check_launch("decoder_backward(reduce)");
 }

@@ -596,19 +596,16 @@ namespace scanerf {
 int launch_render_bwd_f32(const BwdArgs &a, int feat_dtype, int blocks, size_t lds_extra, hipStream_t st)
 {
     const size_t lds_bytes = (size_t)kBwdLdsFloats * sizeof(float) + lds_extra;
-#define SCANERF_LAUNCH_BWD(DT)                                                                                     \
-    {                                                                                                              \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_render_bwd<DT>),                      \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);            \
-        SCANERF_REQUIRE(e == hipSuccess, "render_backward: cannot reserve %zu B of LDS: %s", lds_bytes,             \
-                        hipGetErrorString(e));                                                                     \
-        hipLaunchKernelGGL((k_render_bwd<DT>), dim3(blocks), dim3(kBwdThreads), lds_bytes, st, a);                  \
-    }
-    if (feat_dtype == SCANERF_F32) SCANERF_LAUNCH_BWD(SCANERF_F32)
-    else if (feat_dtype == SCANERF_F16) SCANERF_LAUNCH_BWD(SCANERF_F16)
-    else SCANERF_LAUNCH_BWD(SCANERF_BF16)
-#undef SCANERF_LAUNCH_BWD
-    return 0;
+    void (*kernel)(BwdArgs);   // (an if chain: as one conditional expression the kernels' listings differ from the validated ones)
+    if (feat_dtype == SCANERF_F32) kernel = &k_render_bwd<SCANERF_F32>;
+    else if (feat_dtype == SCANERF_F16) kernel = &k_render_bwd<SCANERF_F16>;
+    else kernel = &k_render_bwd<SCANERF_BF16>;
+    return launch_with_lds(kernel, blocks, kBwdThreads, lds_bytes, st, "render_backward", a);
+}
+
+void launch_reduce_dw(const float *partial, int rows, const float *wf, float *grad_blob, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_reduce_dw, dim3(ceil_div(SCANERF_PARAMSIZE, 64)), dim3(1024), 0, st, partial, rows, wf, grad_blob);
 }
 }  // namespace scanerf
 
@@ -694,7 +691,6 @@ SCANERF_API int scanerf_render_backward(const float *rays_o, const float *rays_d
                    : launch_render_bwd_f32(a, feat_dtype, blocks, lds_extra, st))
         return e;
     if (int e = check_launch("render_backward")) return e;
-    hipLaunchKernelGGL(k_reduce_dw, dim3(ceil_div(SCANERF_PARAMSIZE, 64)), dim3(1024), 0, st, dw_partial, prows,
-                       weight_feature, grad_blob);
+    launch_reduce_dw(dw_partial, prows, weight_feature, grad_blob, st);
     return check_launch("render_backward(reduce)");
 }

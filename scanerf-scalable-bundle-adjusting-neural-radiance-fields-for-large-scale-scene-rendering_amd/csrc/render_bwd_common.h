@@ -50,5 +50,8 @@ __device__ __forceinline__ float opaque1(float v)
 int launch_render_bwd_f32(const BwdArgs &a, int feat_dtype, int blocks, size_t lds_extra, hipStream_t st);
 int launch_render_bwd_h3(const BwdArgs &a, int feat_dtype, int blocks, size_t lds_extra, hipStream_t st);
 int launch_render_bwd_t16(const BwdArgs &a, int feat_dtype, int blocks, size_t lds_extra, hipStream_t st, bool split);
+// grad_blob += the `rows` partial rows of `partial`, summed in a fixed order (render_bwd.hip k_reduce_dw); wf = weight_feature,
+// which the first layer's weights carry folded in.  The caller checks the launch.
+void launch_reduce_dw(const float *partial, int rows, const float *wf, float *grad_blob, hipStream_t st);
 
 }  // namespace scanerf

@@ -696,19 +696,11 @@ int launch_render_bwd_h3(const BwdArgs &a, int feat_dtype, int blocks, size_t ld
 {
     const size_t lds_bytes = (size_t)kLdsCursor + lds_extra;
     SCANERF_REQUIRE(lds_bytes <= 160 * 1024, "render_backward(h3): %zu B of LDS needed (table too large for the fused scatter)", lds_bytes);
-#define SCANERF_LAUNCH_BWD(DT)                                                                                     \
-    {                                                                                                              \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_render_bwd_h3<DT>),                   \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);            \
-        SCANERF_REQUIRE(e == hipSuccess, "render_backward(h3): cannot reserve %zu B of LDS: %s", lds_bytes,         \
-                        hipGetErrorString(e));                                                                     \
-        hipLaunchKernelGGL((k_render_bwd_h3<DT>), dim3(blocks), dim3(kThreads), lds_bytes, st, a);                  \
-    }
-    if (feat_dtype == SCANERF_F32) SCANERF_LAUNCH_BWD(SCANERF_F32)
-    else if (feat_dtype == SCANERF_F16) SCANERF_LAUNCH_BWD(SCANERF_F16)
-    else SCANERF_LAUNCH_BWD(SCANERF_BF16)
-#undef SCANERF_LAUNCH_BWD
-    return 0;
+    void (*kernel)(BwdArgs);   // (an if chain: as one conditional expression the kernels' listings differ from the validated ones)
+    if (feat_dtype == SCANERF_F32) kernel = &k_render_bwd_h3<SCANERF_F32>;
+    else if (feat_dtype == SCANERF_F16) kernel = &k_render_bwd_h3<SCANERF_F16>;
+    else kernel = &k_render_bwd_h3<SCANERF_BF16>;
+    return launch_with_lds(kernel, blocks, kThreads, lds_bytes, st, "render_backward(h3)", a);
 }
 
 }  // namespace scanerf

@@ -16,11 +16,13 @@
 //   * POSE = true: also the per-ray sums of the pose refinement (g_dnorm, g_rowsum) and, from the forward's Jacobian stash
 //     (render_device.h jst_pack), dL/d(rays_o), dL/d(rays_d) through the sample positions.
 // Needs the forward's x-stash (without one the caller falls back to render_bwd_h3.hip, which re-gathers).
+// The helpers and the barrier-free segments of the SPLIT layer steps that decoder.hip's k_decoder_bwd_s16 runs too are in
+// render_bwd_t16_device.h (its head lists what is still written out in both kernels).
 // What bounds it, measured: DESIGN.md 4.2a (cycle stamps: -DT16_STAMPS + tools/bwd_stamps.py).
 #include <stdlib.h>
 
 #include "render_bwd_common.h"
-#include "render_t16.h"
+#include "render_bwd_t16_device.h"
 
 using namespace scanerf;
 
@@ -218,123 +220,6 @@ __global__ void __launch_bounds__(256) k_pack_decoder_s16(const float *__restric
     }
 }
 
-// ------------------------------------------------------------------ device helpers
-// A lane index the optimiser cannot trace back.  LDS addresses derived from the plain lane index are loop invariants: the
-// ~60 distinct ones this kernel uses (operand slots in three 64 KB windows, bias rows, the XOR-swizzled staging slots of
-// every block) get hoisted out of the tile loop and held -- or spilled -- for its whole duration.  Derived from an opaque
-// copy they are recomputed where they are used (a handful of VALU per step).
-__device__ __forceinline__ int fresh(int v)
-{
-    asm volatile("" : "+v"(v));
-    return v;
-}
-__device__ __forceinline__ T16Lane fresh_lane(const T16Lane &L)
-{
-    T16Lane r;
-    r.lo16 = fresh(L.lo16);
-    r.w1 = fresh(L.w1);
-    r.r1 = fresh(L.r1);
-    r.r2 = fresh(L.r2);
-    r.pos8 = fresh(L.pos8);
-    r.trp = fresh(L.trp);
-    return r;
-}
-template <int N>
-__device__ __forceinline__ void zero4(v4f (&v)[N])
-{
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = v4f{ 0, 0, 0, 0 };
-}
-// Gaussian activation of a block and its derivative factor G'(u) = -100 u G(u) as f16
-__device__ __forceinline__ void act_deriv(v4f &u, t16_h4 &dg)
-{
-    v4f d;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const float a = gauss_fast(u[g]);
-        d[g] = -100.0f * u[g] * a;
-        u[g] = a;
-    }
-    dg = t16_hi4(d);
-}
-__device__ __forceinline__ v4f mul_dg(const v4f &a, const t16_h4 &dg)
-{
-    return v4f{ a[0] * (float)dg[0], a[1] * (float)dg[1], a[2] * (float)dg[2], a[3] * (float)dg[3] };
-}
-__device__ __forceinline__ t16_h4 lo4(const t16_h8 &v) { return __builtin_shufflevector(v, v, 0, 1, 2, 3); }
-__device__ __forceinline__ t16_h4 hi4(const t16_h8 &v) { return __builtin_shufflevector(v, v, 4, 5, 6, 7); }
-
-// Weight-gradient blocks owned by this wave: acc[i] += sum over the 4 tile pairs of dY[yb] X[xb0 + i]^T (operands read back
-// transposed from the pairs' staging images).  ROWSUM: also accumulate this lane's row sums of dY (bias gradients).
-// SPLIT: hi and lo parts of both operands staged ({Y, X, Y lo, X lo} per wave), three products per term.
-template <int NX, bool ROWSUM, int XSTRIDE = 1, bool SPLIT = false>
-__device__ __forceinline__ void wgrad(v4f *acc, float &rowsum, const char *stage, const T16Lane &L, int yb, int x_mat_off, int xb0)
-{
-#ifdef T16_NO_WGRAD
-    return;
-#endif
-    constexpr int kWave = SPLIT ? 2 * T16_STAGE_WAVE : T16_STAGE_WAVE, kLo = 2 * T16_STAGE_MAT;
-#pragma unroll
-    for (int P = 0; P < 4; ++P) {
-        const char *pm = stage + P * 2 * kWave;
-        const t16_h8 a = t16_stage_get(pm, L, yb);
-        t16_h8 b[NX];
-#pragma unroll
-        for (int i = 0; i < NX; ++i) b[i] = t16_stage_get(pm + x_mat_off, L, xb0 + i * XSTRIDE);
-        if (ROWSUM) rowsum = t16_sum8(a, rowsum);
-        if constexpr (SPLIT) {
-            const t16_h8 alo = t16_stage_get(pm + kLo, L, yb);
-            if (ROWSUM) rowsum = t16_sum8(alo, rowsum);
-#pragma unroll
-            for (int i = 0; i < NX; ++i) {
-                const t16_h8 blo = t16_stage_get(pm + x_mat_off + kLo, L, xb0 + i * XSTRIDE);
-                acc[i] = t16_mfma(alo, b[i], acc[i]);
-                acc[i] = t16_mfma(a, blo, acc[i]);
-                acc[i] = t16_mfma(a, b[i], acc[i]);
-            }
-#ifndef T16_FREE_WGRAD   // (-DT16_FREE_WGRAD: experiment -- let the scheduler hoist the next pair's operand reads over this pair's products)
-            __builtin_amdgcn_sched_barrier(0);   // (bounds the operands in flight: the pairs' reads are not hoisted over each other)
-#endif
-        } else {
-            T16_REGION_BEGIN();
-#pragma unroll
-            for (int i = 0; i < NX; ++i) acc[i] = t16_mfma(a, b[i], acc[i]);
-            T16_REGION_END();
-        }
-    }
-}
-// a split operand (hi, lo) of this lane's sample into blocks b, b + 1 of a staged matrix and of its lo twin
-__device__ __forceinline__ void stage_put2(char *mat, const T16Lane &L, int b, const T16HL &v)
-{
-    t16_stage_put(mat, L, b, __builtin_shufflevector(v.hi, v.hi, 0, 1, 2, 3));
-    t16_stage_put(mat, L, b + 1, __builtin_shufflevector(v.hi, v.hi, 4, 5, 6, 7));
-    t16_stage_put(mat + 2 * T16_STAGE_MAT, L, b, __builtin_shufflevector(v.lo, v.lo, 0, 1, 2, 3));
-    t16_stage_put(mat + 2 * T16_STAGE_MAT, L, b + 1, __builtin_shufflevector(v.lo, v.lo, 4, 5, 6, 7));
-}
-// G'(u) = -100 u G(u) of a block, f32, from its pre-activation (the activation is formed again: 4 exponentials against 4 more
-// registers held across the weight-gradient products)
-__device__ __forceinline__ v4f gauss_deriv(const v4f &u)
-{
-    v4f d;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) d[g] = -100.0f * u[g] * gauss_fast(u[g]);
-    return d;
-}
-// the Gaussian activations of a layer (64 units from their pre-activations), split and staged as blocks 0..3 of X and X lo
-__device__ __forceinline__ void stage_act(char *stX, const T16Lane &L, const v4f u[4])
-{
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        v4f a0, a1;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            a0[g] = gauss_fast(u[2 * t][g]);
-            a1[g] = gauss_fast(u[2 * t + 1][g]);
-        }
-        stage_put2(stX, L, 2 * t, t16_split(a0, a1));
-    }
-}
-
 // REC: format of the scatter records (scatter_common.h): 0 = Rec (16 bytes), 1 = Rec8 (8 bytes), 2 = Rec12 (12 bytes).  POSE: also the two per-ray sums the pose
 // refinement needs (render_bwd_common.h g_dnorm / g_rowsum; csrc/render_bwd_h3.hip is the other kernel that produces them)
 // SPLIT ("t16s"): the gradient products split as well -- dY, W^T (read transposed out of the forward image) and both operands of
@@ -388,13 +273,6 @@ __global__ void __launch_bounds__(kThreads, T16_MIN_WAVES) k_render_bwd_t16(BwdA
 #pragma unroll
     for (int i = 0; i < 23; ++i) stamps[i] = 0;
     uint32_t tlast = (uint32_t)__builtin_amdgcn_s_memtime();
-#endif
-#ifdef T16_WG_STAGGER   // experiment: workgroups start T16_WG_STAGGER x 64 cycles apart in 8 phases (their record bursts then do not coincide chip-wide)
-    for (int i = 0; i < (int)((blockIdx.x >> 3) & 7u); ++i) __builtin_amdgcn_s_sleep(T16_WG_STAGGER);
-#endif
-#ifdef T16_SKEW_START   // timing experiments only (with -DT16_NO_BARRIER): the second wave of every SIMD starts T16_SKEW_START x 8 128 cycles late
-    if (wv >= 4)
-        for (int i = 0; i < T16_SKEW_START; ++i) __builtin_amdgcn_s_sleep(127);
 #endif
     const int ngroups_all = (a.f.B + kWaves - 1) / kWaves;
     for (int grp = blockIdx.x; grp < ngroups_all; grp += gridDim.x) {
@@ -573,12 +451,7 @@ __global__ void __launch_bounds__(kThreads, T16_MIN_WAVES) k_render_bwd_t16(BwdA
             in.xb = v4f{ 0, 0, 0, 0 };
             if (active) {
                 const float4 *xs = reinterpret_cast<const float4 *>(a.xstash + ((size_t)ray * S + (live ? s : 0)) * 32 + 8 * q);
-#ifdef T16_NT_LOADS   // experiment: the x-stash (1 GB, read once) as non-temporal loads, so that it does not displace the records' partially written lines in L2
-                const v4f n0 = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(xs)), n1 = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(xs) + 1);
-                const float4 q0 = make_float4(n0[0], n0[1], n0[2], n0[3]), q1 = make_float4(n1[0], n1[1], n1[2], n1[3]);
-#else
                 const float4 q0 = xs[0], q1 = xs[1];
-#endif
                 in.xa = v4f{ q0.x, q0.y, q0.z, q0.w };
                 in.xb = v4f{ q1.x, q1.y, q1.z, q1.w };
             }
@@ -587,14 +460,6 @@ __global__ void __launch_bounds__(kThreads, T16_MIN_WAVES) k_render_bwd_t16(BwdA
         TileIn nxt = load_tile(nt16 - 1);
         for (int tile = nt16 - 1; tile >= 0; --tile) {
             STAMP(22);
-#ifdef T16_DUMMY_VALU_TOP   // timing experiment: is the kernel bound by vector issue?  N dependent-free vector instructions per tile
-            {
-                float dmy = 1.0f;
-#pragma unroll
-                for (int i = 0; i < T16_DUMMY_VALU_TOP; ++i) asm volatile("v_mul_f32 %0, 1.0, %0" : "+v"(dmy));
-                asm volatile("" ::"v"(dmy));
-            }
-#endif
             const int ln = fresh(lane);               // this tile's lane terms (not loop invariants: see fresh())
             const int c = ln & 15, q = ln >> 4;
             T16Lane L = t16_lane(ln, LD::kStageWave);
@@ -895,10 +760,7 @@ __global__ void __launch_bounds__(kThreads, T16_MIN_WAVES) k_render_bwd_t16(BwdA
                 T16HL dyS[2];
                 {
                     v4f dc[4];
-                    zero4(dc);
-                    s16_chain_narrow<4>(dc, lds, S16T_D2, L.lo16, narS);
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) dc[b] *= gauss_deriv(kv1[b]);
+                    chain_narrow_rgb(dc, lds, L, narS, kv1);
                     dyS[0] = t16_split(dc[0], dc[1]);
                     dyS[1] = t16_split(dc[2], dc[3]);
                 }
@@ -907,15 +769,13 @@ __global__ void __launch_bounds__(kThreads, T16_MIN_WAVES) k_render_bwd_t16(BwdA
                 STAMP(6);
                 // ================= Directional_MLP.mlp.2 (64 -> 64) =================
                 L = fresh_lane(L);
-                stage_put2(stY, L, 0, dyS[0]);
-                stage_put2(stY, L, 2, dyS[1]);
+                stage_dy(stY, L, dyS);
                 stage_act(stX, L, kv0);
                 STAMP(7);
                 STEP_BARRIER();  // ---- A2
                 STAMP(8);
                 if (T16_LOAD_AT == 2 && tile > 0) nxt = load_tile(tile - 1);   // (early: see load_tile)
-                if (cb == 0) wgrad<2, true, 1, true>(gW_D1, gB_D1, stage, L, rb, T16_STAGE_MAT, 0);
-                else { float dummy = 0.0f; wgrad<2, false, 1, true>(gW_D1, dummy, stage, L, rb, T16_STAGE_MAT, 2); }
+                wgrad_layer<2>(gW_D1, gB_D1, stage, L, rb, cb);
                 {
                     v4f dc[4];
                     zero4(dc);
@@ -943,36 +803,22 @@ __global__ void __launch_bounds__(kThreads, T16_MIN_WAVES) k_render_bwd_t16(BwdA
                 STAMP(9);
                 STEP_BARRIER();  // ---- B2
                 STAMP(10);
-#ifdef T16_DUMMY_VALU_MID
-                {
-                    float dmy = 1.0f;
-#pragma unroll
-                    for (int i = 0; i < T16_DUMMY_VALU_MID; ++i) asm volatile("v_mul_f32 %0, 1.0, %0" : "+v"(dmy));
-                    asm volatile("" ::"v"(dmy));
-                }
-#endif
                 // ================= Directional_MLP.mlp.0 (32 of its 48 inputs; the SH part per ray) =================
                 L = fresh_lane(L);
-                stage_put2(stY, L, 0, dyS[0]);
-                stage_put2(stY, L, 2, dyS[1]);
+                stage_dy(stY, L, dyS);
                 stage_put2(stX, L, 0, t16_split(khh[2], khh[3]));
-                {   // the SH part of the layer's input is constant along the ray: staged as 16 more "units" (block 2 of X)
+                {   // the SH part of the layer's input is constant along the ray
                     const float4 shq = *reinterpret_cast<const float4 *>(shbuf + wv * 16 + 4 * q);
-                    const T16HL shS = t16_split(v4f{ shq.x, shq.y, shq.z, shq.w }, zero);
-                    t16_stage_put(stX, L, 2, lo4(shS.hi));
-                    t16_stage_put(stX + kLo, L, 2, lo4(shS.lo));
+                    stage_sh(stX, L, v4f{ shq.x, shq.y, shq.z, shq.w });
                 }
                 STAMP(11);
                 STEP_BARRIER();  // ---- A3
                 STAMP(12);
                 if (T16_LOAD_AT == 3 && tile > 0) nxt = load_tile(tile - 1);   // (early: see load_tile)
-                if (cb == 0) wgrad<2, true, 2, true>(gW_D0, gB_D0, stage, L, rb, T16_STAGE_MAT, 0);   // x = H[32:48] and SH
-                else { float dummy = 0.0f; wgrad<1, false, 1, true>(gW_D0, dummy, stage, L, rb, T16_STAGE_MAT, 1); }   // x = H[48:64]
+                wgrad_dir0(gW_D0, gB_D0, stage, L, rb, cb);
                 {
                     v4f dH[4];
-                    zero4(dH);
-                    s16_chain<2, 2, 2>(&dH[2], lds, T16_D0, L.trp, dyS);        // dH[32:64] = W_D0[:, :32]^T dv0 (input k-step 0 of the D0 pairs)
-                    s16_chain_narrow<2>(&dH[0], lds, S16T_HEAD, L.lo16, narS);  // dH[0:32] = heads^T gh
+                    chain_dH(dH, lds, L.trp, L.lo16, dyS, narS);
                     dyS[0] = t16_split(dH[0], dH[1]);
                     dyS[1] = t16_split(dH[2], dH[3]);
                 }
@@ -981,8 +827,7 @@ __global__ void __launch_bounds__(kThreads, T16_MIN_WAVES) k_render_bwd_t16(BwdA
                 STAMP(14);
                 // ================= Spatial_MLP.mlp.2 (64 -> 64, linear) =================
                 L = fresh_lane(L);
-                stage_put2(stY, L, 0, dyS[0]);
-                stage_put2(stY, L, 2, dyS[1]);
+                stage_dy(stY, L, dyS);
                 {   // u0 = W0 x + b0 again (12 MFMAs against 16 registers held through the whole tile)
                     const T16HL xB = t16_split(xa, xb);
 #pragma unroll
@@ -994,14 +839,10 @@ __global__ void __launch_bounds__(kThreads, T16_MIN_WAVES) k_render_bwd_t16(BwdA
                 STEP_BARRIER();  // ---- A4
                 STAMP(16);
                 if (T16_LOAD_AT == 4 && tile > 0) nxt = load_tile(tile - 1);   // (early: see load_tile)
-                if (cb == 0) wgrad<2, true, 1, true>(gW_L1, gB_L1, stage, L, rb, T16_STAGE_MAT, 0);
-                else { float dummy = 0.0f; wgrad<2, false, 1, true>(gW_L1, dummy, stage, L, rb, T16_STAGE_MAT, 2); }
+                wgrad_layer<2>(gW_L1, gB_L1, stage, L, rb, cb);
                 {
                     v4f dc[4];
-                    zero4(dc);
-                    s16_chain<4, 2, 2>(dc, lds, T16_L1, L.trp, dyS);
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) dc[b] *= gauss_deriv(ku0[b]);   // du0
+                    chain_gauss(dc, lds, T16_L1, L.trp, dyS, ku0);   // du0
                     dyS[0] = t16_split(dc[0], dc[1]);
                     dyS[1] = t16_split(dc[2], dc[3]);
                 }
@@ -1010,15 +851,13 @@ __global__ void __launch_bounds__(kThreads, T16_MIN_WAVES) k_render_bwd_t16(BwdA
                 STAMP(18);
                 // ================= Spatial_MLP.mlp.0 (32 -> 64) =================
                 L = fresh_lane(L);
-                stage_put2(stY, L, 0, dyS[0]);
-                stage_put2(stY, L, 2, dyS[1]);
+                stage_dy(stY, L, dyS);
                 stage_put2(stX, L, 0, t16_split(xa, xb));
                 STAMP(19);
                 STEP_BARRIER();  // ---- A5
                 STAMP(20);
                 if (T16_LOAD_AT == 5 && tile > 0) nxt = load_tile(tile - 1);   // (early: see load_tile)
-                if (cb == 0) wgrad<1, true, 1, true>(gW_L0, gB_L0, stage, L, rb, T16_STAGE_MAT, 0);
-                else { float dummy = 0.0f; wgrad<1, false, 1, true>(gW_L0, dummy, stage, L, rb, T16_STAGE_MAT, 1); }
+                wgrad_layer<1>(gW_L0, gB_L0, stage, L, rb, cb);
                 s16_chain<2, 2, 1>(dx, lds, T16_L0, L.trp, dyS);
             } else {
                 // ================= narrow layers: heads (32 -> 7) and rgb (64 -> 3) =================
@@ -1366,30 +1205,17 @@ int launch_render_bwd_t16(const BwdArgs &a_in, int feat_dtype, int blocks, size_
     SCANERF_REQUIRE(a.xstash, "render_backward(t16): needs the x-stash");
     SCANERF_REQUIRE((a.g_dnorm != nullptr) == (a.g_rowsum != nullptr), "render_backward(t16): g_dnorm and g_rowsum come together");
     SCANERF_REQUIRE(!a.g_raypos || (a.g_dnorm && a.f.jstash), "render_backward(t16): g_raypos needs g_dnorm / g_rowsum and the forward's jstash");
-#define SCANERF_LAUNCH_BWD(DT, R8, PO, SP)                                                                         \
-    {                                                                                                              \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_render_bwd_t16<DT, R8, PO, SP>),      \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);            \
-        SCANERF_REQUIRE(e == hipSuccess, "render_backward(t16): cannot reserve %zu B of LDS: %s", lds_bytes,        \
-                        hipGetErrorString(e));                                                                     \
-        hipLaunchKernelGGL((k_render_bwd_t16<DT, R8, PO, SP>), dim3(blocks), dim3(kThreads), lds_bytes, st, a);     \
-    }
     (void)feat_dtype;  // the table is only read through the x-stash here
     const int rec = a.recs ? a.bins.rec8 : 0;   // record format as the plan decided (scatter_common.h fused_rec8)
     SCANERF_REQUIRE(!(split && rec == 1) && !(!split && rec == 2), "render_backward(t16): record format %d does not belong to this arithmetic", rec);
+    const bool pose = a.g_dnorm != nullptr;
+    void (*kernel)(BwdArgs);   // k_render_bwd_t16<feature type, record format, POSE, SPLIT>
     if (split) {
-        if (a.g_dnorm) {
-            if (rec == 2) SCANERF_LAUNCH_BWD(SCANERF_F32, 2, true, true)
-            else SCANERF_LAUNCH_BWD(SCANERF_F32, 0, true, true)
-        } else if (rec == 2) SCANERF_LAUNCH_BWD(SCANERF_F32, 2, false, true)
-        else SCANERF_LAUNCH_BWD(SCANERF_F32, 0, false, true)
-    } else if (a.g_dnorm) {
-        if (rec == 1) SCANERF_LAUNCH_BWD(SCANERF_F32, 1, true, false)
-        else SCANERF_LAUNCH_BWD(SCANERF_F32, 0, true, false)
-    } else if (rec == 1) SCANERF_LAUNCH_BWD(SCANERF_F32, 1, false, false)
-    else SCANERF_LAUNCH_BWD(SCANERF_F32, 0, false, false)
-#undef SCANERF_LAUNCH_BWD
-    return 0;
+        if (pose) kernel = rec == 2 ? &k_render_bwd_t16<SCANERF_F32, 2, true, true> : &k_render_bwd_t16<SCANERF_F32, 0, true, true>;
+        else kernel = rec == 2 ? &k_render_bwd_t16<SCANERF_F32, 2, false, true> : &k_render_bwd_t16<SCANERF_F32, 0, false, true>;
+    } else if (pose) kernel = rec == 1 ? &k_render_bwd_t16<SCANERF_F32, 1, true, false> : &k_render_bwd_t16<SCANERF_F32, 0, true, false>;
+    else kernel = rec == 1 ? &k_render_bwd_t16<SCANERF_F32, 1, false, false> : &k_render_bwd_t16<SCANERF_F32, 0, false, false>;
+    return launch_with_lds(kernel, blocks, kThreads, lds_bytes, st, "render_backward(t16)", a);
 }
 
 }  // namespace scanerf

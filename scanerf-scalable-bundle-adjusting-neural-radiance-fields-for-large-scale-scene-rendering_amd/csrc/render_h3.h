@@ -55,7 +55,7 @@ struct HL {
     h8 hi, lo;
 };
 // registers 8t .. 8t+7 of an accumulator block -> B operand of k-step t
-// H3_MIX_SPLIT (default, round 4): lo = (f16)(x - (float)hi) as ONE instruction per element (v_fma_mixlo_f16 / v_fma_mixhi_f16:
+// Since round 4: lo = (f16)(x - (float)hi) as ONE instruction per element (v_fma_mixlo_f16 / v_fma_mixhi_f16:
 // the f16 hi part as it is, times -1.0, plus the f32 x, the exact f32 difference rounded to f16 into one half of the destination)
 // instead of v_cvt_f32_f16 + v_sub_f32 per element and a v_cvt_pk_f16_f32 per pair: 12 instead of 24 vector instructions per
 // operand -- the same roundings, the same bits (render_t16.h t16_split is the same form, with what it measured).  Inline asm,
@@ -63,13 +63,9 @@ struct HL {
 // hazard recogniser would put between a vector instruction it can see and a matrix instruction reading its result.
 // (Round 2 tried v_fma_mix_f32 here, -4 % on the render-time frame, and withdrew it because the training step then differed
 // between runs: that build still held packed-f32 instructions, the cause found in round 3 -- DESIGN.md 4.10.)
-#ifndef H3_MIX_SPLIT
-#define H3_MIX_SPLIT 1
-#endif
 __device__ __forceinline__ HL split8(const v16f &v, int t)
 {
     HL o;
-#if H3_MIX_SPLIT
     uint32_t lo32[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -90,20 +86,6 @@ __device__ __forceinline__ HL split8(const v16f &v, int t)
         o.lo[2 * q] = lo[0];
         o.lo[2 * q + 1] = lo[1];
     }
-#else
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const f2v x = { v[8 * t + 2 * q], v[8 * t + 2 * q + 1] };
-        const h2v hi = __builtin_convertvector(x, h2v);
-        const f2v back = __builtin_convertvector(hi, f2v);
-        const f2v r = { x[0] - back[0], x[1] - back[1] };
-        const h2v lo = __builtin_convertvector(r, h2v);
-        o.hi[2 * q] = hi[0];
-        o.hi[2 * q + 1] = hi[1];
-        o.lo[2 * q] = lo[0];
-        o.lo[2 * q + 1] = lo[1];
-    }
-#endif
 #if !(defined(H3_REGIONS) && H3_REGIONS) && SCANERF_GUARDS
     asm volatile("s_nop 1" : "+v"(o.hi), "+v"(o.lo));  // operand guard, see "operand hazard" below
 #endif

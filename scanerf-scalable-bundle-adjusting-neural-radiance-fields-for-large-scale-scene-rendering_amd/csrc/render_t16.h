@@ -55,7 +55,7 @@ struct T16HL {
 };
 // k-step operand from two accumulator blocks (slots j < 4 from `a`, j >= 4 from `b`), split hi + lo
 //
-// T16_MIX_SPLIT (default): lo = (f16)(x - (float)hi) as ONE instruction per element -- v_fma_mixlo_f16 / v_fma_mixhi_f16 take the
+// lo = (f16)(x - (float)hi) as ONE instruction per element -- v_fma_mixlo_f16 / v_fma_mixhi_f16 take the
 // f16 hi part as it is, multiply by -1.0, add the f32 x and round the (exact) f32 difference to f16 into one half of the
 // destination -- instead of v_cvt_f32_f16 + v_sub_f32 per element and a v_cvt_pk_f16_f32 per pair: 12 instead of 24 vector
 // instructions per 8-element operand, 29 operands per tile.  The same two roundings as the plain form (the difference is exact in
@@ -63,13 +63,11 @@ struct T16HL {
 // prefers cvt_pk for a pair of truncations), hence inline asm; what the assembler cannot know is that a matrix instruction must not
 // read a register within two wait states of the vector instruction that wrote it (the hazard recogniser pads that case for
 // instructions it sees: `s_nop` after a v_mov feeding an MFMA), so the lo registers pass through one `s_nop 1` tied to them.
-#ifndef T16_MIX_SPLIT
-#define T16_MIX_SPLIT 1
-#endif
+// (render_h3.h split8 is this code on its own types: written once in render_common.h for both, the render-time kernels' validated
+// listings changed, so there are two.)
 __device__ __forceinline__ T16HL t16_split(const v4f &a, const v4f &b)
 {
     T16HL o;
-#if T16_MIX_SPLIT
     uint32_t lo32[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
@@ -90,20 +88,6 @@ __device__ __forceinline__ T16HL t16_split(const v4f &a, const v4f &b)
         o.lo[2 * p] = lo[0];
         o.lo[2 * p + 1] = lo[1];
     }
-#else
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const t16_f2 x = p < 2 ? t16_f2{ a[2 * p], a[2 * p + 1] } : t16_f2{ b[2 * p - 4], b[2 * p - 3] };
-        const t16_h2 hi = __builtin_convertvector(x, t16_h2);
-        const t16_f2 back = __builtin_convertvector(hi, t16_f2);
-        const t16_f2 r = { x[0] - back[0], x[1] - back[1] };
-        const t16_h2 lo = __builtin_convertvector(r, t16_h2);
-        o.hi[2 * p] = hi[0];
-        o.hi[2 * p + 1] = hi[1];
-        o.lo[2 * p] = lo[0];
-        o.lo[2 * p + 1] = lo[1];
-    }
-#endif
 #if SCANERF_GUARDS
     asm volatile("s_nop 1" : "+v"(o.hi), "+v"(o.lo));  // operand guard (render_h3.h, "operand hazard")
 #endif
@@ -263,9 +247,7 @@ __device__ __forceinline__ void s16_chain(v4f dx[NBI], const char *img, int base
             dx[bi] = t16_mfma(alo, dY[t].hi, dx[bi]);
             dx[bi] = t16_mfma(ahi, dY[t].lo, dx[bi]);
             dx[bi] = t16_mfma(ahi, dY[t].hi, dx[bi]);
-#ifndef T16_FREE_CHAIN   // (-DT16_FREE_CHAIN: experiment -- no bound on the operands in flight)
-            if (bi & 1) __builtin_amdgcn_sched_barrier(0);   // (two input blocks' operands in flight at a time)
-#endif
+            if (bi & 1) __builtin_amdgcn_sched_barrier(0);   // (two input blocks' operands in flight at a time; no bound changed nothing)
         }
 }
 // ... of a narrow layer (heads, rgb): its own transposed pairs (hi, lo), lane l's 16 B at 16 l, one k-step
