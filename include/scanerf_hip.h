@@ -588,6 +588,21 @@ int scanerf_mesh_first_enter(const float *rays_o, const float *rays_d, int B, co
                              const int32_t *start_num, const float *cell_box, const float *scene_info, int log2dim, int lds,
                              float *out, scanerf_stream_t stream);
 
+/* ---- tile allocation (csrc/coverage.hip): the one hot step of the reference's preprocess/build_tiles.py:129-156, fused.  For every
+ *   camera c and every candidate tile box k: counts[k][c] = number of pixels of the reduced frame (h = H / scale, w = W / scale,
+ *   integer division) whose ray enters box k before it meets the mesh.  Ks [C,9] and C2Ws [C,12] row-major f32.  Rays are the
+ *   reference's get_rays_torch_v2 on K / scale (no +0.5 pixel centre): x = (i - cx / scale) / (fx / scale), y = (j - cy / scale) /
+ *   (fy / scale), d = x R[:,0] + y R[:,1] + R[:,2] (not normalised), o = C2W[:,3].  Depth = scanerf_mesh_first_hit's, 0 -> 1e5; near =
+ *   scanerf_ray_aabb_intersection's (box_sizes: full sides), a miss never counts; counted where near < depth.  The tracer's arrays are
+ *   scanerf_mesh_first_hit's.  counts [K,C] i32 must be ZERO-FILLED by the caller: workgroups add into it (integer adds: exact,
+ *   two launches give equal bits).  The boxes are walked in passes of scanerf_view_coverage_boxes_per_pass(); any K works.
+ *   C == 0 or K == 0 is a no-op. */
+int scanerf_view_coverage_boxes_per_pass(void);
+int scanerf_view_coverage(const float *Ks, const float *C2Ws, int C, int H, int W, int scale, const float *box_centers,
+                          const float *box_sizes, int K, const float *vertices, const int32_t *faces, const float *tris,
+                          const uint64_t *bitmask, const uint32_t *rank, const int32_t *start_num, const int32_t *cell_faces,
+                          const float *scene_info, int log2dim, int32_t *counts, scanerf_stream_t stream);
+
 #define SCANERF_RAY_OUT 16
 
 #ifdef __cplusplus

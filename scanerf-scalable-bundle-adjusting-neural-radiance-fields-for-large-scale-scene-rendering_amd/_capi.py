@@ -102,6 +102,8 @@ PROTOTYPES = {
     "scanerf_mesh_gather_triangles": ("I", "PPPLPP", REQ),
     "scanerf_mesh_first_hit": ("I", "PPIPPPPPPPPIIPP", REQ),
     "scanerf_mesh_first_enter": ("I", "PPIPPPPPIIPP", REQ),
+    "scanerf_view_coverage_boxes_per_pass": ("I", "", REQ),
+    "scanerf_view_coverage": ("I", "PPIIIIPPIPPPPPPPPIPP", REQ),
 }
 SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if required]
 OPTIONAL_SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if not required]
