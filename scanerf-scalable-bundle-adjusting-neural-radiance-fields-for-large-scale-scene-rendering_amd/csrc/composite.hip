@@ -28,16 +28,20 @@ __device__ __forceinline__ float wave_sum64(float v)
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
+// The transmittance is a product of up to 512 factors u = 1 - alpha + 1e-6, and float32 cannot hold 1 + 1e-6 (it rounds to
+// 1 + 9.5367e-7): along an empty ray that is 4.6e-8 per factor, 2.4e-5 at S = 512, all of one sign.  So u and the running product are
+// formed in double and rounded once per sample.
 // inclusive prefix product over the lanes
-__device__ __forceinline__ float scan_mul(float v, int lane)
+__device__ __forceinline__ double scan_mul_d(double v, int lane)
 {
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
-        const float t = __shfl_up(v, off, 64);
+        const double t = __shfl_up(v, off, 64);
         if (lane >= off) v *= t;
     }
     return v;
 }
+__device__ __forceinline__ double u_of(float alpha) { return 1.0 - (double)alpha + 1e-6; }
 // inclusive SUFFIX sum over the lanes (lane l: sum of lanes >= l)
 __device__ __forceinline__ float scan_add_down(float v, int lane)
 {
@@ -49,21 +53,30 @@ __device__ __forceinline__ float scan_add_down(float v, int lane)
     return v;
 }
 
+// alpha = 1 - exp(-x) with the fast exponential, exactly as the fused kernels form it (render_device.h): the two routes agree on
+// every ray, thin ones included, where this difference keeps few digits (profiles/per_ray_ops_error.md).
+__device__ __forceinline__ float alpha_of(float x) { return 1.0f - __expf(-x); }
+
 struct Sample {
-    float sigma, z, delta, alpha, u;   // u = 1 - alpha + 1e-6
+    double ud;                            // u in double (the product's factor)
+    float sigma, z, delta, alpha, u, e;   // u = 1 - alpha + 1e-6 (the adjoint's divisor);  e = exp(-sigma delta) = dalpha/dx, kept as the exponential:
+                                          // behind the `infinity` sample's delta = 1e10, 1 - alpha would lose it below 6e-8
     float cd[3], cs[3], tn[3];
 };
 __device__ __forceinline__ Sample load_sample(const float *sigma, const float *dif, const float *spec, const float *tint, const float *z_vals,
                                               const float *dists, size_t e, bool live, bool last, float dnorm, int infinity)
 {
     Sample s = {};
-    s.u = 1.0f;
+    s.u = s.e = 1.0f;
+    s.ud = 1.0;
     if (!live) return s;
     s.sigma = sigma[e];
     s.z = z_vals[e];
     s.delta = (infinity && last) ? 1e10f : dists[e] * dnorm;
-    s.alpha = 1.0f - __expf(-s.sigma * s.delta);
-    s.u = 1.0f - s.alpha + 1e-6f;
+    s.alpha = alpha_of(s.sigma * s.delta);
+    s.e = expf(-s.sigma * s.delta);
+    s.ud = u_of(s.alpha);
+    s.u = (float)s.ud;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         s.cd[c] = dif[3 * e + c];
@@ -84,17 +97,18 @@ __global__ void __launch_bounds__(kThreads) k_composite_fwd(const float *__restr
     for (int i = blockIdx.x * (kThreads >> 6) + (threadIdx.x >> 6); i < B; i += nw) {
         const float dx = rays_d[3 * i], dy = rays_d[3 * i + 1], dz = rays_d[3 * i + 2];
         const float dnorm = sqrtf(dx * dx + dy * dy + dz * dz);
-        float T = 1.0f, T_left = 1.0f;
+        double T = 1.0;
+        float T_left = 1.0f;
         float acc[11] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };   // depth, diffuse 3, tint 3, specular 3, w |c_s|^2
         for (int s0 = 0; s0 < S; s0 += 64) {
             const int s = s0 + lane;
             const bool live = s < S;
             const size_t e = (size_t)i * S + (live ? s : 0);
             const Sample p = load_sample(sigma, dif, spec, tint, z_vals, dists, e, live, s == S - 1, dnorm, infinity);
-            const float incl = scan_mul(p.u, lane);
-            float excl = __shfl_up(incl, 1, 64);
-            if (lane == 0) excl = 1.0f;
-            const float Ts = T * excl, w = p.alpha * Ts;
+            const double incl = scan_mul_d(p.ud, lane);
+            double excl = __shfl_up(incl, 1, 64);
+            if (lane == 0) excl = 1.0;
+            const float Ts = (float)(T * excl), w = p.alpha * Ts;
             if (live) {
                 if (weights) weights[e] = w;
                 if (s == S - 1) T_left = Ts;
@@ -132,7 +146,7 @@ __global__ void __launch_bounds__(kThreads) k_composite_fwd(const float *__restr
 // Adjoint.  g_out [B,16]: dL/d(out_ray) (column 14 = the gradient of sum w |c_s|^2, with w detached); g_w [B,S] (may be null):
 // dL/d(weights).  Writes dL/d(sigma) [N], dL/d(diffuse / specular / tint) [N,3], and g_dnorm [B] = dL/d|d| through delta.
 //   dL/dw_s   = g_depth z + g_dif . c_d + g_tint . t + g_spec . (t c_s) + g_w
-//   dL/dalpha_s = dL/dw_s T_s - (sum_{k>s} dL/dw_k w_k + g_Tleft T_left [s < S-1]) / u_s ,   dalpha/dsigma = delta (1 - alpha)
+//   dL/dalpha_s = dL/dw_s T_s - (sum_{k>s} dL/dw_k w_k + g_Tleft T_left [s < S-1]) / u_s ,   dalpha/dsigma = delta exp(-sigma delta)
 __global__ void __launch_bounds__(kThreads) k_composite_bwd(const float *__restrict__ sigma, const float *__restrict__ dif,
                                                             const float *__restrict__ spec, const float *__restrict__ tint,
                                                             const float *__restrict__ z_vals, const float *__restrict__ dists,
@@ -160,20 +174,20 @@ __global__ void __launch_bounds__(kThreads) k_composite_bwd(const float *__restr
         }
         const float gdepth = go[3], gTl = go[4], gl2 = go[14], T_left = fo[4];
         // transmittance entering each round of 64 samples (forward order), then the rounds last -> first with the suffix sum carried
-        float Tin[8];   // (S <= 512)
+        double Tin[8];   // (S <= 512)
         {
-            float T = 1.0f;
+            double T = 1.0;
             for (int r = 0; r < rounds; ++r) {
                 Tin[r] = T;
                 const int s = 64 * r + lane;
                 const bool live = s < S;
                 const size_t e = (size_t)i * S + (live ? s : 0);
-                float u = 1.0f;
+                double u = 1.0;
                 if (live) {
                     const float delta = (infinity && s == S - 1) ? 1e10f : dists[e] * dnorm;
-                    u = 1.0f - (1.0f - __expf(-sigma[e] * delta)) + 1e-6f;
+                    u = u_of(alpha_of(sigma[e] * delta));
                 }
-                T *= __shfl(scan_mul(u, lane), 63, 64);
+                T *= __shfl(scan_mul_d(u, lane), 63, 64);
             }
         }
         float R = 0.0f;   // sum over the samples of LATER rounds of dL/dw w (+ the T_left term, which every sample but the last sees)
@@ -183,10 +197,10 @@ __global__ void __launch_bounds__(kThreads) k_composite_bwd(const float *__restr
             const bool live = s < S;
             const size_t e = (size_t)i * S + (live ? s : 0);
             const Sample p = load_sample(sigma, dif, spec, tint, z_vals, dists, e, live, s == S - 1, dnorm, infinity);
-            const float incl = scan_mul(p.u, lane);
-            float excl = __shfl_up(incl, 1, 64);
-            if (lane == 0) excl = 1.0f;
-            const float Ts = Tin[r] * excl, w = p.alpha * Ts;
+            const double incl = scan_mul_d(p.ud, lane);
+            double excl = __shfl_up(incl, 1, 64);
+            if (lane == 0) excl = 1.0;
+            const float Ts = (float)(Tin[r] * excl), w = p.alpha * Ts;
             float gw = 0.0f;
             if (live) {
                 gw = gdepth * p.z + (g_w ? g_w[e] : 0.0f);
@@ -198,9 +212,9 @@ __global__ void __launch_bounds__(kThreads) k_composite_bwd(const float *__restr
             if (live) {
                 const float tl = s < S - 1 ? gTl * T_left : 0.0f;
                 const float galpha = gw * Ts - (later + tl) / p.u;
-                const float dads = p.delta * (1.0f - p.alpha);   // dalpha / dsigma; dalpha / ddelta = sigma (1 - alpha)
+                const float dads = p.delta * p.e;   // dalpha / dsigma = delta exp(-sigma delta); dalpha / ddelta = sigma exp(-sigma delta)
                 g_sigma[e] = galpha * dads;
-                if (!(infinity && s == S - 1)) gdn += galpha * p.sigma * (1.0f - p.alpha) * dists[e];
+                if (!(infinity && s == S - 1)) gdn += galpha * p.sigma * p.e * dists[e];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     g_dif[3 * e + c] = w * gd[c];

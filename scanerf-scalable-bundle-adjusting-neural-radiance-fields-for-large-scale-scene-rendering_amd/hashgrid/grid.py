@@ -270,7 +270,7 @@ class HashGrid(nn.Module):
         else:   # (any module with the reference's call signature)
             dec = decoder(torch.cat([feats, dirs], -1), weight_feature=wf)
         train = mode is TRAIN or mode == TRAIN
-        if rays_o.is_cuda and S <= 512:
+        if rays_o.is_cuda and S <= render.COMPOSITE_BACKWARD_MAX_S:
             out_ray, weights = render.composite_rays(dec["sigma"], dec["diffuse"], dec["specular"], dec["tint"], z_vals, dists, rays_d, infinity)
             out = render.render_batch_rays_dict(out_ray, weights, train)
         else:   # (CPU tensors never reach here on the product path: the encoder op raises first; kept for S > 512)

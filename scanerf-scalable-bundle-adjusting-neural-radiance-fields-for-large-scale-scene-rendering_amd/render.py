@@ -609,12 +609,17 @@ def fused_render_rays(rays_o, rays_d, z_vals, dists, features, blob, resolutions
                                  contract_mode, infinity, ray_valid, skip_levels, want_weights)
 
 
+COMPOSITE_BACKWARD_MAX_S = 512   # csrc/composite.hip k_composite_bwd: Tin[8]
+
+
 class CompositeRays(torch.autograd.Function):
     """Alpha compositing of per-sample decoder outputs along rays as ONE op each way (csrc/composite.hip): what
     HashGrid.cal_integrate_weight + accumulate x 4 + the l2_reg_specular sum do in ~35 torch kernels (hashgrid/__init__.py:344-366,
     :564-574, :591-594).  sigma [B,S,1] or [B,S]; diffuse / specular / tint [B,S,3]; z_vals / dists [B,S]; rays_d [B,3] ->
     out_ray [B,16] (columns as the fused forward's: RGB, DEPTH, T_LEFT, DIFFUSE, SPECULAR, TINT, W_SPEC2), weights [B,S].
-    Gradients flow to sigma, diffuse, specular, tint and (through delta = dists |d|) rays_d; z_vals / dists are sampler outputs."""
+    Gradients flow to sigma, diffuse, specular, tint and (through delta = dists |d|) rays_d; z_vals / dists are sampler outputs.
+    The forward takes any S; the adjoint keeps one transmittance per round of 64 samples in registers and stops at
+    COMPOSITE_BACKWARD_MAX_S, so composite_rays() refuses a differentiable call beyond it, instead of loss.backward() failing later."""
 
     @staticmethod
     def forward(ctx, sigma, diffuse, specular, tint, z_vals, dists, rays_d, infinity):
@@ -650,13 +655,20 @@ class CompositeRays(torch.autograd.Function):
             dev_ptr(g_cd, _f32, "g_diffuse"), dev_ptr(g_cs, _f32, "g_specular"), dev_ptr(g_tn, _f32, "g_tint"),
             dev_ptr(g_dn, _f32, "g_dnorm"), B, S, 1 if ctx.infinity else 0, stream()),
             "composite_backward")
-        g_rd = g_dn[:, None] * rd / rd.norm(dim=-1, keepdim=True) if ctx.needs_input_grad[6] else None
+        g_rd = None
+        if ctx.needs_input_grad[6]:   # |d| at d = 0: the subgradient 0, as torch's own norm backward (not 0 / 0)
+            n = rd.norm(dim=-1, keepdim=True)
+            g_rd = torch.where(n == 0, torch.zeros_like(rd), g_dn[:, None] * rd / n)
         sshape, cshape = ctx.shapes
         return g_sigma.reshape(sshape), g_cd.reshape(cshape), g_cs.reshape(cshape), g_tn.reshape(cshape), None, None, g_rd, None
 
 
 def composite_rays(sigma, diffuse, specular, tint, z_vals, dists, rays_d, infinity=False):
     """-> (out_ray [B,16], weights [B,S]); see CompositeRays."""
+    S = z_vals.shape[1]
+    if S > COMPOSITE_BACKWARD_MAX_S and torch.is_grad_enabled() and any(t.requires_grad for t in (sigma, diffuse, specular, tint, rays_d)):
+        raise RuntimeError(f"composite_rays: S={S} with a differentiable input: scanerf_composite_backward takes S <= "
+                           f"{COMPOSITE_BACKWARD_MAX_S} (composite in torch beyond it, or call under torch.no_grad())")
     return CompositeRays.apply(sigma, diffuse, specular, tint, z_vals, dists, rays_d, infinity)
 
 

@@ -249,14 +249,17 @@ class TileModel(nn.Module):
             from . import decoder_op
             sigma, dif, spec, tint = decoder_op.decoder_apply_parts(feats.reshape(-1, 32), d[:, None, :].expand(B, S, 3).reshape(-1, 3),
                                                                     self.decoder.blob(), wf)
-            out_ray, w2 = render.composite_rays(sigma, dif, spec, tint, z, dist, d, False)
-            out = {"valid": valid, "depth": out_ray[:, render.DEPTH], "diffuse": out_ray[:, render.DIFFUSE],
-                   "specular": out_ray[:, render.SPECULAR], "T_left": out_ray[:, render.T_LEFT], "weights": w2, "rgb": out_ray[:, render.RGB]}
-            if train:
-                out["l2_reg_specular"] = out_ray[:, render.W_SPEC2].sum() / (3.0 * B)   # = (w.detach() * spec ** 2).sum(1).mean() of the torch form below
-            return out
-        # other level counts (BASELINE configs[0]: 8), or hip_decoder = False: the torch graph
-        sigma, dif, spec, tint = self.decoder(feats, d[:, None, :].expand(B, S, 3), wf)
+            if S <= render.COMPOSITE_BACKWARD_MAX_S:
+                out_ray, w2 = render.composite_rays(sigma, dif, spec, tint, z, dist, d, False)
+                out = {"valid": valid, "depth": out_ray[:, render.DEPTH], "diffuse": out_ray[:, render.DIFFUSE],
+                       "specular": out_ray[:, render.SPECULAR], "T_left": out_ray[:, render.T_LEFT], "weights": w2, "rgb": out_ray[:, render.RGB]}
+                if train:
+                    out["l2_reg_specular"] = out_ray[:, render.W_SPEC2].sum() / (3.0 * B)   # = (w.detach() * spec ** 2).sum(1).mean() of the torch form below
+                return out
+            # (longer rays than the compositing op's adjoint takes: the torch compositing below, as hashgrid/grid.py does)
+            sigma, dif, spec, tint = sigma.reshape(B, S, 1), dif.reshape(B, S, 3), spec.reshape(B, S, 3), tint.reshape(B, S, 3)
+        else:   # other level counts (BASELINE configs[0]: 8), or hip_decoder = False: the torch graph
+            sigma, dif, spec, tint = self.decoder(feats, d[:, None, :].expand(B, S, 3), wf)
         w2, T_left = composite_weights(sigma[..., 0], dist, d, False)
         w = w2[..., None]
         out = {"valid": valid, "depth": (w[..., 0] * z).sum(1), "diffuse": (w * dif).sum(1),
