@@ -603,6 +603,30 @@ int scanerf_view_coverage(const float *Ks, const float *C2Ws, int C, int H, int 
                           const uint64_t *bitmask, const uint32_t *rank, const int32_t *start_num, const int32_t *cell_faces,
                           const float *scene_info, int log2dim, int32_t *counts, scanerf_stream_t stream);
 
+/* ---- surface normals (csrc/normals.hip): the density's position gradient, fused.  The reference forms it by torch
+ *   autograd through encoder and decoder (hashgrid/__init__.py:374-392 compute_normal, :576-588 render_batch_rays(out_normal=True),
+ *   tile.py:695-712 render_normals).  Here: one gather pass per sample (features and their three position tangents from the same
+ *   eight corner values of each level), the 64 x 32 first-layer product on the f32-input matrix instruction, and the rest of the
+ *   density path in closed form (it is linear behind the first layer).  16 levels, 32-channel decoder; tables f32 / f16.
+ *     x = contracted position in [-2,2]^3, cells as scanerf_embedding_bg_forward;  f = feat * weight_feature [32];
+ *     u0 = W0 f + b0;  s = ws . (W1[:32] G(u0) + b1[:32]) + bs;  sigma = softplus(s);  G(u) = exp(-50 u^2);
+ *     g_k = d sigma / d p_k = sigmoid(s) sum_j a_j G'(u0_j) (W0 (weight_feature * d feat / d p_k))_j,  a = W1[:32]^T ws^T;
+ *     d feat_l / d p_k = A_k (res_l,k - 1) / 4 * sum_c (d w_c / d t_k) table_l[idx_c];   n = -g / (|g| + 1e-8).
+ *   mlp_blob: the flat decoder blob [SCANERF_PARAMSIZE] (not a packed image); weight_feature [32] f32.  Deterministic.
+ * Point form: x = points [N,3] as given, A = axis_scale [3] (host).  -> sigma [N], grad [N,3] = g (may be NULL), normal [N,3]. */
+int scanerf_sigma_normals_points(const float *points, const float *axis_scale /*[3] host*/, const void *features, int feat_dtype,
+                                 const int32_t *resolutions /*[16,3]*/, const float *mlp_blob, const float *weight_feature,
+                                 float *sigma, float *grad, float *normal, int N, int T, scanerf_stream_t stream);
+/* Ray form: samples o + z d, x = contract_fore of the box min_bbox / bbox_size ([3] host each; A = 4 / bbox_size), weights w_i of
+ *   hashgrid/__init__.py:344-360 (delta = dists |d|, T_i = prod_{j<i} (1 - alpha_j + 1e-6), infinity: the last delta is 1e10).
+ *   -> out [B,4] = (sum_i w_i n_i, sum_i w_i), 16-byte aligned; sample_normals [B,S,3] = n_i (may be NULL).  Rays with
+ *   ray_valid[b] == 0 (ray_valid may be NULL) write zeros.  The background contraction is not offered. */
+int scanerf_render_normals(const float *rays_o, const float *rays_d, const float *z_vals, const float *dists, const void *features,
+                           int feat_dtype, const int32_t *resolutions, const float *mlp_blob, const float *weight_feature,
+                           const float *min_bbox /*[3] host*/, const float *bbox_size /*[3] host*/, int infinity,
+                           const uint8_t *ray_valid, float *out, float *sample_normals, int B, int S, int T,
+                           scanerf_stream_t stream);
+
 #define SCANERF_RAY_OUT 16
 
 #ifdef __cplusplus

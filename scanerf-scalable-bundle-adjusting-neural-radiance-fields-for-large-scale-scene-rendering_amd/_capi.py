@@ -104,6 +104,8 @@ PROTOTYPES = {
     "scanerf_mesh_first_enter": ("I", "PPIPPPPPIIPP", REQ),
     "scanerf_view_coverage_boxes_per_pass": ("I", "", REQ),
     "scanerf_view_coverage": ("I", "PPIIIIPPIPPPPPPPPIPP", REQ),
+    "scanerf_sigma_normals_points": ("I", "PPPIPPPPPPIIP", REQ),
+    "scanerf_render_normals": ("I", "PPPPPIPPPPPIPPPIIIP", REQ),
 }
 SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if required]
 OPTIONAL_SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if not required]

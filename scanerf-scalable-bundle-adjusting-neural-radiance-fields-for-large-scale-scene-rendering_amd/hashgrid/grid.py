@@ -173,6 +173,65 @@ class HashGrid(nn.Module):
         linf = torch.max(torch.abs(x), dim=-1, keepdim=True)[0]
         return x * ((2 - 1.0 / linf) / linf), None
 
+    # ---- density and surface normals at points (:368-392) --------------------------------------------------------------------------
+    def _fused_normals(self, decoder, t):
+        return (self.fused and t.is_cuda and hasattr(decoder, "blob") and self.HE.n_levels == 16
+                and getattr(decoder, "in_channel", 32) == 32)
+
+    def _ones_mask(self):
+        return torch.ones(32, dtype=torch.float32, device=self.device)
+
+    def _sigma_torch(self, samples, decoder):
+        feats = self.HE(samples.reshape(-1, 3))
+        return decoder.inference_sigma(feats.reshape(*samples.shape[:-1], 32))
+
+    def inference_sigma(self, samples, decoder):
+        """:368-372: the density at `samples` [...,3], positions of the encoder's own space ([-2,2]^3: no contraction is applied,
+        and no coarse-to-fine mask) -> [...,1].  CUDA samples with a 32-channel blob decoder and 16 levels: the fused kernel
+        (render.sigma_normals_points), detached; anything else: encoder op + decoder.inference_sigma under autograd."""
+        if not self._fused_normals(decoder, samples):
+            return self._sigma_torch(samples, decoder)
+        sigma, _, _ = render.sigma_normals_points(samples.detach().reshape(-1, 3).float().contiguous(), self.HE.features.detach(),
+                                                  self.HE.resolution.to(self.device).int().contiguous(), decoder.blob().detach(),
+                                                  self._ones_mask())
+        return sigma.reshape(*samples.shape[:-1], 1)
+
+    def compute_normal(self, samples, decoder):
+        """:374-392: (normal [...,3], sigma [...,1]) with normal = -g / (|g| + 1e-8), g = d sigma / d samples.
+        The fused route (see inference_sigma) evaluates g in closed form in one launch (csrc/normals.hip).  DIVERGENCE: the
+        reference differentiates with create_graph=True and returns tensors that carry a second-order graph; nothing in it
+        uses that graph (tile.py:708-711 composites under no_grad), and both routes here return detached tensors."""
+        if self._fused_normals(decoder, samples):
+            sigma, _, normal = render.sigma_normals_points(samples.detach().reshape(-1, 3).float().contiguous(), self.HE.features.detach(),
+                                                           self.HE.resolution.to(self.device).int().contiguous(),
+                                                           decoder.blob().detach(), self._ones_mask())
+            return normal.reshape(*samples.shape[:-1], 3), sigma.reshape(*samples.shape[:-1], 1)
+        with torch.enable_grad():
+            x = samples.detach().requires_grad_(True)
+            sigma = self._sigma_torch(x, decoder)
+            g = torch.autograd.grad(sigma, x, torch.ones_like(sigma))[0]
+        return (-g / (g.norm(2, dim=-1, keepdim=True) + 1e-8)).detach(), sigma.detach()
+
+    @torch.no_grad()
+    def render_normals(self, rays_o, rays_d, z_vals, dists, decoder, global_step=None, infinity=False):
+        """Composited surface normals sum_i w_i n_i [B,3] of rays sampled in the foreground box (contract_fore): what
+        render_batch_rays(out_normal=True)["normal"] holds, as ONE launch where the fused route applies (render.render_normals).
+        global_step=None: no coarse-to-fine mask (all ones), as compute_normal; a step: that step's mask, as out_normal."""
+        if z_vals.shape[0] == 0:
+            return torch.zeros((0, 3), dtype=torch.float32, device=z_vals.device)
+        if self._fused_normals(decoder, rays_o):
+            wf = self._ones_mask() if global_step is None else self.weight_feature(global_step).repeat_interleave(2, dim=-1).contiguous()
+            out, _ = render.render_normals(rays_o.detach().contiguous(), rays_d.detach().contiguous(), z_vals.contiguous(), dists.contiguous(),
+                                           self.HE.features.detach(), self.HE.resolution.to(self.device).int().contiguous(),
+                                           decoder.blob().detach(), wf, self._converted("min_bbox", "list"),
+                                           self._converted("bbox_size", "list"), infinity)
+            self.last_render_route = "fused_normals"
+            return out[:, :3].contiguous()
+        with torch.enable_grad():   # (the mask is all ones from step 10 000 on)
+            out, _ = self.render_batch_rays(rays_o.detach(), rays_d.detach(), z_vals, dists, decoder, INFERENCE, self.contract_fore, out_normal=True,
+                                            infinity=infinity, global_step=10000 if global_step is None else global_step)
+        return out["normal"].detach()
+
     # ---- rendering (:413-596) ----------------------------------------------------------------------------------------------------
     def _masked(self, valid, out, B, like_o, like_d):
         if valid is None:   # every ray rendered: the scatter into zero / one filled tensors is the identity

@@ -160,6 +160,76 @@ def render_forward(rays_o, rays_d, z_vals, dists, features, resolutions, packed,
     return out_ray, weights
 
 
+# ---- surface normals: the density's position gradient, fused (csrc/normals.hip) --------------------------------
+_TABLE_DTYPES = (torch.float32, torch.float16)   # (exported tiles are f16; bf16 gather copies keep the op-by-op route)
+
+
+def _normals_common(features, resolutions, blob, weight_feature):
+    """The checks both forms share, before any launch -> (T, the five leading pointers' tail)."""
+    if features.dim() != 3 or features.shape[0] != 16 or features.shape[2] != 2:
+        raise RuntimeError("scanerf: the fused normals need a [16,T,2] table (the reference hard-codes 16 levels)")
+    T = int(features.shape[1])
+    if T < 2 or T & (T - 1):
+        raise RuntimeError(f"scanerf: the table size T={T} must be a power of two")
+    if blob.numel() != _capi.PARAMSIZE or weight_feature.numel() != 32:
+        raise RuntimeError(f"scanerf: blob must hold {_capi.PARAMSIZE} floats and weight_feature 32")
+    if tuple(resolutions.shape) != (16, 3):
+        raise RuntimeError(f"scanerf: resolutions must be [16,3], got {tuple(resolutions.shape)}")
+    return T, (dev_ptr(features, _TABLE_DTYPES, "features"), feat_dtype_code(features), dev_ptr(resolutions, torch.int32, "resolutions"),
+               dev_ptr(blob, _f32, "mlp_blob"), dev_ptr(weight_feature, _f32, "weight_feature"))
+
+
+def _host3(v, name):
+    v = [float(x) for x in v]
+    if len(v) != 3:
+        raise RuntimeError(f"scanerf: {name} must hold 3 floats")
+    return (ctypes.c_float * 3)(*v)
+
+
+def sigma_normals_points(points, features, resolutions, blob, weight_feature, axis_scale=(1.0, 1.0, 1.0), want_grad=False):
+    """Density, its position gradient and the surface normal at contracted points [N,3] in [-2,2]^3 (hashgrid/__init__.py:374-392
+    compute_normal, in closed form): -> sigma [N], grad [N,3] or None (d sigma / d p, with d x_k / d p_k = axis_scale[k]),
+    normal [N,3] = -grad / (|grad| + 1e-8).  blob: the flat decoder blob; weight_feature [32]."""
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError(f"scanerf: points must be [N,3], got {tuple(points.shape)}")
+    T, mid = _normals_common(features, resolutions, blob, weight_feature)
+    N = int(points.shape[0])
+    p = dev_ptr(points, _f32, "points")
+    sigma = torch.empty((N,), dtype=_f32, device=points.device)
+    normal = torch.empty((N, 3), dtype=_f32, device=points.device)
+    grad = torch.empty((N, 3), dtype=_f32, device=points.device) if want_grad else None
+    check(lib().scanerf_sigma_normals_points(p, _host3(axis_scale, "axis_scale"), *mid, dev_ptr(sigma, _f32, "sigma"),
+                                             dev_ptr(grad, _f32, "grad", allow_none=True), dev_ptr(normal, _f32, "normal"), N, T,
+                                             stream()), "sigma_normals_points")
+    return sigma, grad, normal
+
+
+def render_normals(rays_o, rays_d, z_vals, dists, features, resolutions, blob, weight_feature, min_bbox, bbox_size, infinity=False,
+                   ray_valid=None, want_sample_normals=False):
+    """Normals composited along rays (hashgrid/__init__.py:576-588 / tile.py:695-712 as one launch): samples o + z d in
+    contract_fore of the box -> out [B,4] = (sum_i w_i n_i, sum_i w_i) and, on request, the per-sample normals [B,S,3].
+    Rays with ray_valid == 0 give zeros.  min_bbox / bbox_size: host sequences of 3 floats (the HashGrid 2x box)."""
+    if z_vals.dim() != 2:
+        raise RuntimeError(f"scanerf: z_vals must be [B,S], got {tuple(z_vals.shape)}")
+    B, S = (int(v) for v in z_vals.shape)
+    if S < 1:
+        raise RuntimeError(f"scanerf: render_normals needs S >= 1, got S={S}")
+    for t, name, shape in ((rays_o, "rays_o", (B, 3)), (rays_d, "rays_d", (B, 3)), (dists, "dists", (B, S))):
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f"scanerf: {name} must be {list(shape)}, got {list(t.shape)}")
+    if ray_valid is not None and tuple(ray_valid.shape) != (B,):
+        raise RuntimeError(f"scanerf: ray_valid must be [{B}], got {list(ray_valid.shape)}")
+    T, mid = _normals_common(features, resolutions, blob, weight_feature)
+    head = (dev_ptr(rays_o, _f32, "rays_o"), dev_ptr(rays_d, _f32, "rays_d"), dev_ptr(z_vals, _f32, "z_vals"), dev_ptr(dists, _f32, "dists"))
+    valid = dev_ptr(ray_valid, (torch.bool, torch.uint8), "ray_valid", allow_none=True)
+    out = torch.empty((B, 4), dtype=_f32, device=z_vals.device)
+    sn = torch.empty((B, S, 3), dtype=_f32, device=z_vals.device) if want_sample_normals else None
+    check(lib().scanerf_render_normals(*head, *mid, _host3(min_bbox, "min_bbox"), _host3(bbox_size, "bbox_size"), int(bool(infinity)),
+                                       valid, dev_ptr(out, _f32, "out"), dev_ptr(sn, _f32, "sample_normals", allow_none=True), B, S, T,
+                                       stream()), "render_normals")
+    return out, sn
+
+
 _KEEP_DW_PARTIAL = None
 
 

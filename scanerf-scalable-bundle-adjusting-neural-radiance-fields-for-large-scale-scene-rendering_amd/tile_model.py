@@ -317,7 +317,58 @@ class TileModel(nn.Module):
                 "pred_depth": fg[:, render.DEPTH, None] + T * bg[:, render.DEPTH, None],
                 "pred_specular": fg[:, render.SPECULAR] + T * bg[:, render.SPECULAR],
                 "pred_diffuse": fg[:, render.DIFFUSE] + T * bg[:, render.DIFFUSE],
-                "fg": fg, "bg": bg, "fg_weights": wfg, "bg_weights": wbg}
+                "fg": fg, "bg": bg, "fg_weights": wfg, "bg_weights": wbg, "fg_z_vals": z, "fg_dists": dist}
+
+    # ---- surface normals and whole views (tile.py:695-756) ----------------------------------------------------------------------
+    def _ray_normals(self, rays_o, rays_d, z, dist, valid):
+        """sum_i w_i n_i [B,3] of sampled rays, zeros where `valid` (may be None) is off: one fused launch (csrc/normals.hip) on
+        gather_table(), no coarse-to-fine mask (hashgrid/__init__.py:368-392 applies none)."""
+        if self.n_levels != 16:
+            raise RuntimeError("scanerf: the fused normals need 16 levels (the reference hard-codes them)")
+        ones = torch.ones(32, dtype=torch.float32, device=self.device)
+        out, _ = render.render_normals(rays_o.contiguous(), rays_d.contiguous(), z.contiguous(), dist.contiguous(), self.gather_table().detach(),
+                                       self.resolution, self.decoder.blob().detach(), ones, self.min_bbox.tolist(), self.bbox_size.tolist(),
+                                       False, ray_valid=valid)
+        return out[:, :3]
+
+    @torch.no_grad()
+    def render_normals(self, rays_o, rays_d, S):
+        """tile.py:695-712: the composited surface normals of the rays the foreground sampler serves, in their order, mapped to
+        [0,1] as (sum_i w_i n_i + 1) / 2; None when it serves none.  (Valid = every sample placed, this package's fore_valid rule;
+        the sampler fills a ray's row completely or not at all.)"""
+        z, dist = self.sample(rays_o, rays_d, S)
+        valid = torch.all(z != -1, dim=-1)
+        if not bool(valid.any()):
+            return None
+        return (self._ray_normals(rays_o[valid], rays_d[valid], z[valid], dist[valid], None) + 1.0) / 2.0
+
+    @torch.no_grad()
+    def render_image_rays(self, rays_o, rays_d, S_fg, S_bg, global_step, occlusion_mask=None, batch_size=2 ** 14, normals=True,
+                          invalid_underground=False, bg_mode="IZ", fmesh=None):
+        """tile.py:724-756: a whole view in chunks of batch_size rays through render_rays_fused -> the reference's eight maps
+        {"rgb", "fore_depth", "depth", "diffuse", "specular", "fore", "normal", "tint"} ([N,3], depths [N,1]).  "normal": what the
+        reference's commented-out lines (:740,751) would fill -- render_normals' values on the fore-valid rays, zeros elsewhere
+        (the chunk's own foreground samples and valid set go to the kernel, which writes zeros for the other rays: no second
+        sampler launch, no compaction); normals=False leaves it black, as the reference ships it."""
+        N = rays_o.shape[0]
+        z3 = lambda: torch.zeros((N, 3), dtype=torch.float32, device=rays_o.device)
+        z1 = lambda: torch.zeros((N, 1), dtype=torch.float32, device=rays_o.device)
+        img = {"rgb": z3(), "fore_depth": z1(), "depth": z1(), "diffuse": z3(), "specular": z3(), "fore": z3(), "normal": z3(), "tint": z3()}
+        for i in range(0, N, batch_size):
+            o, d = rays_o[i:i + batch_size].contiguous(), rays_d[i:i + batch_size].contiguous()
+            occ = None if occlusion_mask is None else occlusion_mask[i:i + batch_size]
+            sl = slice(i, i + o.shape[0])
+            out = self.render_rays_fused(o, d, S_fg, S_bg, global_step, invalid_underground=invalid_underground, occlusion_mask=occ,
+                                         bg_mode=bg_mode, fmesh=fmesh)
+            fg, vf = out["fg"], out["fore_valid"]
+            img["rgb"][sl], img["depth"][sl] = out["pred_color"], out["pred_depth"]
+            # (an invalid ray's foreground row is zeros: the masked scatters of tile.py:747-752 are these copies)
+            img["fore_depth"][sl], img["fore"][sl], img["tint"][sl] = fg[:, render.DEPTH, None], fg[:, render.RGB], fg[:, render.TINT]
+            img["diffuse"][sl], img["specular"][sl] = fg[:, render.DIFFUSE], fg[:, render.SPECULAR]
+            if normals:
+                n = self._ray_normals(o, d, out["fg_z_vals"], out["fg_dists"], vf)
+                img["normal"][sl] = (n + 1.0) / 2.0 * vf[:, None]
+        return img
 
     # ---- optimiser on the table: fused sparse Adam (only touched entries move) --------------
     @torch.no_grad()

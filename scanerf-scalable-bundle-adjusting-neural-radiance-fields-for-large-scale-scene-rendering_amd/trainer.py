@@ -293,6 +293,40 @@ class TileTrainer:
                 on_step(self.global_step, loss)
         return loss
 
+    @torch.no_grad()
+    def validate(self, views, batch_size=2 ** 14, normals=True):
+        """The reference's periodic look at test views (tile.py:810-862) without its image files: for every view
+        (rays_o [H*W,3], rays_d [H*W,3], target [H,W,3] in 0..1 or None, occlusion [H*W,1] bool or None, H, W) a dictionary with
+        "psnr" / "ssim" (metrics.py; None without a target), "panel" = the training-view frame of :834-835 (colour, diffuse,
+        specular / depth, foreground depth, target) and "novel_panel" = the novel-view frame of :859-860 (foreground, diffuse,
+        specular / normal map with its channels reversed, foreground depth, colour): float32 arrays [2H,3W,3] in [0,1]."""
+        import numpy as np
+        from . import metrics
+        if self.num_bg_sample < 1:
+            raise ValueError("TileTrainer.validate renders foreground + background (tile.py:639-692): it needs num_bg_sample >= 1")
+        rows = []
+        for rays_o, rays_d, target, occlusion, H, W in views:
+            out = self.model.render_image_rays(rays_o, rays_d, self.num_sample, self.num_bg_sample, self.global_step, occlusion_mask=occlusion,
+                                               batch_size=batch_size, normals=normals, **self._mesh_kw_view())
+            im = {k: v.reshape(H, W, -1).float() for k, v in out.items()}
+            unit = lambda dep: (dep / dep.max().clamp_min(1e-12)).expand(H, W, 3)
+            tgt = torch.zeros_like(im["rgb"]) if target is None else torch.as_tensor(target, dtype=torch.float32).to(im["rgb"].device).reshape(H, W, 3)
+            row = {"psnr": None, "ssim": None}
+            if target is not None:
+                row["psnr"] = metrics.psnr(im["rgb"] * 255.0, tgt * 255.0)
+                row["ssim"] = float(metrics.ssim(im["rgb"][None].permute(0, 3, 1, 2), tgt[None].permute(0, 3, 1, 2)))
+            cat = lambda top, bottom: torch.cat([torch.cat(top, 1), torch.cat(bottom, 1)], 0).clamp(0, 1).cpu().numpy().astype(np.float32)
+            row["panel"] = cat([im["rgb"], im["diffuse"], im["specular"]], [unit(im["depth"]), unit(im["fore_depth"]), tgt])
+            row["novel_panel"] = cat([im["fore"], im["diffuse"], im["specular"]], [im["normal"].flip(-1), unit(im["fore_depth"]), im["rgb"]])
+            rows.append(row)
+        return rows
+
+    def _mesh_kw_view(self):
+        if self.bg_mode == "IZ":
+            return {}
+        self.fmesh.set(self.model._center_dev, self.model._half_dev)
+        return {"bg_mode": self.bg_mode, "fmesh": self.fmesh}
+
     def export_check_point(self, path):
         self.model.table_lr = self.table_lr
         return formats.export_check_point(path, self.model, self.consensus, self.dec_opt, self.global_step)

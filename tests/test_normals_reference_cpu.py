@@ -1,0 +1,150 @@
+"""The surface-normal yardstick (tests/normals_reference.py) checked on its own, without a GPU: against the reference's autograd
+golden G18, against a finite difference of its own float64 density, the conditions each family of the case list claims, and the
+new entry points' prototypes."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import normals_reference as R
+from gradient_reference64 import pinned_cells, pinned_points
+from oracle import oracle as O
+
+T = torch.from_numpy
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def _g18():
+    g15, g18 = np.load(os.path.join(GOLD, "g15_render_masks.npz")), np.load(os.path.join(GOLD, "g18_normals.npz"))
+    corner, size = T(g15["tile_corner"]), T(g15["tile_size"])
+    center = corner + size / 2.0
+    sz = size * 2
+    mn = center - sz / 2.0
+    sd = {k[3:]: T(g15[k]) for k in g15.files if k.startswith("sd.")}
+    return g15, g18, sd, mn, sz
+
+
+def test_float64_yardstick_reproduces_the_reference_autograd_golden_g18():
+    """G18 is the reference's own render_batch_rays(out_normal=True): autograd through ITS decoder, ITS normalisation and weights.
+    The closed form in float64 behind the pinned cells gives the same composited normals (2x box and contraction scale included)."""
+    g15, g18, sd, mn, sz = _g18()
+    step = int(g18["global_step"])
+    r = R.render_normals(g18["rays_o"], g18["rays_d"], g18["z_vals"], g18["dists"], T(g15["features"]), T(g15["res"]), sd, mn, sz,
+                         R.mask64(step).to(R.F32), False)
+    ref = T(g18["normal"]).double()
+    rel = float((r["out"][:, :3] - ref).norm() / ref.norm())
+    print(f"G18: float64 closed form vs the reference's autograd golden: relative L2 {rel:.2e}, max abs {float((r['out'][:, :3] - ref).abs().max()):.2e}")
+    assert float(ref.norm(dim=-1).max()) > 0.1
+    assert rel < 2e-6, rel
+
+
+def test_gradient_matches_a_central_difference_of_the_float64_density_inside_the_cells():
+    """d sigma / d p of the closed form against (sigma(p + h e_k) - sigma(p - h e_k)) / 2h in float64, moving the cell offsets of every
+    level by h A_k (res_l,k - 1) / 4 inside their cells (h = 1e-6: truncation ~ h^2, rounding ~ 1e-16 / h, both far below 1e-6 of
+    the conditioning scale), anisotropic box, non-zero biases, partly closed mask."""
+    c = R.Case("aniso", 40, 8, 12, False, False, "all", 77)
+    ins = R.case_inputs(c)
+    sd = O.init_mlp(seed=3, bias_scale=0.05)
+    mask = R.mask64(R.MASK_STEP_PARTLY).to(R.F32)
+    x = pinned_points(ins["o"], ins["d"], ins["z"], False, ins["mn"], ins["sz"])
+    res = ins["res"].numpy()
+    A = R.ascale_of(ins["sz"])
+    b, t = pinned_cells(x, res)
+    keep = np.all((t > 0.01) & (t < 0.99), axis=(1, 2))
+    assert keep.sum() >= 64, keep.sum()
+    b, t = b[keep], T(t[keep]).double()
+    ev = lambda tt: R.evaluate_cells(b, tt, A, ins["table"], res, sd, mask, R.F64)
+    base = ev(t)
+    h = 1e-6
+    step = T(A.astype(np.float64))[None, :] * (T(res.astype(np.float64)) - 1) / 4     # [L,3]: d t / d p
+    fd = torch.zeros_like(base["g"])
+    for k in range(3):
+        dt = torch.zeros_like(t)
+        dt[..., k] = h * step[None, :, k]
+        fd[:, k] = (ev(t + dt)["sigma"] - ev(t - dt)["sigma"]) / (2 * h)
+    err = (base["g"] - fd).norm(dim=1) / base["cond"].norm(dim=1)
+    print(f"finite difference on {int(keep.sum())} samples: max error over the conditioning scale {float(err.max()):.2e}")
+    assert float(base["g"].norm(dim=1).min()) > 0
+    assert float(err.max()) < 1e-6
+
+
+def test_every_family_meets_its_stated_conditions():
+    seen = set()
+    for c in R.ALL_CASES:
+        ins, r64, r32 = R.case_reference(c)
+        seen.add(c.family)
+        assert 10 <= c.log2_T <= 13 or c is R.CASE_LARGE
+        assert ins["table"].dtype == (torch.float16 if c.half else torch.float32) and ins["table"].shape == (16, 2 ** c.log2_T, 2)
+        assert np.abs(r64["x"]).max() <= 2.0   # every sample inside the 2x box
+        assert bool(torch.isfinite(r64["out"]).all()) and bool(torch.isfinite(r32["out"]).all())
+        B, S = ins["z"].shape
+        w, sigma = r64["w"], r64["pts"]["sigma"].reshape(B, S)
+        if c.family == "opaque":
+            delta = T(ins["dist"]).double() * T(ins["d"]).double().norm(dim=1, keepdim=True)
+            Tr = torch.exp(-(sigma * delta)[:, :4].sum(1))
+            assert float((Tr < 1e-5).double().mean()) == 1.0, float(Tr.max())
+        if c.family == "empty":
+            assert float(r64["out"][:, 3].max()) < 1e-4 and float(sigma.max()) < 1e-4
+        if c.family == "mask":
+            assert int((R.case_mask(ins) == 0).sum()) >= 2 and int((R.case_mask(ins) == 1).sum()) >= 2
+        else:
+            assert bool((R.case_mask(ins) == 1).all())
+        if c.family == "aniso":
+            A = R.ascale_of(ins["sz"])
+            assert A.max() / A.min() >= 3
+        if c.family == "bias":
+            assert all(float(v.abs().max()) > 0 for k, v in ins["sd"].items() if k.endswith(".bias"))
+        if c.family == "fresh":
+            assert 2e-5 < float(ins["table"].float().abs().mean()) < 2e-4
+        if c.family == "scaled":
+            # a tangent of the finest level leaves f16's range
+            assert float(r64["pts"]["dfeat"].abs().max()) > 65504 and float((r64["pts"]["dfeat"].abs() > 65504).double().mean()) > 0.01
+            assert float(r64["pts"]["g"].norm(dim=1).median()) > 1e-3   # (and the gradients are not washed out)
+        if c.family == "zero":
+            assert bool((r64["pts"]["g"] == 0).all()) and bool((r64["out"][:, :3] == 0).all()) and float(r64["out"][:, 3].min()) > 0.1
+        if c.family == "faces":
+            _, t = pinned_cells(r64["x"], ins["res"].numpy())
+            assert int((r64["x"][:, 0] == 2.0).sum()) >= S and int((t[:, 0, 1] == 0).sum()) == B * S
+        if c.valid == "none":
+            assert not ins["valid"].any() and bool((r64["out"] == 0).all())
+        if c.valid == "alternate":
+            assert 0 < ins["valid"].sum() < B
+    assert seen == set(R.FAMILIES)
+    assert {c.S for c in R.ALL_CASES} >= {1, 2, 15, 16, 17, 33, 128} and {c.B for c in R.ALL_CASES} >= {1, 3, 63, 64, 65, 261}
+    assert {c.infinity for c in R.ALL_CASES} == {False, True} and {c.half for c in R.ALL_CASES} == {False, True}
+    assert R.CASE_LARGE.log2_T == 19 and np.array_equal(R.case_inputs(R.CASE_LARGE)["res"][[0, -1]].numpy(), [[32] * 3, [2048] * 3])
+
+
+def test_float32_yardstick_is_at_float32_rounding():
+    """The yardstick's own figures on the base cases: a few float32 roundings, as on G18's inputs."""
+    for c in R.CASES_S:
+        _, r64, r32 = R.case_reference(c)
+        f = R.figures(r32["out"][:, :3], r64["out"][:, :3], r64["out"][:, 3])
+        g = R.figures(r32["pts"]["g"], r64["pts"]["g"], r64["pts"]["cond"].norm(dim=1))
+        assert 1e-8 < f["median"] < 1e-6 and f["max"] < 1e-5, f
+        assert 1e-8 < g["median"] < 1e-6 and g["max"] < 1e-5, g
+
+
+def test_new_prototypes_agree_with_the_header():
+    """The two new exports go through the existing _capi mechanism: one table entry each, equal to the header's declaration."""
+    import scanerf_amd  # noqa
+    from scanerf_amd import _capi
+    from test_capi_cpu import _header_prototypes
+    hdr = _header_prototypes()
+    for name in ("scanerf_sigma_normals_points", "scanerf_render_normals"):
+        assert hdr[name] == _capi.PROTOTYPES[name][:2], (name, hdr[name])
+        assert _capi.PROTOTYPES[name][2] is _capi.REQ
+        assert hasattr(_capi.lib(), name)
+    assert _capi.lib().scanerf_abi_version() == 9
+
+
+def test_python_surface_exists():
+    import scanerf_amd  # noqa
+    from scanerf_amd import render, tile_model, trainer
+    from scanerf_amd.hashgrid import HashGrid
+    assert callable(render.sigma_normals_points) and callable(render.render_normals)
+    for name in ("inference_sigma", "compute_normal", "render_normals"):
+        assert callable(getattr(HashGrid, name))
+    assert callable(tile_model.TileModel.render_normals) and callable(tile_model.TileModel.render_image_rays)
+    assert callable(trainer.TileTrainer.validate)
