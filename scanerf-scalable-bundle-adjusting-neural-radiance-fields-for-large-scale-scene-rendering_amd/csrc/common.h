@@ -35,34 +35,13 @@ inline int check_launch(const char *what)
         }                                          \
     } while (0)
 
-// Wait-state guards of rounds 1-2, COMPILED OUT (SCANERF_GUARDS = 0).  They were placed behind global stores
-// (SCANERF_STORE_GUARD: 16 states), behind gathers (SCANERF_LOAD_GUARD: 32) and around matrix instructions (render_h3.h
-// H3_REGIONS, render_t16.h T16_REGION_*, the operand guards of the splits) after launch-to-launch differences that came and went
-// with the register allocation.  Round 3 found what those differences have in common: packed-f32 instructions
-// (v_pk_mul/add/fma_f32, formed by the SLP vectoriser) in a kernel that also runs matrix instructions.  Without them no guard is
-// needed (0 differing launches of 1 200 with every guard off, instruction caches swept or not; with them and no guards 199 of
-// 199: tools/guard_probe.py), so the kernels are compiled with -fno-slp-vectorize (csrc/Makefile, tools/isa_audit.py) and carry no
-// guards.  -DSCANERF_GUARDS=1 -DH3_REGIONS=1 rebuilds the guarded listings for that experiment matrix (tools/build_variant.py).
-#ifndef SCANERF_GUARDS
-#define SCANERF_GUARDS 0
-#endif
-#if SCANERF_GUARDS
-#define SCANERF_LOAD_GUARD()                                                         \
-    do {                                                                             \
-        __builtin_amdgcn_sched_barrier(0);                                           \
-        asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7\n\ts_nop 7");                    \
-        __builtin_amdgcn_sched_barrier(0);                                           \
-    } while (0)
-#define SCANERF_STORE_GUARD()                    \
-    do {                                         \
-        __builtin_amdgcn_sched_barrier(0);       \
-        asm volatile("s_nop 7\n\ts_nop 7");      \
-        __builtin_amdgcn_sched_barrier(0);       \
-    } while (0)
-#else
-#define SCANERF_LOAD_GUARD() do { } while (0)
-#define SCANERF_STORE_GUARD() do { } while (0)
-#endif
+// NO PACKED-F32 ARITHMETIC, and no wait-state guards.  Rounds 1-2 placed guards behind global stores, behind gathers and around
+// matrix instructions (closed scheduling regions followed by s_nop) after launch-to-launch differences that came and went with
+// the register allocation.  Round 3 found what those differences have in common: packed-f32 instructions (v_pk_mul/add/fma_f32,
+// formed by the SLP vectoriser) in a kernel that also runs matrix instructions.  Without them no guard is needed (0 differing
+// launches of 1 200 with every guard off, instruction caches swept or not; with them and no guards 199 of 199), so the kernels are
+// compiled with -fno-slp-vectorize (csrc/Makefile, tools/isa_audit.py) and the guards are gone from the source: commit 2f39c6d is
+// the last tree that can rebuild the guarded listings of that experiment matrix (tools/build_variant.py, tools/guard_probe.py).
 
 // Tuning switches of the A/B experiments (launch shapes, alternative producers): environment variables read at launch time ONLY in
 // a library built with -DSCANERF_EXPERIMENTS (make EXP=1); the product build compiles every one of them to its default -- no

@@ -45,9 +45,7 @@ __global__ void __launch_bounds__(64) k_h3_selftest(const float *packed, const f
 #pragma unroll
                 for (int tq = 0; tq < 2; ++tq) {
                     const A2 a = h3_lda_T(lds, base, ksb, nb, tq, ib, L);
-                    H3_REGION_BEGIN();
                     mma3(acc, a, ys[nb].t[tq]);
-                    H3_REGION_END();
                 }
 #pragma unroll
             for (int g = 0; g < 16; ++g) out_dx[(layer * 64 + 32 * ib + nmap(g, h)) * 32 + sl] = acc[g];
@@ -67,9 +65,7 @@ __global__ void __launch_bounds__(64) k_h3_selftest(const float *packed, const f
             for (int t = 0; t < 2; ++t) {
                 const HL a = h3_stage_get(stY, L.g0[nb], L.g1[nb], t), b = h3_stage_get(stX, L.g0[kb], L.g1[kb], t);
                 if (kb == 0) rs = h3_sum8(a, rs);
-                H3_REGION_BEGIN();
                 mma3(acc, a, b);
-                H3_REGION_END();
             }
             // acc: row n = 32nb + nmap(g,h), column k = 32kb + sl
 #pragma unroll

@@ -83,14 +83,12 @@ __device__ __forceinline__ void chain64(v16f dx[NIB], const char *img, int base,
             HL a[NIB];
 #pragma unroll
             for (int ib = 0; ib < NIB; ++ib) a[ib] = h3_lda_T(img, base, ksb, nb, tq, ib, L);
-            H3_REGION_BEGIN();
 #pragma unroll
             for (int ib = 0; ib < NIB; ++ib) dx[ib] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[ib].lo, dy[nb].t[tq].hi, dx[ib], 0, 0, 0);
 #pragma unroll
             for (int ib = 0; ib < NIB; ++ib) dx[ib] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[ib].hi, dy[nb].t[tq].lo, dx[ib], 0, 0, 0);
 #pragma unroll
             for (int ib = 0; ib < NIB; ++ib) dx[ib] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[ib].hi, dy[nb].t[tq].hi, dx[ib], 0, 0, 0);
-            H3_REGION_END();
         }
 }
 // dX (NIB row blocks) = W^T dY for a layer with ONE 32-row output block whose live rows sit in k-step 0 (heads, rgb)
@@ -100,10 +98,8 @@ __device__ __forceinline__ void chain_narrow(v16f dx[NIB], const char *img, int 
     HL a[NIB];
 #pragma unroll
     for (int ib = 0; ib < NIB; ++ib) a[ib] = h3_lda_T(img, base, ksb, 0, 0, ib, L);
-    H3_REGION_BEGIN();
 #pragma unroll
     for (int ib = 0; ib < NIB; ++ib) mma3(dx[ib], a[ib], dy);
-    H3_REGION_END();
 }
 
 // Weight-gradient block owned by this wave: acc += sum over slots [slot0, slot0+NS) of dY_slot[yb] X_slot[xb]^T, the
@@ -129,9 +125,7 @@ __device__ __forceinline__ void wgrad_block(v16f &acc, float &rowsum, const char
         // row sums (bias gradients) only over steps [ROWSUM_FROM, ROWSUM_TO) + rs_shift: the two owners of a row
         // block share that work
         if (ROWSUM_TO > ROWSUM_FROM && i >= ROWSUM_FROM + rs_shift && i < ROWSUM_TO + rs_shift) rowsum = h3_sum8(a, rowsum);
-        H3_REGION_BEGIN();
         mma3(acc, a, b);
-        H3_REGION_END();
         a = an;
         b = bn;
     }
@@ -615,7 +609,6 @@ __global__ void __launch_bounds__(kThreads, 1) k_render_bwd_h3(BwdArgs a)
                     }
                 }
             }
-            SCANERF_STORE_GUARD();  // dfeat / record stores: their data registers are about to be reused by matrix results
         }
         // ---- per ray group: pose-gradient row sums of the own slots' rays
         if (a.g_rowsum && h == 0) {

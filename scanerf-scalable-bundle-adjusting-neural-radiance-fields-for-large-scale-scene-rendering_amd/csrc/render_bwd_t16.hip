@@ -314,11 +314,9 @@ __global__ void __launch_bounds__(kThreads, T16_MIN_WAVES) k_render_bwd_t16(BwdA
                 const char *p = lds + T16_D0 + (b * 2 + 1) * T16_PAIR + (SPLIT ? L.pos8 : L.lo16);
                 const t16_h8 ahi = SPLIT ? s16_lda(p) : *reinterpret_cast<const t16_h8 *>(p);
                 const t16_h8 alo = SPLIT ? s16_lda(p + T16_SUB) : *reinterpret_cast<const t16_h8 *>(p + T16_SUB);
-                T16_REGION_BEGIN();
                 dinit[b] = t16_mfma(alo, shB.hi, dinit[b]);
                 dinit[b] = t16_mfma(ahi, shB.lo, dinit[b]);
                 dinit[b] = t16_mfma(ahi, shB.hi, dinit[b]);
-                T16_REGION_END();
             }
             if (c == 0) {
                 float4 *dp = reinterpret_cast<float4 *>(lds + LD::kDinit + wv * 256);
@@ -402,7 +400,6 @@ __global__ void __launch_bounds__(kThreads, T16_MIN_WAVES) k_render_bwd_t16(BwdA
                 else emit_pairs<8>(pr, gx, gy, cl, a.bins.bucket_log, a.bins.capacity, a.recs, gl);
 #endif
             }
-            SCANERF_STORE_GUARD();  // the records' / dfeat's data registers are about to be reused by matrix results
         };
         v4f pdx0 = { 0, 0, 0, 0 }, pdx1 = { 0, 0, 0, 0 };   // the previous tile's dX, emitted during this one
         float ppe[3] = { 0, 0, 0 };                         // ... and its samples' contracted positions (computed once per tile)
@@ -514,11 +511,9 @@ __global__ void __launch_bounds__(kThreads, T16_MIN_WAVES) k_render_bwd_t16(BwdA
                     for (int b = 0; b < 4; ++b) {  // k-step 0 of the D0 pairs
                         const char *p = lds + T16_D0 + (b * 2) * T16_PAIR + L.pos8;
                         const t16_h8 ahi = s16_lda(p), alo = s16_lda(p + T16_SUB);
-                        T16_REGION_BEGIN();
                         kv0[b] = t16_mfma(alo, HB[1].hi, kv0[b]);
                         kv0[b] = t16_mfma(ahi, HB[1].lo, kv0[b]);
                         kv0[b] = t16_mfma(ahi, HB[1].hi, kv0[b]);
-                        T16_REGION_END();
                     }
                     v4f act[4];
 #pragma unroll
@@ -590,11 +585,9 @@ __global__ void __launch_bounds__(kThreads, T16_MIN_WAVES) k_render_bwd_t16(BwdA
                     for (int b = 0; b < 4; ++b) {  // k-step 0 of the D0 pairs
                         const char *p = lds + T16_D0 + (b * 2) * T16_PAIR + L.lo16;
                         const t16_h8 ahi = *reinterpret_cast<const t16_h8 *>(p), alo = *reinterpret_cast<const t16_h8 *>(p + T16_SUB);
-                        T16_REGION_BEGIN();
                         v[b] = t16_mfma(alo, HB[1].hi, v[b]);
                         v[b] = t16_mfma(ahi, HB[1].lo, v[b]);
                         v[b] = t16_mfma(ahi, HB[1].hi, v[b]);
-                        T16_REGION_END();
                     }
 #pragma unroll
                     for (int b = 0; b < 4; ++b) act_deriv(v[b], dgv0[b]);
@@ -1105,7 +1098,6 @@ __global__ void __launch_bounds__(kThreads, T16_MIN_WAVES) k_render_bwd_t16(BwdA
                 a.g_dnorm[(size_t)ray * ncol] = pose_dn;
                 for (int t = 1; t < ncol; ++t) a.g_dnorm[(size_t)ray * ncol + t] = 0.0f;
             }
-            SCANERF_STORE_GUARD();
         }
     }
 

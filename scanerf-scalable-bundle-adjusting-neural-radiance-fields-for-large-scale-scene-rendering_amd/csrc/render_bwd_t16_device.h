@@ -95,10 +95,8 @@ __device__ __forceinline__ void wgrad(v4f *acc, float &rowsum, const char *stage
             }
             __builtin_amdgcn_sched_barrier(0);   // (bounds the operands in flight: the pairs' reads are not hoisted over each other; freeing them changed nothing)
         } else {
-            T16_REGION_BEGIN();
 #pragma unroll
             for (int i = 0; i < NX; ++i) acc[i] = t16_mfma(a, b[i], acc[i]);
-            T16_REGION_END();
         }
     }
 }

@@ -482,7 +482,6 @@ __device__ __forceinline__ void encode8_01(const void *table, const int32_t *res
         x[2 * j + 1] = ay;
         if ((j + 1) % GATHER_BATCH == 0) __builtin_amdgcn_sched_barrier(0);
     }
-    SCANERF_LOAD_GUARD();
 }
 
 // decode_tile with the SH part of the directional layer computed inline (per-lane direction):

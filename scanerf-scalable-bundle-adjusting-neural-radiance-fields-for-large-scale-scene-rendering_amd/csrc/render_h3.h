@@ -31,7 +31,7 @@ typedef float f2v __attribute__((ext_vector_type(2)));
 namespace scanerf {
 
 __host__ __device__ constexpr int h3_ku(int t, int h, int j) { return 16 * t + 8 * (j >> 2) + 4 * h + (j & 3); }
-// H3_OPAQUE_ADDR (render.hip and render_time.hip): lane offsets and the base of the f32 tail are made opaque to the optimiser.
+// H3_OPAQUE_ADDR (render.hip and render_infer.hip): lane offsets and the base of the f32 tail are made opaque to the optimiser.
 // Seeing lane >> 5 as a 0/1 value it otherwise turns every `image offset + lane offset` into its own select of two constants, and
 // the f32 tail lies past 64 KB, beyond the immediate of an LDS read: one address register per weight / bias read, ~35 of them
 // live across the sample loop (render-time kernel 25 -> 4 spilled registers, frame 105 -> 99 ms; training forward 51 -> 0 spills
@@ -86,9 +86,6 @@ __device__ __forceinline__ HL split8(const v16f &v, int t)
         o.lo[2 * q] = lo[0];
         o.lo[2 * q + 1] = lo[1];
     }
-#if !(defined(H3_REGIONS) && H3_REGIONS) && SCANERF_GUARDS
-    asm volatile("s_nop 1" : "+v"(o.hi), "+v"(o.lo));  // operand guard, see "operand hazard" below
-#endif
     return o;
 }
 struct HL2 {
@@ -102,12 +99,8 @@ __device__ __forceinline__ HL2 split16(const v16f &v)
     return o;
 }
 
-// ---- "operand hazard" (rounds 1-2; guards compiled out, see common.h SCANERF_GUARDS).
-// With the f16 MFMAs scheduled freely among the VALU code that produces their B operands, 3e-4 of the 32-sample tiles came out
-// wrong in lanes 16-31, differently on every launch.  Rounds 1-2 answered with wait states where an operand is produced (split8)
-// or with closed scheduling regions around every MFMA group (H3_REGIONS = 1).  Round 3: the differences need packed-f32
-// instructions in the kernel (the splits' x - (float)hi had become v_pk_add_f32); compiled with -fno-slp-vectorize the kernels
-// are bit-reproducible without either (tools/guard_probe.py), which is how they are built.
+// (The f16 MFMAs are scheduled freely among the VALU code that produces their B operands; the "operand hazard" of rounds 1-2
+// and its wait-state guards: common.h.)
 typedef HL A2;  // an A operand (weights): the same pair of parts
 __device__ __forceinline__ A2 h3_lda(const char *sub)  // `sub` = address of this lane's 16 B of the hi part
 {
@@ -116,16 +109,7 @@ __device__ __forceinline__ A2 h3_lda(const char *sub)  // `sub` = address of thi
     a.lo = *reinterpret_cast<const h8 *>(sub + H3_SUB);
     return a;
 }
-#if defined(H3_REGIONS) && H3_REGIONS
-#define H3_REGION_BEGIN() __builtin_amdgcn_sched_barrier(0)
-#define H3_REGION_END()          \
-    asm volatile("s_nop 1");     \
-    __builtin_amdgcn_sched_barrier(0)
-#else
-#define H3_REGION_BEGIN()
-#define H3_REGION_END()
-#endif
-// acc += W * B with the three-term split (small terms first); call between H3_REGION_BEGIN / END
+// acc += W * B with the three-term split (small terms first)
 __device__ __forceinline__ void mma3(v16f &acc, const A2 &a, const HL &b)
 {
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a.lo, b.hi, acc, 0, 0, 0);
@@ -145,14 +129,12 @@ __device__ __forceinline__ void h3_layer2(v16f u[2], const char *img, int base, 
             n0 = h3_lda(img + base + ((0 * ksb + s + 1) * 2) * H3_SUB + lo);
             n1 = h3_lda(img + base + ((1 * ksb + s + 1) * 2) * H3_SUB + lo);
         }
-        H3_REGION_BEGIN();
         u[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0.lo, B[s]->hi, u[0], 0, 0, 0);
         u[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1.lo, B[s]->hi, u[1], 0, 0, 0);
         u[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0.hi, B[s]->lo, u[0], 0, 0, 0);
         u[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1.hi, B[s]->lo, u[1], 0, 0, 0);
         u[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0.hi, B[s]->hi, u[0], 0, 0, 0);
         u[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1.hi, B[s]->hi, u[1], 0, 0, 0);
-        H3_REGION_END();
         a0 = n0;
         a1 = n1;
     }
@@ -166,9 +148,7 @@ __device__ __forceinline__ void h3_layer1(v16f &u, const char *img, int base, in
     for (int s = 0; s < KS; ++s) {
         A2 n = a;
         if (s + 1 < KS) n = h3_lda(img + base + ((s + 1) * 2) * H3_SUB + lo);
-        H3_REGION_BEGIN();
         mma3(u, a, *B[s]);
-        H3_REGION_END();
         a = n;
     }
 }
@@ -304,10 +284,8 @@ __device__ __forceinline__ void h3_dinit(const char *img, int lane, const float 
     dinit[0] = h3_bias(img, 2, 0, h);
     dinit[1] = h3_bias(img, 2, 1, h);
     const A2 a0 = h3_lda(h3_sub(img, H3_D0, 3, 0, 2, lo)), a1 = h3_lda(h3_sub(img, H3_D0, 3, 1, 2, lo));
-    H3_REGION_BEGIN();
     mma3(dinit[0], a0, b);
     mma3(dinit[1], a1, b);
-    H3_REGION_END();
 }
 
 __device__ __forceinline__ v16f act16_fast(const v16f &x)

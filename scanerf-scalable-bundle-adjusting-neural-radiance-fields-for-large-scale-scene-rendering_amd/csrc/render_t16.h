@@ -88,9 +88,6 @@ __device__ __forceinline__ T16HL t16_split(const v4f &a, const v4f &b)
         o.lo[2 * p] = lo[0];
         o.lo[2 * p + 1] = lo[1];
     }
-#if SCANERF_GUARDS
-    asm volatile("s_nop 1" : "+v"(o.hi), "+v"(o.lo));  // operand guard (render_h3.h, "operand hazard")
-#endif
     return o;
 }
 // hi part only (gradient operands)
@@ -104,9 +101,6 @@ __device__ __forceinline__ t16_h8 t16_hi(const v4f &a, const v4f &b)
         o[2 * p] = hi[0];
         o[2 * p + 1] = hi[1];
     }
-#if SCANERF_GUARDS
-    asm volatile("s_nop 1" : "+v"(o));
-#endif
     return o;
 }
 __device__ __forceinline__ t16_h4 t16_hi4(const v4f &a)
@@ -138,18 +132,7 @@ __device__ __forceinline__ v4f t16_mfma(const t16_h8 &a, const t16_h8 &b, const 
 {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
-// Rounds 1-2 made every group of MFMAs a closed scheduling region followed by wait states (1e-5 .. 3e-3 of the forward's tiles
-// came out wrong in sample columns 16-31 otherwise).  Compiled out since round 3 (common.h SCANERF_GUARDS): without packed-f32
-// instructions in the kernel (-fno-slp-vectorize) nothing differs between launches with the MFMAs scheduled freely.
-#if SCANERF_GUARDS
-#define T16_REGION_BEGIN() __builtin_amdgcn_sched_barrier(0)
-#define T16_REGION_END()       \
-    asm volatile("s_nop 3");   \
-    __builtin_amdgcn_sched_barrier(0)
-#else
-#define T16_REGION_BEGIN()
-#define T16_REGION_END()
-#endif
+// (The MFMAs are scheduled freely; the wait-state guards of rounds 1-2 around them: common.h.)
 
 // forward layer: u[b] += W[b] X over KS k-steps (three products per term, small ones first).  `img` + `base` =
 // the layer's first pair, `lo16` = 16 * lane.
@@ -171,14 +154,12 @@ __device__ __forceinline__ void t16_layer(v4f u[NB], const char *img, int base, 
                 ahi[b] = *reinterpret_cast<const t16_h8 *>(p);
                 alo[b] = *reinterpret_cast<const t16_h8 *>(p + T16_SUB);
             }
-            T16_REGION_BEGIN();
 #pragma unroll
             for (int b = 0; b < G; ++b) u[b0 + b] = t16_mfma(alo[b], B[t].hi, u[b0 + b]);
 #pragma unroll
             for (int b = 0; b < G; ++b) u[b0 + b] = t16_mfma(ahi[b], B[t].lo, u[b0 + b]);
 #pragma unroll
             for (int b = 0; b < G; ++b) u[b0 + b] = t16_mfma(ahi[b], B[t].hi, u[b0 + b]);
-            T16_REGION_END();
         }
 }
 // transposed product: dx[b_in] += W^T[b_in] dY over KS k-steps of the output units (hi parts only)
@@ -190,10 +171,8 @@ __device__ __forceinline__ void t16_chain(v4f dx[NBI], const char *img, int base
         t16_h8 a[NBI];
 #pragma unroll
         for (int b = 0; b < NBI; ++b) a[b] = *reinterpret_cast<const t16_h8 *>(img + base + (b * KS + t) * T16_SUB + lo16);
-        T16_REGION_BEGIN();
 #pragma unroll
         for (int b = 0; b < NBI; ++b) dx[b] = t16_mfma(a[b], dY[t], dx[b]);
-        T16_REGION_END();
     }
 }
 // ---- "t16s": the same layers with the gradient products split as well (hi + lo of W^T and of dY, three MFMAs per term) ----
@@ -218,14 +197,12 @@ __device__ __forceinline__ void s16_layer(v4f u[NB], const char *img, int base, 
                 ahi[b] = s16_lda(p);
                 alo[b] = s16_lda(p + T16_SUB);
             }
-            T16_REGION_BEGIN();
 #pragma unroll
             for (int b = 0; b < G; ++b) u[b0 + b] = t16_mfma(alo[b], B[t].hi, u[b0 + b]);
 #pragma unroll
             for (int b = 0; b < G; ++b) u[b0 + b] = t16_mfma(ahi[b], B[t].lo, u[b0 + b]);
 #pragma unroll
             for (int b = 0; b < G; ++b) u[b0 + b] = t16_mfma(ahi[b], B[t].hi, u[b0 + b]);
-            T16_REGION_END();
         }
 }
 __device__ __forceinline__ t16_h4 t16_tr4(const char *p);
@@ -258,11 +235,9 @@ __device__ __forceinline__ void s16_chain_narrow(v4f dx[NBI], const char *img, i
     for (int b = 0; b < NBI; ++b) {
         const char *p = img + base + b * T16_PAIR + lo16;
         const t16_h8 ahi = *reinterpret_cast<const t16_h8 *>(p), alo = *reinterpret_cast<const t16_h8 *>(p + T16_SUB);
-        T16_REGION_BEGIN();
         dx[b] = t16_mfma(alo, dY.hi, dx[b]);
         dx[b] = t16_mfma(ahi, dY.lo, dx[b]);
         dx[b] = t16_mfma(ahi, dY.hi, dx[b]);
-        T16_REGION_END();
     }
 }
 

@@ -89,7 +89,7 @@ def test_backward_is_bit_reproducible(arith):
 def test_forward_as_the_training_step_calls_it_is_bit_reproducible(dt):
     """Forward with the x-stash and tile_T outputs (what train_step_fused launches) after two training steps: this is the
     configuration in which a vector-memory store picked up a rewritten data register in 1 of ~4e5 tiles before
-    SCANERF_STORE_GUARD (csrc/common.h)."""
+    SCANERF_STORE_GUARD (a wait-state guard of rounds 1-2; csrc/common.h says why none is needed any more)."""
     from scanerf_amd import render
     from scanerf_amd.tile_model import TileModel, train_step_fused
     torch.manual_seed(9)

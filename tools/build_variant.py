@@ -4,17 +4,19 @@ standard objects of the rest into <pkg>/lib/debug/libscanerf_hip_<tag>.so (selec
 the product).
 
     tools/build_variant.py <tag> unit="flags" [unit="flags" ...]
-    e.g. tools/build_variant.py slp_guarded render="-DH3_OPAQUE_ADDR=1 -DSCANERF_GUARDS=1 -DH3_REGIONS=1"   (rounds 1-2's form)
-         tools/build_variant.py slp_bare render="-DH3_OPAQUE_ADDR=1"                                       (differs in every launch)
+    e.g. tools/build_variant.py slp_bare render="-DH3_OPAQUE_ADDR=1 -fslp-vectorize"       (differs in every launch)
 
-`flags` replace the unit's EXTRA of csrc/Makefile (the common flags stay)."""
+`flags` replace the unit's EXTRA of csrc/Makefile (the common flags stay).
+
+The guarded variant of rounds 1-2 (slp_guarded: render="-DH3_OPAQUE_ADDR=1 -DSCANERF_GUARDS=1 -DH3_REGIONS=1") is built from commit
+2f39c6d, the last tree whose sources hold the wait-state guards (csrc/common.h says why they are gone)."""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "scanerf-scalable-bundle-adjusting-neural-radiance-fields-for-large-scale-scene-rendering_amd")
 CSRC, OBJ, DBG = os.path.join(PKG, "csrc"), os.path.join(PKG, "lib", "obj"), os.path.join(PKG, "lib", "debug")
 COMMON = ("-O3 --offload-arch=gfx950 -fPIC -fvisibility=hidden -std=c++17 -munsafe-fp-atomics -Wall -I../../include -I. "
           "-fno-slp-vectorize -Xclang -target-feature -Xclang -packed-fp32-ops").split()   # (csrc/Makefile COMMON; a unit's flags may undo them)
-UNITS = "rays adam render_time voxelize api hashgrid render scatter render_bwd render_bwd_h3 render_bwd_t16 h3_selftest loss compact decoder composite".split()
+UNITS = "rays adam render_time render_infer voxelize api hashgrid render scatter render_bwd render_bwd_h3 render_bwd_t16 h3_selftest loss compact decoder composite".split()
 tag, specs = sys.argv[1], dict(a.split("=", 1) for a in sys.argv[2:])
 assert all(u in UNITS for u in specs), specs
 os.makedirs(DBG, exist_ok=True)
