@@ -106,14 +106,17 @@ __global__ void __launch_bounds__(kThreads) k_select(const float *__restrict__ r
                     cost = 0.9f * angle + 0.1f * dis;
                 }
             }
-            // sorted insert: strict < keeps the earlier (lower-index) camera ahead on ties
+            // sorted insert: strict < places the new camera behind the earlier (lower-index) ones it ties with; from there on
+            // every entry shifts down one slot (a carried entry that ties with the next one must not be dropped in its favour)
             float cc = cost;
             int ci = c0 + i;
+            bool placed = false;
 #pragma unroll
             for (int j = 0; j < kMaxK; ++j) {
-                if (j < K && cc < best[j]) {
+                if (j < K && (placed || cc < best[j])) {
                     const float tc = best[j]; best[j] = cc; cc = tc;
                     const int ti = bidx[j]; bidx[j] = ci; ci = ti;
+                    placed = true;
                 }
             }
         }
