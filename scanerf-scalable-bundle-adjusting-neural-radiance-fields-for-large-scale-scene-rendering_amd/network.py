@@ -51,6 +51,22 @@ def xavier_blob(seed=0, device="cpu", bias_scale=0.0, in_channel=32):
     return blob_from_state_dict(sd, in_channel).to(device)
 
 
+_C1 = 0.4886025119029199
+_C2 = (1.0925484305920792, -1.0925484305920792, 0.31539156525252005, -1.0925484305920792, 0.5462742152960396)
+_C3 = (-0.5900435899266435, 2.890611442640554, -0.4570457994644658, 0.3731763325901154, -0.4570457994644658,
+       1.445305721320277, -0.5900435899266435)
+
+
+def sh3(v):
+    """Real spherical harmonics up to degree 3 of unit vectors (16 values, network.py:38-77 ordering)."""
+    x, y, z = v.unbind(-1)
+    xx, yy, zz, xy, yz, xz = x * x, y * y, z * z, x * y, y * z, x * z
+    return torch.stack([torch.full_like(x, 0.28209479177387814), _C1 * y, _C1 * z, _C1 * x, _C2[0] * xy, _C2[1] * yz,
+                        _C2[2] * (2.0 * zz - xx - yy), _C2[3] * xz, _C2[4] * (xx - yy), _C3[0] * y * (3 * xx - yy),
+                        _C3[1] * xy * z, _C3[2] * y * (4 * zz - xx - yy), _C3[3] * z * (2 * zz - 3 * xx - 3 * yy),
+                        _C3[4] * x * (4 * zz - xx - yy), _C3[5] * z * (xx - yy), _C3[6] * x * (xx - 3 * yy)], -1)
+
+
 def skip_levels(global_step):
     """Bit l set: weight_feature(global_step) is exactly zero on level l (levels >= alpha of the coarse-to-fine schedule)."""
     w = weight_feature(global_step)[::2]
@@ -146,7 +162,6 @@ class ShallowMLP(nn.Module):
         return self.sigma_layer(H[..., :32])
 
     def forward_torch(self, x, **kwargs):
-        from .tile_model import sh3
         features, viewdirs = x[..., :-3], x[..., -3:]
         viewdirs = viewdirs / (viewdirs.norm(2, dim=-1, keepdim=True) + 1e-8)
         H = self.Spatial_MLP(features * kwargs["weight_feature"])

@@ -1,10 +1,12 @@
 """Fused fast path: one launch per HashGrid.render_batch_rays (hashgrid/__init__.py:512-596)."""
+import contextlib
 import ctypes
 
 import torch
 
 from . import _capi
 from ._capi import RAY_OUT, RenderCfg, check, dev_ptr, feat_dtype_code, lib, stream
+from .network import sh3
 
 _f32 = torch.float32
 FORE, BG = 0, 1
@@ -514,11 +516,10 @@ def ray_gradients_fused(rays_o, rays_d, blob, ray_pos_grad, g_dnorm, g_rowsum, r
 def ray_gradients_fused_autograd(rays_o, rays_d, blob, ray_pos_grad, g_dnorm, g_rowsum, ray_valid=None):
     """ray_gradients_fused by torch autograd on [B]-sized tensors (what it was before the epilogue kernel: ~150 small launches);
     kept as the reference the tests compare the kernel with."""
-    from . import tile_model
     d = rays_d.detach().clone().requires_grad_(True)
     with torch.enable_grad():
         dn = d.norm(2, dim=-1, keepdim=True)
-        sh = tile_model.sh3(d / (dn + 1e-8))
+        sh = sh3(d / (dn + 1e-8))
     w_sh = blob[6503 + 64 + 32 * 64: 6503 + 64 + 48 * 64].reshape(16, 64)  # Directional_MLP.mlp.0 weight^T rows 32..47
     g_sh = g_rowsum.sum(1) @ w_sh.t()
     g_dn = g_dnorm.sum(1, keepdim=True)
@@ -535,7 +536,6 @@ def ray_gradients(rays_o, rays_d, z_vals, features, resolutions, blob, min_bbox,
     """dL/d(rays_o), dL/d(rays_d) of a fused render (for pose refinement: tile.py trains se3_refine through
     the rays).  Three paths: the sample positions (hash-encoder point gradient kernel on dfeat, then the
     contraction's Jacobian by torch autograd), |d| through delta = dist*|d|, and SH(d/|d|) of the decoder."""
-    from . import tile_model
     B, S = z_vals.shape
     dev = z_vals.device
     mn = torch.as_tensor(min_bbox, dtype=_f32, device=dev)
@@ -548,7 +548,7 @@ def ray_gradients(rays_o, rays_d, z_vals, features, resolutions, blob, min_bbox,
             linf = torch.max(torch.abs(x), dim=-1, keepdim=True)[0]
             x = x * ((2 - 1.0 / linf) / linf)
         dn = d.norm(2, dim=-1, keepdim=True)
-        sh = tile_model.sh3(d / (dn + 1e-8))
+        sh = sh3(d / (dn + 1e-8))
     gp = torch.zeros(B * S, 3, dtype=_f32, device=dev)
     xd = x.detach().contiguous()
     check(lib().scanerf_embedding_bg_point_grad(dev_ptr(xd, _f32, "points"), dev_ptr(dfeat, _f32, "dfeat"),
@@ -568,6 +568,154 @@ def ray_gradients(rays_o, rays_d, z_vals, features, resolutions, blob, min_bbox,
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# One render branch, forward to table gradient: what the training steps (tile_model) and the autograd boundary below both run.
+# Table-gradient routes (table_grad_route):
+RECORDS_ADAM = "records_adam"    # the backward kernel emits the records; accumulate + sparse Adam (adam2 for two branches)
+RECORDS_TABLE = "records_table"  # the backward kernel emits the records; accumulate into a gradient table
+RAYS_ADAM = "rays_adam"          # dfeat -> scatter_table_grad_adam_rays (places the samples itself; large tables)
+POINTS_ADAM = "points_adam"      # dfeat at contracted points built in torch -> scatter_table_grad_adam
+POINTS_TABLE = "points_table"    # dfeat at contracted points -> scatter_table_grad into a gradient table (then table_adam)
+_TABLE_ROUTES = (RECORDS_TABLE, POINTS_TABLE)
+# ... and the entry points asking for one
+SINGLE, FGBG_STEP, FGBG_GRADIENTS, AUTOGRAD = "single", "fgbg_step", "fgbg_gradients", "autograd"
+
+
+def table_grad_route(entry, T, B, S, arith, half_table=False, fused_adam=True, fused_scatter=None, large_t_route="dfeat"):
+    """How a training step's feature gradients reach the table -> (routes: one per branch sample count in S, the
+    `compact_records` of a contracted-points scatter).  Pure: no allocation, no launch.  arith: the backward's arithmetic;
+    half_table: a half-precision gather copy is resident; large_t_route: the steps' switch tile_model.LARGE_T_ROUTE (the
+    tile_model wrapper of this function passes it).  Each entry point keeps the choice it made before this was one place
+    (tests/test_table_grad_route_cpu.py gives each row's reason):
+      SINGLE: records where fused_scatter (default: T <= 2^21 or LARGE_T_ROUTE "fused") and the workspace allow, f32 included;
+        else rays / points ending in the Adam, or with fused_adam=False points into a gradient table (compact above 2^21 only);
+      FGBG_STEP: records + adam2 as SINGLE but never under f32; above 2^21 (not f32, no half table) ONE rays / points scatter
+        over both branches; else FGBG_GRADIENTS' gradient table;
+      FGBG_GRADIENTS: per branch, records into the table at T <= 2^21 (LARGE_T_ROUTE ignored), else points with -1;
+      AUTOGRAD (only asked when the table needs a gradient): records at T <= 2^21, else points with -1."""
+    # records emitted by the backward kernel need the level's cursors in ITS LDS (256 buckets per level): above 2^21 entries
+    # they outgrow the accumulate's LDS image.  The split pass in front of the accumulate (csrc/scatter.hip k_bin_split) serves
+    # larger tables, but the stand-alone scatter from dfeat (2^13-entry buckets) is still ahead there (T = 2^24, 16 384 rays:
+    # 5.6 against 6.1 ms per step): LARGE_T_ROUTE = "fused" selects the split pass
+    small = T <= (1 << 21)
+    records = all(scatter_supported(B, s, T) for s in S)
+    compact = compact_record_format(arith)
+    if entry == SINGLE:
+        if fused_scatter is None:
+            fused_scatter = small or large_t_route == "fused"
+        if fused_scatter and records:
+            route = RECORDS_ADAM if fused_adam else RECORDS_TABLE
+        elif not fused_adam:
+            route, compact = POINTS_TABLE, (-1 if small else compact)
+        else:
+            route = RAYS_ADAM if scatter_rays_supported(T, arith) and not half_table else POINTS_ADAM
+        return (route,), compact
+    if entry == FGBG_STEP:
+        if (small or large_t_route == "fused") and records and arith != _capi.ARITH_F32:
+            return (RECORDS_ADAM,) * len(S), compact
+        if not small and arith != _capi.ARITH_F32 and not half_table:
+            return (RAYS_ADAM if scatter_rays_supported(T, arith) else POINTS_ADAM,) * len(S), compact
+        entry = FGBG_GRADIENTS
+    if entry == FGBG_GRADIENTS:
+        return tuple(RECORDS_TABLE if small and scatter_supported(B, s, T) else POINTS_TABLE for s in S), -1
+    if entry == AUTOGRAD:
+        return (RECORDS_TABLE if small and records else POINTS_TABLE,), -1
+    raise ValueError(f"table_grad_route: unknown entry point {entry!r}")
+
+
+def _sec(timer, name, alg_bytes=0, alg_flops=0):
+    """A section of `timer` (tile_model.KernelTimer), or nothing to enter without one."""
+    return timer.section(name, alg_bytes, alg_flops) if timer is not None else contextlib.nullcontext()
+
+
+MLP_FLOPS_PER_SAMPLE = 2 * 13728  # SURVEY.md 8(d): 27 456 FLOP per sample forward
+
+
+class _Branch:
+    """One render branch on the fused kernels: the forward with its stashes, the record plan of the table-gradient route, the
+    backward, the ray gradients and the finish of a route into a gradient table.
+    resolution, packed, blob: the grid's level resolutions, the PackedDecoder this pass packed (its skip_levels go to the plan)
+    and the decoder blob; box: the 2x box as host (min_bbox, bbox_size); route / compact: from table_grad_route (route None:
+    no table gradient, dfeat only).  sized=False (fgbg_gradients): only the backward is a timer section, without byte and FLOP
+    counts; workspace: the branch's own record workspace (default: the per-stream one); master: the fp32 table the point
+    gradients of ray_gradients read (default: the gather table, converted); box_dev: the box as device tensors for points()
+    (default: uploaded when asked)."""
+
+    def __init__(self, resolution, packed, blob, box, rays_o, rays_d, z, dist, valid, mode, infinity, route, compact, timer=None,
+                 sized=True, workspace=None, master=None, box_dev=None):
+        self.resolution, self.packed, self.blob, self.master, self.box_dev = resolution, packed, blob, master, box_dev
+        self.rays_o, self.rays_d, self.z, self.dist, self.valid = rays_o, rays_d, z, dist, valid
+        self.box = (*box, mode, infinity)
+        self.route, self.compact, self.timer, self.sized, self.workspace = route, compact, timer, sized, workspace
+        self.records = route in (RECORDS_ADAM, RECORDS_TABLE)
+        self.B, self.S = z.shape
+        self.ws = self.tile_T = self.xstash = self.jstash = self.dfeat = self.arith = None
+
+    def _sec(self, name, *counts):
+        return _sec(self.timer if self.sized else None, name, *counts)
+
+    def forward(self, table, plan=False, jstash=False, want_weights=False, stash=True):
+        """plan: the launch also reserves the backward's record ranges (forward_plan_supported); jstash: it stashes the encoder's
+        position Jacobians, so that the backward chains the feature gradients to the rays without a second pass over the table;
+        stash=False (nothing needs a gradient): no tile_T / x-stash, no backward.  -> out_ray (weights in self.weights)."""
+        B, S, dev = self.B, self.S, self.z.device
+        self.table = table
+        if stash:
+            self.tile_T = torch.empty((B, tile_T_columns(S)), device=dev)
+            self.xstash = torch.empty((B * S, 32), device=dev)  # encoder outputs: 1 GB at 65 536 x 128, saves the re-gather
+        if jstash:
+            self.jstash = torch.empty(jstash_shape(B, S), dtype=JSTASH_DTYPE, device=dev)
+        with self._sec("render_forward", B * (24 + 20 + S * 16 * 8 * 2 * table.element_size()), B * S * MLP_FLOPS_PER_SAMPLE):
+            r = render_forward(self.rays_o, self.rays_d, self.z, self.dist, table, self.resolution, self.packed, *self.box,
+                               ray_valid=self.valid, want_weights=want_weights, tile_T=self.tile_T, xstash=self.xstash,
+                               plan=plan, plan_workspace=self.workspace, jstash=self.jstash)
+        if plan:
+            self.ws = r[2]
+        self.out, self.weights = r[0], r[1]
+        return self.out
+
+    def points(self):
+        mn, sz = self.box_dev or (torch.as_tensor(v, dtype=_f32, device=self.z.device) for v in self.box[:2])
+        return contracted_points(self.rays_o, self.rays_d, self.z, mn, sz, self.box[2])
+
+    def backward(self, grad_out, weight_feature, grad_blob, grad_table, pose_grads):
+        """The backward of dL/d(out_ray) = grad_out; the record routes emit into grad_table (the gradient table, or the
+        overflow table of a route ending in the sparse Adam), the *_TABLE routes finish into it.  -> (g_o, g_d) with pose_grads."""
+        B, S, dev = self.B, self.S, self.z.device
+        self.arith = backward_arith(True, pose_grads)   # of the plan, the backward and the accumulate alike
+        if self.records and self.ws is None:   # count + scan of the scatter records (depends on the sample positions only)
+            with self._sec("scatter_plan", B * S * 4):
+                self.ws = scatter_plan(self.rays_o, self.rays_d, self.z, self.resolution, self.table.shape[1], *self.box,
+                                       ray_valid=self.valid, arith=self.arith, workspace=self.workspace,
+                                       skip_levels=self.packed.skip_levels)
+        bufs = (torch.zeros(B, (S + 31) // 32, device=dev), torch.zeros(B, 2, 64, device=dev)) if pose_grads else None
+        ray_pos = torch.zeros(B, 6, device=dev) if self.jstash is not None else None
+        # forward recompute + activation gradients + weight gradients = 3x the forward MLP FLOPs (SURVEY.md 8d)
+        counts = (B * (24 + 20 + S * 16 * 8 * 2 * 4 + S * 16 * 8), 3 * B * S * MLP_FLOPS_PER_SAMPLE) if self.sized else ()
+        with _sec(self.timer, "render_backward", *counts):
+            self.dfeat, _ = render_backward(
+                self.rays_o, self.rays_d, self.z, self.dist, self.table, self.resolution, self.packed, weight_feature,
+                *self.box, self.out, self.tile_T, grad_out, ray_valid=self.valid, grad_blob=grad_blob, xstash=self.xstash,
+                ray_grad_buffers=bufs, scatter=(self.ws, grad_table) if self.records else None,
+                want_dfeat=not self.records or (pose_grads and self.jstash is None),
+                arith=self.arith, jstash=self.jstash, ray_pos_grad=ray_pos)
+        g = None
+        if pose_grads and self.jstash is not None:
+            g = ray_gradients_fused(self.rays_o, self.rays_d, self.blob, ray_pos, *bufs, ray_valid=self.valid)
+        elif pose_grads:
+            master = self.master if self.master is not None else self.table.to(_f32)
+            g = ray_gradients(self.rays_o, self.rays_d, self.z, master, self.resolution, self.blob, *self.box[:3], self.dfeat,
+                              *bufs, ray_valid=self.valid)
+        if self.route == RECORDS_TABLE:
+            with self._sec("table_grad_accumulate", B * S * 16 * 64):
+                scatter_accumulate(self.ws, grad_table, B, S, arith=self.arith)
+        elif self.route == POINTS_TABLE:
+            pts = self.points()
+            with self._sec("table_grad_scatter", B * S * 16 * (8 + 16 * 8)):
+                scatter_table_grad(pts, self.dfeat, grad_table, self.resolution, compact_records=self.compact)
+        return g
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Autograd boundary of the fused path: HashGrid.render_batch_rays (hashgrid/__init__.py:512-596) as ONE differentiable op.
 # A caller that keeps the reference's loss code -- depth / smoothness / ADMM penalty terms on the per-ray outputs, summed
 # and sent through loss.backward() (tile.py:954-1011, criterions.py:122-196) -- reaches the fused kernels through it.
@@ -581,6 +729,7 @@ class FusedRenderRays(torch.autograd.Function):
     backward = scanerf_render_backward on an ARBITRARY dL/d(out_ray) [B,16], returning the gradient of the hash table (dense
                [16,T,2]: fused record emission + scanerf_render_scatter_accumulate up to 2^21 entries per level, dfeat + the
                binned scatter above), of the decoder blob [13994] and of rays_o / rays_d.
+    Both run through one _Branch, on table_grad_route's AUTOGRAD row.
     Not differentiated: z_vals / dists (the sampler runs under no_grad in the reference, hashgrid/__init__.py:278-285) and the
     `weights` output (returned for inspection: gradients flowing into it are ignored, as for l2_reg_specular's detached
     weights, hashgrid/__init__.py:593).  The out_ray column W_SPEC2 is differentiated with the weights detached (ibid.)."""
@@ -592,85 +741,50 @@ class FusedRenderRays(torch.autograd.Function):
         dev = z_vals.device
         rays_o, rays_d = rays_o.contiguous(), rays_d.contiguous()
         z_vals, dists = z_vals.contiguous(), dists.contiguous()
-        packed = PackedDecoder(dev).pack(blob.detach().contiguous(), weight_feature.reshape(-1).contiguous(), skip_levels)
+        ctx.wf = weight_feature.reshape(-1).contiguous()
+        packed = PackedDecoder(dev).pack(blob.detach().contiguous(), ctx.wf, skip_levels)
         need_rays = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         need_grad = need_rays or ctx.needs_input_grad[4] or ctx.needs_input_grad[5]
         table = features.detach()
-        tile_T = torch.empty((B, tile_T_columns(S)), dtype=_f32, device=dev) if need_grad else None
-        xstash = torch.empty((B * S, 32), dtype=_f32, device=dev) if need_grad else None
-        jstash = None
-        if need_rays and table.dtype == torch.float32 and ARITH in _capi.T16_FAMILY:
-            jstash = torch.empty(jstash_shape(B, S), dtype=JSTASH_DTYPE, device=dev)
         if ray_valid is not None and ray_valid.dtype not in (torch.bool, torch.uint8):
             raise RuntimeError("scanerf: ray_valid must be bool / uint8")
+        T = table.shape[1]
+        arith = backward_arith(True, need_rays)
+        route = compact = None   # (no table gradient wanted: no route)
+        if ctx.needs_input_grad[4]:
+            (route,), compact = table_grad_route(AUTOGRAD, T, B, [S], arith)
         # The forward launch counts the backward's record ranges (its hash indices are the plan's: no separate count launch, 0.27 ms at
         # configs[1]) where the table gradient will go through the fused records -- into a workspace this call OWNS until its
         # backward has run (other render calls may come between the two and use the per-stream one).
-        T = table.shape[1]
-        from . import tile_model   # (it imports this module)
-        ctx.route = ctx.compact = None   # (no table gradient wanted: no route)
-        if ctx.needs_input_grad[4]:
-            (ctx.route,), ctx.compact = tile_model.table_grad_route(tile_model.AUTOGRAD, T, B, [S], backward_arith(True, need_rays))
-        own_ws = None
-        if (FORWARD_PLAN_IN_AUTOGRAD and ctx.route == tile_model.RECORDS_TABLE and forward_plan_supported(B, S, T)
-                and backward_arith(True, need_rays) in _capi.T16_FAMILY):
-            own_ws = torch.empty(lib().scanerf_render_scatter_workspace_bytes(B, S, T),
-                                 dtype=torch.uint8, device=dev)
-        r = render_forward(rays_o, rays_d, z_vals, dists, table, resolutions, packed, min_bbox, bbox_size, contract_mode,
-                           infinity, ray_valid=ray_valid, want_weights=want_weights, tile_T=tile_T, xstash=xstash, jstash=jstash,
-                           plan=own_ws is not None, plan_workspace=own_ws)
-        ctx.plan_ws, ctx.plan_arith = own_ws, (backward_arith(True, need_rays) if own_ws is not None else None)
-        out, weights = r[0], r[1]
-        ctx.save_for_backward(rays_o, rays_d, z_vals, dists, table, resolutions, weight_feature.reshape(-1).contiguous(), out,
-                              tile_T, xstash, jstash, ray_valid, blob.detach())
-        ctx.packed, ctx.geom = packed, (list(min_bbox), list(bbox_size), int(contract_mode), bool(infinity))
-        if weights is None:
-            weights = out.new_empty(0)
+        ctx.plan_ws = None
+        if (FORWARD_PLAN_IN_AUTOGRAD and route == RECORDS_TABLE and forward_plan_supported(B, S, T)
+                and arith in _capi.T16_FAMILY):
+            ctx.plan_ws = torch.empty(lib().scanerf_render_scatter_workspace_bytes(B, S, T), dtype=torch.uint8, device=dev)
+        br = _Branch(resolutions, packed, blob.detach(), (list(min_bbox), list(bbox_size)), rays_o, rays_d, z_vals, dists, ray_valid,
+                     int(contract_mode), bool(infinity), route, compact, workspace=ctx.plan_ws)
+        out = br.forward(table, plan=ctx.plan_ws is not None, want_weights=want_weights, stash=need_grad,
+                         jstash=need_rays and table.dtype == torch.float32 and ARITH in _capi.T16_FAMILY)
+        # what the launch wrote goes through save_for_backward: freed with the graph, and `out` will carry this node
+        ctx.save_for_backward(out, br.tile_T, br.xstash, br.jstash)
+        br.out = br.tile_T = br.xstash = br.jstash = None
+        ctx.branch = br
+        weights = br.weights if br.weights is not None else out.new_empty(0)
         ctx.mark_non_differentiable(weights)
         return out, weights
 
     @staticmethod
     def backward(ctx, grad_out, _grad_weights):
-        (rays_o, rays_d, z_vals, dists, table, resolutions, wf, out, tile_T, xstash, jstash, ray_valid, blob) = ctx.saved_tensors
-        B, S = z_vals.shape
-        dev = z_vals.device
-        T = table.shape[1]
-        box = ctx.geom
+        br = ctx.branch
+        dev = br.z.device
         need_rays = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        need_table = ctx.needs_input_grad[4]
         grad_out = grad_out.contiguous().to(_f32)
-        arith = backward_arith(True, need_rays)
-        from . import tile_model
-        fused = ctx.route == tile_model.RECORDS_TABLE
-        gtab = torch.zeros((16, T, 2), dtype=_f32, device=dev) if need_table else None
+        gtab = torch.zeros((16, br.table.shape[1], 2), dtype=_f32, device=dev) if ctx.needs_input_grad[4] else None
         gblob = torch.zeros(_capi.PARAMSIZE, dtype=_f32, device=dev)
-        ws = None
-        if fused and ctx.plan_ws is not None and ctx.plan_arith == arith:
-            ws = ctx.plan_ws   # (counted by the forward launch)
-        elif fused:   # (count + scan here, on the per-stream workspace: plan, backward and accumulate run back to back)
-            ws = scatter_plan(rays_o, rays_d, z_vals, resolutions, T, *box, ray_valid=ray_valid, arith=arith,
-                              skip_levels=ctx.packed.skip_levels)
-        ntile = (S + 31) // 32
-        bufs = (torch.zeros(B, ntile, device=dev), torch.zeros(B, 2, 64, device=dev)) if need_rays else None
-        rp = torch.zeros(B, 6, device=dev) if (need_rays and jstash is not None) else None
-        dfeat, _ = render_backward(rays_o, rays_d, z_vals, dists, table, resolutions, ctx.packed, wf, *box, out, tile_T,
-                                   grad_out, ray_valid=ray_valid, grad_blob=gblob, xstash=xstash, ray_grad_buffers=bufs,
-                                   scatter=(ws, gtab) if fused else None, want_dfeat=not fused or (need_rays and jstash is None),
-                                   arith=arith, jstash=jstash, ray_pos_grad=rp)
-        g_o = g_d = None
-        if need_rays and jstash is not None:
-            g_o, g_d = ray_gradients_fused(rays_o, rays_d, blob, rp, bufs[0], bufs[1], ray_valid=ray_valid)
-        elif need_rays:
-            g_o, g_d = ray_gradients(rays_o, rays_d, z_vals, table.to(_f32), resolutions, blob, box[0], box[1], box[2], dfeat,
-                                     bufs[0], bufs[1], ray_valid=ray_valid)
-        if fused:
-            scatter_accumulate(ws, gtab, B, S, arith=arith)
-        elif need_table:
-            pts = contracted_points(rays_o, rays_d, z_vals, torch.as_tensor(box[0], dtype=_f32, device=dev),
-                                    torch.as_tensor(box[1], dtype=_f32, device=dev), box[2])
-            scatter_table_grad(pts, dfeat, gtab, resolutions, compact_records=ctx.compact)
-        if gtab is not None and table.dtype != _f32:
-            gtab = gtab.to(table.dtype)
+        br.out, br.tile_T, br.xstash, br.jstash = ctx.saved_tensors
+        g_o, g_d = br.backward(grad_out, ctx.wf, gblob, gtab, need_rays) or (None, None)
+        br.out = br.tile_T = br.xstash = br.jstash = None
+        if gtab is not None and br.table.dtype != _f32:
+            gtab = gtab.to(br.table.dtype)
         return (g_o if ctx.needs_input_grad[0] else None, g_d if ctx.needs_input_grad[1] else None, None, None, gtab,
                 gblob if ctx.needs_input_grad[5] else None, None, None, None, None, None, None, None, None, None)
 

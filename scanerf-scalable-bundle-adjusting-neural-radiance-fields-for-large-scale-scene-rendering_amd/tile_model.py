@@ -22,22 +22,10 @@ import torch.nn.functional as F
 from . import network, render
 from .cuda import adam_step_cuda, sample_points_grid
 from .hashgrid import HashEmbeddingBG, level_resolutions
-
-_C1 = 0.4886025119029199
-_C2 = (1.0925484305920792, -1.0925484305920792, 0.31539156525252005, -1.0925484305920792, 0.5462742152960396)
-_C3 = (-0.5900435899266435, 2.890611442640554, -0.4570457994644658, 0.3731763325901154, -0.4570457994644658,
-       1.445305721320277, -0.5900435899266435)
-
-
-def sh3(v):
-    """Real spherical harmonics up to degree 3 of unit vectors (16 values, network.py:38-77 ordering)."""
-    x, y, z = v.unbind(-1)
-    xx, yy, zz, xy, yz, xz = x * x, y * y, z * z, x * y, y * z, x * z
-    return torch.stack([torch.full_like(x, 0.28209479177387814), _C1 * y, _C1 * z, _C1 * x, _C2[0] * xy, _C2[1] * yz,
-                        _C2[2] * (2.0 * zz - xx - yy), _C2[3] * xz, _C2[4] * (xx - yy), _C3[0] * y * (3 * xx - yy),
-                        _C3[1] * xy * z, _C3[2] * y * (4 * zz - xx - yy), _C3[3] * z * (2 * zz - 3 * xx - 3 * yy),
-                        _C3[4] * x * (4 * zz - xx - yy), _C3[5] * z * (xx - yy), _C3[6] * x * (xx - 3 * yy)], -1)
-
+from .network import sh3
+# the branch pass, its timer sections and the table-gradient routes live with the kernels' wrappers
+from .render import (_TABLE_ROUTES, AUTOGRAD, FGBG_GRADIENTS, FGBG_STEP, MLP_FLOPS_PER_SAMPLE, POINTS_ADAM, POINTS_TABLE,  # noqa: F401
+                     RAYS_ADAM, RECORDS_ADAM, RECORDS_TABLE, SINGLE, _Branch, _sec)
 
 def composite_weights(sigma, dists, rays_d, infinity):
     """Alpha compositing weights of hashgrid/__init__.py:344-360 in torch: delta = dists * |d| (last sample 1e10 for a background
@@ -438,21 +426,6 @@ class KernelTimer:
         return name, cand[name], self.bytes[name], self.flops.get(name, 0)
 
 
-class _Null:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
-
-
-def _sec(timer, name, alg_bytes=0, alg_flops=0):
-    return timer.section(name, alg_bytes, alg_flops) if timer is not None else _Null()
-
-
-MLP_FLOPS_PER_SAMPLE = 2 * 13728  # 27 456 FLOP per sample forward
-
-
 def train_step_ops(model, dec_opt, rays_o, rays_d, target, S, global_step, table_lr=1e-2, timer=None):
     """One iteration of tile.py:880-1015 on the foreground branch: MSE + 0.01*l2_reg_specular
     (criterions.py:142-144, tile.py:999), decoder by torch Adam, table by the fused sparse Adam."""
@@ -480,56 +453,10 @@ FORWARD_PLAN = True         # the forward launch counts the backward's record ra
 LEVEL_SKIP = True           # levels whose coarse-to-fine weight is exactly zero are left out of gathers and records (same results)
 JSTASH = True               # pose gradients: the forward stashes the encoder's position Jacobians for the backward
 
-# Table-gradient routes (table_grad_route):
-RECORDS_ADAM = "records_adam"    # the backward kernel emits the records; accumulate + sparse Adam (adam2 for two branches)
-RECORDS_TABLE = "records_table"  # the backward kernel emits the records; accumulate into a gradient table
-RAYS_ADAM = "rays_adam"          # dfeat -> scatter_table_grad_adam_rays (places the samples itself; large tables)
-POINTS_ADAM = "points_adam"      # dfeat at contracted points built in torch -> scatter_table_grad_adam
-POINTS_TABLE = "points_table"    # dfeat at contracted points -> scatter_table_grad into a gradient table (then table_adam)
-_TABLE_ROUTES = (RECORDS_TABLE, POINTS_TABLE)
-# ... and the entry points asking for one
-SINGLE, FGBG_STEP, FGBG_GRADIENTS, AUTOGRAD = "single", "fgbg_step", "fgbg_gradients", "autograd"
-
 
 def table_grad_route(entry, T, B, S, arith, half_table=False, fused_adam=True, fused_scatter=None):
-    """How a training step's feature gradients reach the table -> (routes: one per branch sample count in S, the
-    `compact_records` of a contracted-points scatter).  Pure: no allocation, no launch.  arith: the backward's arithmetic;
-    half_table: a half-precision gather copy is resident.  Each entry point keeps the choice it made before this was one place
-    (tests/test_table_grad_route_cpu.py gives each row's reason):
-      SINGLE: records where fused_scatter (default: T <= 2^21 or LARGE_T_ROUTE "fused") and the workspace allow, f32 included;
-        else rays / points ending in the Adam, or with fused_adam=False points into a gradient table (compact above 2^21 only);
-      FGBG_STEP: records + adam2 as SINGLE but never under f32; above 2^21 (not f32, no half table) ONE rays / points scatter
-        over both branches; else FGBG_GRADIENTS' gradient table;
-      FGBG_GRADIENTS: per branch, records into the table at T <= 2^21 (LARGE_T_ROUTE ignored), else points with -1;
-      AUTOGRAD (only asked when the table needs a gradient): records at T <= 2^21, else points with -1."""
-    # records emitted by the backward kernel need the level's cursors in ITS LDS (256 buckets per level): above 2^21 entries
-    # they outgrow the accumulate's LDS image.  The split pass in front of the accumulate (csrc/scatter.hip k_bin_split) serves
-    # larger tables, but the stand-alone scatter from dfeat (2^13-entry buckets) is still ahead there (T = 2^24, 16 384 rays:
-    # 5.6 against 6.1 ms per step): LARGE_T_ROUTE = "fused" selects the split pass
-    small = T <= (1 << 21)
-    records = all(render.scatter_supported(B, s, T) for s in S)
-    compact = render.compact_record_format(arith)
-    if entry == SINGLE:
-        if fused_scatter is None:
-            fused_scatter = small or LARGE_T_ROUTE == "fused"
-        if fused_scatter and records:
-            route = RECORDS_ADAM if fused_adam else RECORDS_TABLE
-        elif not fused_adam:
-            route, compact = POINTS_TABLE, (-1 if small else compact)
-        else:
-            route = RAYS_ADAM if render.scatter_rays_supported(T, arith) and not half_table else POINTS_ADAM
-        return (route,), compact
-    if entry == FGBG_STEP:
-        if (small or LARGE_T_ROUTE == "fused") and records and arith != render._capi.ARITH_F32:
-            return (RECORDS_ADAM,) * len(S), compact
-        if not small and arith != render._capi.ARITH_F32 and not half_table:
-            return (RAYS_ADAM if render.scatter_rays_supported(T, arith) else POINTS_ADAM,) * len(S), compact
-        entry = FGBG_GRADIENTS
-    if entry == FGBG_GRADIENTS:
-        return tuple(RECORDS_TABLE if small and render.scatter_supported(B, s, T) else POINTS_TABLE for s in S), -1
-    if entry == AUTOGRAD:
-        return (RECORDS_TABLE if small and records else POINTS_TABLE,), -1
-    raise ValueError(f"table_grad_route: unknown entry point {entry!r}")
+    """render.table_grad_route under this module's LARGE_T_ROUTE (only the steps' rows read it)."""
+    return render.table_grad_route(entry, T, B, S, arith, half_table, fused_adam, fused_scatter, LARGE_T_ROUTE)
 
 
 def _forward_plans(B, S, T):
@@ -539,79 +466,10 @@ def _forward_plans(B, S, T):
             and FORWARD_PLAN)
 
 
-class _Branch:
-    """One render branch of a training step on the fused kernels: the forward with its stashes, the record plan of the
-    table-gradient route, the backward and the ray gradients.  sized=False (fgbg_gradients): only the backward is a timer
-    section, without byte and FLOP counts; workspace: the branch's own record workspace (default: the per-stream one)."""
-
-    def __init__(self, model, rays_o, rays_d, z, dist, valid, mode, infinity, route, compact, timer=None, sized=True,
-                 workspace=None):
-        self.model, self.rays_o, self.rays_d, self.z, self.dist, self.valid = model, rays_o, rays_d, z, dist, valid
-        self.box = (model.min_bbox.tolist(), model.bbox_size.tolist(), mode, infinity)
-        self.route, self.compact, self.timer, self.sized, self.workspace = route, compact, timer, sized, workspace
-        self.records = route in (RECORDS_ADAM, RECORDS_TABLE)
-        self.B, self.S = z.shape
-        self.ws = self.jstash = self.dfeat = self.arith = None
-
-    def _sec(self, name, *counts):
-        return _sec(self.timer if self.sized else None, name, *counts)
-
-    def forward(self, table, plan=False, jstash=False):
-        """plan: the launch also reserves the backward's record ranges (_forward_plans); jstash: it stashes the encoder's
-        position Jacobians, so that the backward chains the feature gradients to the rays without a second pass over the table."""
-        m, B, S = self.model, self.B, self.S
-        self.table = table
-        self.tile_T = torch.empty((B, render.tile_T_columns(S)), device=m.device)
-        self.xstash = torch.empty((B * S, 32), device=m.device)  # encoder outputs: 1 GB at 65 536 x 128, saves the re-gather
-        if jstash:
-            self.jstash = torch.empty(render.jstash_shape(B, S), dtype=render.JSTASH_DTYPE, device=m.device)
-        with self._sec("render_forward", B * (24 + 20 + S * 16 * 8 * 2 * table.element_size()), B * S * MLP_FLOPS_PER_SAMPLE):
-            r = render.render_forward(self.rays_o, self.rays_d, self.z, self.dist, table, m.resolution, m.packed, *self.box,
-                                      ray_valid=self.valid, want_weights=False, tile_T=self.tile_T, xstash=self.xstash,
-                                      plan=plan, plan_workspace=self.workspace, jstash=self.jstash)
-        if plan:
-            self.ws = r[2]
-        self.out = r[0]
-        return self.out
-
-    def points(self):
-        return render.contracted_points(self.rays_o, self.rays_d, self.z, self.model._min_dev, self.model._size_dev, self.box[2])
-
-    def backward(self, grad_out, weight_feature, grad_blob, grad_table, pose_grads):
-        """The backward of dL/d(out_ray) = grad_out; the record routes emit into grad_table (the gradient table, or the
-        overflow table of a route ending in the sparse Adam), the *_TABLE routes finish into it.  -> (g_o, g_d) with pose_grads."""
-        m, B, S = self.model, self.B, self.S
-        bufs = (torch.zeros(B, (S + 31) // 32, device=m.device), torch.zeros(B, 2, 64, device=m.device)) if pose_grads else None
-        ray_pos = torch.zeros(B, 6, device=m.device) if self.jstash is not None else None
-        self.arith = render.backward_arith(True, pose_grads)   # of the plan, the backward and the accumulate alike
-        if self.records and self.ws is None:   # count + scan of the scatter records (depends on the sample positions only)
-            with self._sec("scatter_plan", B * S * 4):
-                self.ws = render.scatter_plan(self.rays_o, self.rays_d, self.z, m.resolution, m.features.shape[1], *self.box,
-                                              ray_valid=self.valid, arith=self.arith,
-                                              workspace=self.workspace, skip_levels=m.packed.skip_levels)
-        # forward recompute + activation gradients + weight gradients = 3x the forward MLP FLOPs (SURVEY.md 8d)
-        counts = (B * (24 + 20 + S * 16 * 8 * 2 * 4 + S * 16 * 8), 3 * B * S * MLP_FLOPS_PER_SAMPLE) if self.sized else ()
-        with _sec(self.timer, "render_backward", *counts):
-            self.dfeat, _ = render.render_backward(
-                self.rays_o, self.rays_d, self.z, self.dist, self.table, m.resolution, m.packed, weight_feature,
-                *self.box, self.out, self.tile_T, grad_out, ray_valid=self.valid, grad_blob=grad_blob, xstash=self.xstash,
-                ray_grad_buffers=bufs, scatter=(self.ws, grad_table) if self.records else None,
-                want_dfeat=not self.records or (pose_grads and self.jstash is None),
-                arith=self.arith, jstash=self.jstash, ray_pos_grad=ray_pos)
-        g = None
-        if pose_grads and self.jstash is not None:
-            g = render.ray_gradients_fused(self.rays_o, self.rays_d, m.decoder.blob(), ray_pos, *bufs, ray_valid=self.valid)
-        elif pose_grads:
-            g = render.ray_gradients(self.rays_o, self.rays_d, self.z, m.features, m.resolution, m.decoder.blob(), *self.box[:3],
-                                     self.dfeat, *bufs, ray_valid=self.valid)
-        if self.route == RECORDS_TABLE:
-            with self._sec("table_grad_accumulate", B * S * 16 * 64):
-                render.scatter_accumulate(self.ws, grad_table, B, S, arith=self.arith)
-        elif self.route == POINTS_TABLE:
-            pts = self.points()
-            with self._sec("table_grad_scatter", B * S * 16 * (8 + 16 * 8)):
-                render.scatter_table_grad(pts, self.dfeat, grad_table, m.resolution, compact_records=self.compact)
-        return g
+def _branch(model, *args, **kwargs):
+    """render._Branch on the model's grid, decoder and 2x box; point gradients read the fp32 master."""
+    return _Branch(model.resolution, model.packed, model.decoder.blob(), (model.min_bbox.tolist(), model.bbox_size.tolist()), *args,
+                   master=model.features, box_dev=(model._min_dev, model._size_dev), **kwargs)
 
 
 def _table_grad_adam(model, route, compact, rays_o, rays_d, branches, lr, timer):
@@ -691,7 +549,7 @@ def train_step_fused(model, dec_opt, rays_o, rays_d, target, S, global_step, tab
         T = model.features.shape[1]
         (route,), compact = table_grad_route(SINGLE, T, B, [S], render.backward_arith(True, pose_grads),
                                              model._half_table is not None, fused_adam, fused_scatter)
-        br = _Branch(model, rays_o, rays_d, z, dist, valid, render.FORE, False, route, compact, timer)
+        br = _branch(model, rays_o, rays_d, z, dist, valid, render.FORE, False, route, compact, timer)
         plan = br.records and _forward_plans(B, S, T)
         out = br.forward(table, plan, jstash=plan and pose_grads and table.dtype == torch.float32 and JSTASH)
     # loss and dL/d(out_ray) in two launches (the torch graph for it was ~60 tiny kernels with host-bound gaps)
@@ -776,8 +634,8 @@ def _fgbg_pass(model, rays_o, rays_d, target, S_fg, S_bg, global_step, invalid_u
             if getattr(model, "_ws_bg", None) is None or model._ws_bg.numel() < need_bg:
                 model._ws_bg = torch.empty(need_bg, dtype=torch.uint8, device=dev)
             ws_bg = model._ws_bg
-        branches = (_Branch(model, rays_o, rays_d, z, dist, vf, render.FORE, False, routes[0], compact, timer, fused),
-                    _Branch(model, rays_o, rays_d, zb, db, vb, render.BG, True, routes[1], compact, timer, fused, ws_bg))
+        branches = (_branch(model, rays_o, rays_d, z, dist, vf, render.FORE, False, routes[0], compact, timer, fused),
+                    _branch(model, rays_o, rays_d, zb, db, vb, render.BG, True, routes[1], compact, timer, fused, ws_bg))
         for b in branches:
             b.forward(table, plan=fused and _forward_plans(B, b.S, T), jstash=pose_grads)
     # merge and loss on the per-ray outputs (tile.py:666-690; criterions.py:142-144; tile.py:999), two HIP launches
