@@ -631,6 +631,43 @@ int scanerf_render_normals(const float *rays_o, const float *rays_d, const float
                            const uint8_t *ray_valid, float *out, float *sample_normals, int B, int S, int T,
                            scanerf_stream_t stream);
 
+/* ---- normal maps of the multi-tile render (csrc/render_normals_tiles.hip).  The reference has no multi-tile
+ *   normal; the definition is this comment.  Normals are blended exactly as scanerf_pts_inference blends colours
+ *   (rendering_kernel.cu:467-581).  For sample t of ray i with slot list block_idxs[t][0..3] (int16; -1 ends the list), each listed
+ *   tile b in turn, in float32:
+ *     pts = (o + z d - corner_b) / size_b (corner / size of the render box);  dis = (0.5 - |pts - 0.5|) size_b;
+ *     w_b = xz_weight(dis.x, dis.z), counted in W = sum_b w_b whether or not the cell is occupied;
+ *     the tile contributes only if its occupancy cell (scanerf_pts_inference's loc / cell offset) is set; then
+ *       p01 = pts / 2 + 0.25;  per level v = p01 (res - 1), i0 = int(v), t = v - i0 (scanerf_pts_inference's expression: a sample's
+ *       normal and colour read the same cells);  tables f16, read as exported;  density and gradient by the closed form above with
+ *       weight_feature == 1 and the contracted coordinate x = 2 pts - 1 (A = 2 / size_b per axis):  g_b = d sigma_b / d world
+ *       position,  n_b = -g_b / (|g_b| + 1e-8);  pa_b = 1 - exp(-sigma_b dist |d|), |d| of the un-normalised direction;
+ *     pts_normal[t] = sum_b w_b pa_b n_b (summed in slot order), divided by W when W > 0.
+ *   Samples with no listed tile (z == -1 among them) give exactly (0, 0, 0).  EVERY sample is written.  blobs: the flat decoder blobs
+ *   [nb][SCANERF_PARAMSIZE] (not packed images); resolution [nb,16,3]; tables_f16 [nb,16,T,2]; occ / grid_starts / log2dim / corners /
+ *   sizes as scanerf_pts_inference.  pts_normal [B,S,3] and the per-sample inputs in the layout `sample_major` (0, 1 or 2, no flag
+ *   bits).  Any nb that fits the int16 slots; B * S < 2^31.  Deterministic; a sample's bits do not depend on the layout. */
+int scanerf_pts_normals(const float *rays_o, const float *rays_d, const float *z_vals, const float *dists, const int16_t *block_idxs,
+                        const void *tables_f16, const float *blobs, const int32_t *resolution, const uint8_t *occ,
+                        const int64_t *grid_starts, const int32_t *log2dim, const float *corners, const float *sizes,
+                        float *pts_normal, int B, int S, int T, int nb, int sample_major, scanerf_stream_t stream);
+/* The same launch with four counters added into counts [4] u32 (caller-zeroed): [0] 64-sample groups that ran at least one tile,
+ *   [1] stagings of a tile's operands in LDS, [2] passes of the per-tile loop (one gather and first-layer product of a whole wave
+ *   each), [3] lanes that held a sample in those passes.  Measurement entry point (tools/bench_render_normals.py). */
+int scanerf_pts_normals_counted(const float *rays_o, const float *rays_d, const float *z_vals, const float *dists,
+                                const int16_t *block_idxs, const void *tables_f16, const float *blobs, const int32_t *resolution,
+                                const uint8_t *occ, const int64_t *grid_starts, const int32_t *log2dim, const float *corners,
+                                const float *sizes, float *pts_normal, unsigned int *counts, int B, int S, int T, int nb,
+                                int sample_major, scanerf_stream_t stream);
+/* Per-ray accumulation by scanerf_accumulate_color's rule: a ray whose transparency is < 1e-5 is skipped; otherwise per sample, in
+ *   order, normal += T pts_normal[t], T <- T (1 - pts_alpha[t]), T starting at the ray's transparency, pts_alpha as
+ *   scanerf_pts_inference wrote it.  transparency [B] is read, not written: run this BEFORE scanerf_accumulate_color of the same pass.
+ *   normal [B,3] is added into (the raw accumulated vector, world coordinates; foreground only; a display mapping (n + 1) / 2 stays
+ *   with the caller).  SCANERF_SKIP_UNSAMPLED OR-ed into sample_major: a ray whose first depth is -1 is not read (its pts_alpha is
+ *   uninitialised memory behind scanerf_pts_inference_tracing). */
+int scanerf_accumulate_normal(const float *pts_normal, const float *pts_alpha, const float *transparency, const float *z_vals,
+                              float *normal, int B, int S, int sample_major, scanerf_stream_t stream);
+
 #define SCANERF_RAY_OUT 16
 
 #ifdef __cplusplus

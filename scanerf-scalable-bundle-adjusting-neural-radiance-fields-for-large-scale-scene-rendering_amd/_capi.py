@@ -106,6 +106,9 @@ PROTOTYPES = {
     "scanerf_view_coverage": ("I", "PPIIIIPPIPPPPPPPPIPP", REQ),
     "scanerf_sigma_normals_points": ("I", "PPPIPPPPPPIIP", REQ),
     "scanerf_render_normals": ("I", "PPPPPIPPPPPIPPPIIIP", REQ),
+    "scanerf_pts_normals": ("I", "PPPPPPPPPPPPPPIIIIIP", REQ),
+    "scanerf_pts_normals_counted": ("I", "PPPPPPPPPPPPPPPIIIIIP", OPT),
+    "scanerf_accumulate_normal": ("I", "PPPPPIIIP", REQ),
 }
 SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if required]
 OPTIONAL_SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if not required]

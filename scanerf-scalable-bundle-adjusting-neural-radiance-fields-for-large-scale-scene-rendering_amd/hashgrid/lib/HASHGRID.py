@@ -5,7 +5,7 @@ hashgrid/include/rendering.h:20-182 (the render-time ops of rendering.py's novel
 """
 import torch
 
-from ..._capi import check, dev_ptr, feat_dtype_code, lib, stream, workspace
+from ..._capi import check, dev_ptr, feat_dtype_code, has_symbol, lib, stream, workspace
 
 _f32, _i32 = torch.float32, torch.int32
 _feat = (torch.float32, torch.float16, torch.bfloat16)
@@ -256,6 +256,74 @@ def pts_inference_tracing(rays_o, rays_d, z_vals, dists, running_mask, intersect
         dev_ptr(diffuse, _f32, "diffuse"), dev_ptr(specular, _f32, "specular"), dev_ptr(alpha, _f32, "alpha"),
         rays_d.shape[0], _S(z_vals, sample_major), features_tables.shape[2], block_corners.shape[0],
         int(sample_major) | _infer_flags(folded), stream()), "pts_inference_tracing")
+
+
+def _layout_shape(name, t, sample_major, B, S, tail):
+    """`t` is a per-sample array of B rays x S samples in the layout `sample_major` (scanerf_hip.h), `tail` trailing dimensions."""
+    lay = int(sample_major) & 3
+    if lay == 2 and B % 32:
+        raise RuntimeError(f"scanerf: sample_major=2 needs B a multiple of 32, got B={B}")
+    want = {0: (B, S), 1: (S, B), 2: (B // 32, S, 32)}[lay] + tuple(tail)
+    if tuple(t.shape) != want and not (tail == (1,) and tuple(t.shape) == want[:-1]):
+        raise RuntimeError(f"scanerf: {name} has shape {tuple(t.shape)}, expected {want} (sample_major={lay})")
+
+
+def pts_normals(rays_o, rays_d, z_vals, dists, block_idxs, features_tables, params, resolution, grid_occupied, grid_starts,
+                grid_log2dim, block_corners, block_sizes, pts_normal, sample_major=False, counts=None):
+    """Blended per-sample normals of the multi-tile render (include/scanerf_hip.h scanerf_pts_normals; no reference counterpart):
+    pts_normal [B,S,3] in the layout, every sample written.  params: the raw decoder blobs [nb, 13994] (or a PackedDecoders, whose
+    blobs are read).  counts: a zeroed int32 [4] tensor -> the counted launch (groups that ran a tile, stagings, passes of the tile loop, lanes
+    that held a sample in them)."""
+    if isinstance(params, PackedDecoders):
+        params = params.params
+    nb = block_corners.shape[0]
+    if params.dim() != 2 or tuple(params.shape) != (nb, 13994):
+        raise RuntimeError(f"scanerf: decoder blobs must be [{nb}, 13994], got {tuple(params.shape)}")
+    lay = int(sample_major)
+    if lay not in (0, 1, 2):
+        raise RuntimeError(f"scanerf: pts_normals takes sample_major 0, 1 or 2 (no flag bits), got {sample_major}")
+    B, S = rays_d.shape[0], _S(z_vals, lay)
+    _layout_shape("z_vals", z_vals, lay, B, S, ())
+    _layout_shape("dists", dists, lay, B, S, ())
+    _layout_shape("block_idxs", block_idxs, lay, B, S, (4,))
+    _layout_shape("pts_normal", pts_normal, lay, B, S, (3,))
+    if features_tables.dim() != 4 or features_tables.shape[0] != nb or tuple(features_tables.shape[1::2]) != (16, 2):
+        raise RuntimeError(f"scanerf: features_tables must be [{nb}, 16, T, 2], got {tuple(features_tables.shape)}")
+    if tuple(resolution.shape) != (nb, 16, 3):
+        raise RuntimeError(f"scanerf: resolution must be [{nb}, 16, 3], got {tuple(resolution.shape)}")
+    args = (dev_ptr(rays_o, _f32, "rays_o"), dev_ptr(rays_d, _f32, "rays_d"), dev_ptr(z_vals, _f32, "z_vals"),
+            dev_ptr(dists, _f32, "dists"), dev_ptr(block_idxs, _i16, "block_idxs"),
+            dev_ptr(features_tables, torch.float16, "features_tables"), dev_ptr(params, _f32, "params"),
+            dev_ptr(resolution, _i32, "resolution"), dev_ptr(grid_occupied, _bool, "grid_occupied"),
+            dev_ptr(grid_starts, _i64, "grid_starts"), dev_ptr(grid_log2dim, _i32, "grid_log2dim"),
+            dev_ptr(block_corners, _f32, "block_corners"), dev_ptr(block_sizes, _f32, "block_sizes"),
+            dev_ptr(pts_normal, _f32, "pts_normal"))
+    tail = (B, S, features_tables.shape[2], nb, lay, stream())
+    if counts is None:
+        check(lib().scanerf_pts_normals(*args, *tail), "pts_normals")
+        return
+    if not has_symbol("scanerf_pts_normals_counted"):
+        raise RuntimeError("scanerf: this build does not export scanerf_pts_normals_counted (a measurement entry point)")
+    if counts.numel() != 4:
+        raise RuntimeError(f"scanerf: counts must hold 4 int32, got {tuple(counts.shape)}")
+    check(lib().scanerf_pts_normals_counted(*args, dev_ptr(counts, _i32, "counts"), *tail), "pts_normals_counted")
+
+
+def accumulate_normal(pts_normal, pts_alpha, transparency, z_vals, normal, sample_major=False):
+    """accumulate_color's rule for the normal (include/scanerf_hip.h scanerf_accumulate_normal): normal [B,3] is added into,
+    transparency [B,1] is read only -- call it BEFORE accumulate_color of the same pass."""
+    sm = int(sample_major)
+    if sm & ~(3 | SKIP_UNSAMPLED) or (sm & 3) == 3:
+        raise RuntimeError(f"scanerf: accumulate_normal takes sample_major 0, 1 or 2, optionally | SKIP_UNSAMPLED, got {sample_major}")
+    B, S = transparency.shape[0], _S(z_vals, sm)
+    _layout_shape("z_vals", z_vals, sm, B, S, ())
+    _layout_shape("pts_alpha", pts_alpha, sm, B, S, (1,))
+    _layout_shape("pts_normal", pts_normal, sm, B, S, (3,))
+    if tuple(normal.shape) != (B, 3) or transparency.numel() != B:
+        raise RuntimeError(f"scanerf: normal must be [{B}, 3] and transparency [{B}] or [{B}, 1], got {tuple(normal.shape)}, {tuple(transparency.shape)}")
+    check(lib().scanerf_accumulate_normal(
+        dev_ptr(pts_normal, _f32, "pts_normal"), dev_ptr(pts_alpha, _f32, "pts_alpha"), dev_ptr(transparency, _f32, "transparency"),
+        dev_ptr(z_vals, _f32, "z_vals"), dev_ptr(normal, _f32, "normal"), B, S, sm, stream()), "accumulate_normal")
 
 
 def accumulate_color(pts_diffuse, pts_specular, pts_alpha, transparency, z_vals, diffuse, specular, depth, sample_major=False):

@@ -5,6 +5,7 @@ tile export / load formats it consumes (hashgrid/__init__.py:248-257 feature.npz
 Per view: compute_ray_forward -> ray_block_intersection -> argsort(near) -> per tracing step
 {sample_points -> prepare_points -> pts_inference -> accumulate_color} -> update_outgoing_bidx ->
 per blended background {inverse_z_sampling -> bg_pts_inference_v2 -> accumulate_color} -> merge.
+With normals=True each tracing step also runs pts_normals -> accumulate_normal (no reference counterpart: include/scanerf_hip.h).
 """
 import os
 
@@ -14,9 +15,9 @@ import torch
 from . import network
 from .cuda import compute_ray_forward
 from .hashgrid.lib import HASHGRID as _HG
-from .hashgrid import (accumulate_color, bg_pts_inference_v2, inverse_z_sampling, prepare_points, process_occupied_grid,
-                       SKIP_UNSAMPLED, pts_inference, pts_inference_tracing, ray_block_intersection, sample_points, sort_tracing_blocks,
-                       tracing_fusable, update_outgoing_bidx)
+from .hashgrid import (accumulate_color, accumulate_normal, bg_pts_inference_v2, inverse_z_sampling, prepare_points,
+                       process_occupied_grid, SKIP_UNSAMPLED, pts_inference, pts_inference_tracing, pts_normals, ray_block_intersection,
+                       sample_points, sort_tracing_blocks, tracing_fusable, update_outgoing_bidx)
 
 
 def write_feature_npz(path, features, occupied_grid, min_bbox, bbox_size, log2dim, resolution):
@@ -93,8 +94,12 @@ class TileSetRenderer:
 
     @torch.no_grad()
     def render_rays(self, rays_o, rays_d, num_sample=128, num_bg_sample=128, sample_range=1e6, layout=2,
-                    skip_saturated_background=False):
-        """skip_saturated_background: False (default) = the reference's behaviour, every ray gets its blended background
+                    skip_saturated_background=False, normals=False):
+        """-> (diffuse [B,3], specular [B,3], depth [B,1], transparency [B,1]); normals=True adds a fifth tensor, normal [B,3]: the
+        tiles' density normals blended per sample as the colours are and accumulated with the foreground's transmittance (raw vector
+        in world coordinates, foreground only, not normalised; the display mapping (n + 1) / 2 stays with the caller).  The four
+        colour outputs are the same bits either way.
+        skip_saturated_background: False (default) = the reference's behaviour, every ray gets its blended background
         (rendering.py:534-536); True = rays whose foreground transmittance is <= 1e-5 (the threshold at which rendering.py:356
         stops tracing them) get none: colour changes by <= 1e-5, but the returned DEPTH loses transparency * bg_depth, which can
         reach ~1e-5 * sample_range = 10 units (tests/test_gpu_render_time.py bounds both).
@@ -130,29 +135,43 @@ class TileSetRenderer:
         pd = torch.empty(shp(num_sample, 3), device=dev)
         ps = torch.empty(shp(num_sample, 3), device=dev)
         pa = torch.empty(shp(num_sample, 1), device=dev)
+        normal = torch.zeros(B, 3, device=dev) if normals else None
+        pn = torch.empty(shp(num_sample, 3), device=dev) if normals else None
 
         fuse_slots = tracing_fusable(nb) and not single_pass and self.fuse_slots
 
-        def fg_pass(ro, rd, it, tb, tidx, zst, tr, df, sp, dp, running, pd, ps, pa):
-            """One tracing pass (rendering.py:356-420) over the rays given: per-ray state tidx / zst / tr / df / sp / dp updated in place."""
+        def fg_pass(ro, rd, it, tb, tidx, zst, tr, df, sp, dp, running, pd, ps, pa, nm=None, pn=None):
+            """One tracing pass (rendering.py:356-420) over the rays given: per-ray state tidx / zst / tr / df / sp / dp (and the
+            normal nm, when asked for) updated in place."""
             n = ro.shape[0]
             shp_ = {0: lambda S, *tail: (n, S, *tail), 1: lambda S, *tail: (S, n, *tail), 2: lambda S, *tail: (n // 32, S, 32, *tail)}[lay]
             z = torch.full(shp_(num_sample), -1.0, device=dev)
             dd = torch.full(shp_(num_sample), -1.0, device=dev)
             sample_points(ro, rd, self.block_corner, self.block_size, self.fake_occupied_grid, self.grid_starts,
                           self.grid_log2dim, tb, it, tidx, zst, z, dd, sample_major=sm)
+            bi = None
+            if nm is not None:   # the normals read slot lists, on either colour route (which stays what it would have been)
+                bi = torch.full(shp_(num_sample, 4), -1, dtype=torch.int16, device=dev)
+                prepare_points(z, running, it, bi, sample_major=sm)
+                pts_normals(ro, rd, z, dd, bi, self.feature_tables, self.params, self.resolution, self.occupied_grid,
+                            self.grid_starts, self.grid_log2dim, self.block_corner, self.block_size, pn, sample_major=sm)
             if fuse_slots:   # the slot lists never exist: the inference kernel derives them (pts_inference_tracing); rays that
                 # got no sample in this pass (first depth -1) are neither written by it nor read by the accumulation
                 pts_inference_tracing(ro, rd, z, dd, running, it, self.feature_tables, self.packed, self.resolution, self.occupied_grid,
                                       self.grid_starts, self.grid_log2dim, self.block_corner, self.block_size, pd, ps, pa,
                                       sample_major=sm | SKIP_UNSAMPLED)
+                if nm is not None:   # (before accumulate_color, which advances the transparency both read)
+                    accumulate_normal(pn, pa, tr, z, nm, sample_major=sm | SKIP_UNSAMPLED)
                 accumulate_color(pd, ps, pa, tr, z, df, sp, dp, sample_major=sm | SKIP_UNSAMPLED)
                 return
             else:
-                bi = torch.full(shp_(num_sample, 4), -1, dtype=torch.int16, device=dev)
-                prepare_points(z, running, it, bi, sample_major=sm)
+                if bi is None:
+                    bi = torch.full(shp_(num_sample, 4), -1, dtype=torch.int16, device=dev)
+                    prepare_points(z, running, it, bi, sample_major=sm)
                 pts_inference(ro, rd, z, dd, bi, self.feature_tables, self.packed, self.resolution, self.occupied_grid,
                               self.grid_starts, self.grid_log2dim, self.block_corner, self.block_size, pd, ps, pa, sample_major=sm)
+            if nm is not None:
+                accumulate_normal(pn, pa, tr, z, nm, sample_major=sm)
             accumulate_color(pd, ps, pa, tr, z, df, sp, dp, sample_major=sm)
 
         # tiles each ray's path meets (the sorted list ends at the first miss): a ray whose tracing index has reached its own count has
@@ -166,7 +185,8 @@ class TileSetRenderer:
             if n_run == 0:
                 break
             if n_run * 10 > B * self.compact_below_tenths:   # (compaction costs ~0.1 ms of gathers)
-                fg_pass(rays_o, rays_d, inter, tracing_blocks, tracing_idx, z_start, transp, dif, spec, depth, running, pd, ps, pa)
+                fg_pass(rays_o, rays_d, inter, tracing_blocks, tracing_idx, z_start, transp, dif, spec, depth, running, pd, ps, pa,
+                        normal, pn)
                 continue
             # Not every ray runs (rays that miss every tile; later passes: most have left the tiles or are saturated): the pass runs
             # on the running rays alone -- every op
@@ -177,11 +197,13 @@ class TileSetRenderer:
             if lay == 2 and n_run % 32:
                 idx = torch.cat([idx, idx[-1:].expand(32 - n_run % 32)])
             n = idx.shape[0]
-            sub = [t[idx].contiguous() for t in (rays_o, rays_d, inter, tracing_blocks, tracing_idx, z_start, transp, dif, spec, depth)]
+            state = (tracing_idx, z_start, transp, dif, spec, depth) + ((normal,) if normals else ())
+            sub = [t[idx].contiguous() for t in (rays_o, rays_d, inter, tracing_blocks) + state]
             shp_n = {0: lambda S, *tail: (n, S, *tail), 1: lambda S, *tail: (S, n, *tail), 2: lambda S, *tail: (n // 32, S, 32, *tail)}[lay]
-            fg_pass(*sub, torch.ones(n, dtype=torch.bool, device=dev), torch.empty(shp_n(num_sample, 3), device=dev),
-                    torch.empty(shp_n(num_sample, 3), device=dev), torch.empty(shp_n(num_sample, 1), device=dev))
-            for full, part in zip((tracing_idx, z_start, transp, dif, spec, depth), sub[4:]):
+            fg_pass(*sub[:10], torch.ones(n, dtype=torch.bool, device=dev), torch.empty(shp_n(num_sample, 3), device=dev),
+                    torch.empty(shp_n(num_sample, 3), device=dev), torch.empty(shp_n(num_sample, 1), device=dev),
+                    sub[10] if normals else None, torch.empty(shp_n(num_sample, 3), device=dev) if normals else None)
+            for full, part in zip(state, sub[4:]):
                 full[idx] = part   # (the padding repeats the last ray: equal values land on it twice)
         # blended backgrounds of the exit tile(s)
         bg_b = torch.full((B, 4), -1, dtype=torch.int16, device=dev)
@@ -216,10 +238,13 @@ class TileSetRenderer:
             bgd += td * w
             bgs += ts * w
             bgz += tz * w
-        out = (dif + transp * bgd, spec + transp * bgs, depth + transp * bgz, transp)
+        out = (dif + transp * bgd, spec + transp * bgs, depth + transp * bgz, transp) + ((normal,) if normals else ())
         return tuple(t[:n_rays] for t in out) if B != n_rays else out
 
     def render(self, H, W, K, c2w, **kw):
+        """One view -> (diffuse [H,W,3], specular [H,W,3], depth [H,W,1], transparency [H,W,1]), and with normals=True the normal map
+        [H,W,3] (render_rays)."""
         o, d = self.compute_rays(H, W, K, c2w)
-        dif, spec, depth, transp = self.render_rays(o, d, **kw)
-        return dif.reshape(H, W, 3), spec.reshape(H, W, 3), depth.reshape(H, W, 1), transp.reshape(H, W, 1)
+        dif, spec, depth, transp, *nm = self.render_rays(o, d, **kw)
+        return (dif.reshape(H, W, 3), spec.reshape(H, W, 3), depth.reshape(H, W, 1), transp.reshape(H, W, 1),
+                *(x.reshape(H, W, 3) for x in nm))
