@@ -668,6 +668,58 @@ int scanerf_pts_normals_counted(const float *rays_o, const float *rays_d, const 
 int scanerf_accumulate_normal(const float *pts_normal, const float *pts_alpha, const float *transparency, const float *z_vals,
                               float *normal, int B, int S, int sample_major, scanerf_stream_t stream);
 
+/* ---- level-set mesh extraction (csrc/isosurface.hip).  The reference has no mesh extraction; the definition is
+ *   this comment.  float32 unless said otherwise.
+ *   Lattice: n = (nx, ny, nz) cells over the tile box (occ_corner / occ_size in world coordinates, [-1,1]^3 in contracted ones).
+ *     Point (i,j,k), 0 <= i <= nx (likewise j, k), has the contracted position x = float(i) * h_x - 1, h_x = 2.0f / float(nx), the
+ *     multiply and the subtract separately rounded; y and z alike.
+ *   Field: v(i,j,k) = sigma(x) if the point is live, else 0.  sigma is what scanerf_sigma_normals_points returns for that x, bit
+ *     for bit (16 levels, 32-channel decoder, f32 or f16 table, weight_feature).  With G = 2^log2dim per axis, point i lies in the
+ *     CLOSED occupancy cell c (0 <= c < G) of an axis iff c n <= i G <= (c + 1) n (integers; at most two cells per axis, eight in
+ *     all); the point is live iff any of those cells is set in occupied_grid [Gx,Gy,Gz].
+ *   Inside: v > level, strict, level > 0 (sigma units): unoccupied space is outside.
+ *   Surface nets: cell (i,j,k), 0 <= i < nx etc., is active when its 8 corners are neither all inside nor all outside.  An active
+ *     cell owns one vertex, the mean of the crossing points of those of its 12 edges whose ends differ in `inside`.  On an edge
+ *     along axis a from point p (value va) to p + e_a (value vb) the crossing has the lattice coordinate p_a + t,
+ *     t = (level - va) / (vb - va), and integer coordinates otherwise.  Edges are summed in the order a = 0, 1, 2 and, within an
+ *     axis, with o1 = (a+1)%3 and o2 = (a+2)%3, the offsets (d1,d2) along (o1,o2) in the order (0,0), (1,0), (0,1), (1,1);
+ *     sequentially in float32, then divided by the count.  The vertex L (lattice coordinates) has the contracted position
+ *     L * h - 1 and the world position occ_corner + L * (occ_size / n) (dense op: origin + L * spacing), separately rounded.
+ *     A lattice edge along a from p to p + e_a whose ends differ and which is interior (1 <= p_o1 <= n_o1 - 1 and
+ *     1 <= p_o2 <= n_o2 - 1) gives one quad over the vertices of the four cells p + (d1,d2), (d1,d2) = (-1,-1), (0,-1), (0,0),
+ *     (-1,0) along (o1,o2), in this cyclic order q0..q3 -- reversed if p is outside -- split into the triangles (q0,q1,q2) and
+ *     (q0,q2,q3): counter-clockwise seen from the outside.  Edges on the faces of the tile box give no quad: the mesh is open
+ *     there, where the neighbouring tile continues.
+ *   Two passes.  count: per brick of 8^3 cells the active-cell mask and the vertex / quad counts, then their exclusive sums, all in
+ *     `scratch` (scanerf_isosurface_scratch_bytes(nx,ny,nz) bytes, 16-byte aligned: 72 bytes per brick + 72; 0 for a lattice that
+ *     is refused); its first 16 bytes then hold int64 V and int64 F (triangles).  The caller reads them, allocates, and calls
+ *     emit with the SAME arguments and the scratch as count left it:  vertices [V,3] f32 (world), faces [F,3] i32, cells [V,3] i32
+ *     (the owning cell of each vertex), lattice [V,3] f32 (L; may be NULL).  Vertices are ordered by brick, then by cell within
+ *     the brick; faces by brick, then edge.  No atomics: the same bits from launch to launch.  A brick whose entries would not fit
+ *     V / F as passed is not written.  V == 0 is a no-op.  Nothing proportional to the lattice points is ever stored; the fused
+ *     emit evaluates the density of the bricks that hold a vertex a second time.
+ *   Refused before any launch: null pointers, level <= 0, n_k < 1, 2^31 or more cells or points, occ_cells (the elements of
+ *     occupied_grid) != 2^(log2dim[0] + log2dim[1] + log2dim[2]), T not a power of two.
+ * Dense op: the field is the caller's array values [nx+1, ny+1, nz+1] f32 (device); origin / spacing [3] host. */
+size_t scanerf_isosurface_scratch_bytes(int nx, int ny, int nz);
+int scanerf_isosurface_count_dense(const float *values, int nx, int ny, int nz, float level, void *scratch, size_t scratch_bytes,
+                                   scanerf_stream_t stream);
+int scanerf_isosurface_emit_dense(const float *values, int nx, int ny, int nz, float level, const float *origin /*[3] host*/,
+                                  const float *spacing /*[3] host*/, const void *scratch, size_t scratch_bytes, float *vertices,
+                                  int32_t *faces, int32_t *cells, float *lattice, int V, int F, scanerf_stream_t stream);
+/* Fused: the field is the tile's density, evaluated brick by brick where the sampler is occupied.  features [16,T,2] f32 / f16,
+ *   resolutions [16,3], mlp_blob (flat decoder blob), weight_feature [32], occupied_grid (u8 / bool) on the device; log2dim,
+ *   occ_corner, occ_size [3] host. */
+int scanerf_isosurface_count(const void *features, int feat_dtype, const int32_t *resolutions, const float *mlp_blob,
+                             const float *weight_feature, int T, const uint8_t *occupied_grid, const int32_t *log2dim /*[3] host*/,
+                             long long occ_cells, int nx, int ny, int nz, float level, void *scratch, size_t scratch_bytes,
+                             scanerf_stream_t stream);
+int scanerf_isosurface_emit(const void *features, int feat_dtype, const int32_t *resolutions, const float *mlp_blob,
+                            const float *weight_feature, int T, const uint8_t *occupied_grid, const int32_t *log2dim /*[3] host*/,
+                            long long occ_cells, int nx, int ny, int nz, float level, const float *occ_corner /*[3] host*/,
+                            const float *occ_size /*[3] host*/, const void *scratch, size_t scratch_bytes, float *vertices,
+                            int32_t *faces, int32_t *cells, float *lattice, int V, int F, scanerf_stream_t stream);
+
 #define SCANERF_RAY_OUT 16
 
 #ifdef __cplusplus

@@ -109,6 +109,11 @@ PROTOTYPES = {
     "scanerf_pts_normals": ("I", "PPPPPPPPPPPPPPIIIIIP", REQ),
     "scanerf_pts_normals_counted": ("I", "PPPPPPPPPPPPPPPIIIIIP", OPT),
     "scanerf_accumulate_normal": ("I", "PPPPPIIIP", REQ),
+    "scanerf_isosurface_scratch_bytes": ("Z", "III", REQ),
+    "scanerf_isosurface_count_dense": ("I", "PIIIFPZP", REQ),
+    "scanerf_isosurface_emit_dense": ("I", "PIIIFPPPZPPPPIIP", REQ),
+    "scanerf_isosurface_count": ("I", "PIPPPIPPLIIIFPZP", REQ),
+    "scanerf_isosurface_emit": ("I", "PIPPPIPPLIIIFPPPZPPPPIIP", REQ),
 }
 SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if required]
 OPTIONAL_SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if not required]

@@ -73,15 +73,18 @@ __device__ __forceinline__ void locate_p01(float p01, int res, int &b, float &t,
 // (d sigma / d p_k without its factor sigmoid(s)).  Every lane of the wave takes part (dead lanes: any finite x; every table index
 // is masked to the table).  P01: x is the render-time ops' unit-cube position p01 = pts / 2 + 0.25 (the cell is pts_inference's
 // v = p01 (res - 1), the contracted coordinate behind ascale 2 pts - 1) instead of a contracted position in [-2,2].
-template <int DT, bool P01 = false>
+// VALUE: only s is formed (csrc/isosurface.hip): the feature column alone goes through the product, in the same order -- s has the
+// bits of the full form; gsum and ascale are not touched.
+template <int DT, bool P01 = false, bool VALUE = false>
 __device__ __forceinline__ void density_grad(const float *lds, const void *features, int T, const float ascale[3], float c, int lane,
                                              const float x[3], float &s_out, float gsum[3])
 {
+    constexpr int NQ = VALUE ? 1 : 4;
     const uint32_t mask = (uint32_t)T - 1u;
     const int h = lane >> 5;
     const int *lres = reinterpret_cast<const int *>(lds + NL_RES);
     // F[level][nb][col]: after the exchange the B operand of samples 32 nb + (lane & 31), column col (0 = feature, 1 + k = d/dp_k)
-    float F[16][2][4];
+    float F[16][2][NQ];
 #pragma unroll
     for (int l = 0; l < 16; ++l) {
         const int4 res = reinterpret_cast<const int4 *>(lres)[l];
@@ -114,14 +117,16 @@ __device__ __forceinline__ void density_grad(const float *lds, const void *featu
             const float dz0 = fmaf(ty, d01 - d00, d00), dz1 = fmaf(ty, d11 - d10, d10);
             const float y0 = fmaf(ty, e01 - e00, e00), y1 = fmaf(ty, e11 - e10, e10);
             col[ft][0] = fmaf(tx, y1 - y0, y0);
-            col[ft][1] = (sc[0] * ascale[0]) * (y1 - y0);
-            col[ft][2] = (sc[1] * ascale[1]) * fmaf(tx, (e11 - e10) - (e01 - e00), e01 - e00);
-            col[ft][3] = (sc[2] * ascale[2]) * fmaf(tx, dz1 - dz0, dz0);
+            if constexpr (!VALUE) {
+                col[ft][1] = (sc[0] * ascale[0]) * (y1 - y0);
+                col[ft][2] = (sc[1] * ascale[1]) * fmaf(tx, (e11 - e10) - (e01 - e00), e01 - e00);
+                col[ft][3] = (sc[2] * ascale[2]) * fmaf(tx, dz1 - dz0, dz0);
+            }
         }
         // half-wave exchange: lanes < 32 keep feature 0 and receive feature 0 of lane + 32; lanes >= 32 keep feature 1 and receive
         // feature 1 of lane - 32
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
+        for (int q = 0; q < NQ; ++q) {
             const float y = __shfl_xor(h ? col[0][q] : col[1][q], 32, 64);
             F[l][0][q] = h ? y : col[0][q];
             F[l][1][q] = h ? col[1][q] : y;
@@ -136,28 +141,30 @@ __device__ __forceinline__ void density_grad(const float *lds, const void *featu
         gp[nb][0] = gp[nb][1] = gp[nb][2] = 0.0f;
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb) {
-            v16f acc[4];
+            v16f acc[NQ];
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
                 acc[0][g] = lds[NL_B0 + 32 * mb + nmap(g, h)];
-                acc[1][g] = acc[2][g] = acc[3][g] = 0.0f;
+                if constexpr (!VALUE) acc[1][g] = acc[2][g] = acc[3][g] = 0.0f;
             }
 #pragma unroll
             for (int l = 0; l < 16; ++l) {
                 const float aw = lds[NL_A + (mb * 16 + l) * 64 + lane];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(aw, F[l][nb][q], acc[q], 0, 0, 0);
+                for (int q = 0; q < NQ; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(aw, F[l][nb][q], acc[q], 0, 0, 0);
             }
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
                 const float aj = lds[NL_AVEC + 32 * mb + nmap(g, h)];
                 const float u = acc[0][g];
                 const float G = __expf(u * u * -50.0f);
-                const float gd = aj * (-100.0f * u * G);
+                [[maybe_unused]] const float gd = aj * (-100.0f * u * G);
                 sp[nb] = fmaf(aj, G, sp[nb]);
-                gp[nb][0] = fmaf(gd, acc[1][g], gp[nb][0]);
-                gp[nb][1] = fmaf(gd, acc[2][g], gp[nb][1]);
-                gp[nb][2] = fmaf(gd, acc[3][g], gp[nb][2]);
+                if constexpr (!VALUE) {
+                    gp[nb][0] = fmaf(gd, acc[1][g], gp[nb][0]);
+                    gp[nb][1] = fmaf(gd, acc[2][g], gp[nb][1]);
+                    gp[nb][2] = fmaf(gd, acc[3][g], gp[nb][2]);
+                }
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -166,11 +173,13 @@ __device__ __forceinline__ void density_grad(const float *lds, const void *featu
     float mine[4] = { h ? sp[1] : sp[0], h ? gp[1][0] : gp[0][0], h ? gp[1][1] : gp[0][1], h ? gp[1][2] : gp[0][2] };
     float other[4] = { h ? sp[0] : sp[1], h ? gp[0][0] : gp[1][0], h ? gp[0][1] : gp[1][1], h ? gp[0][2] : gp[1][2] };
 #pragma unroll
-    for (int q = 0; q < 4; ++q) mine[q] += __shfl_xor(other[q], 32, 64);
+    for (int q = 0; q < NQ; ++q) mine[q] += __shfl_xor(other[q], 32, 64);
     s_out = mine[0] + c;
-    gsum[0] = mine[1];
-    gsum[1] = mine[2];
-    gsum[2] = mine[3];
+    if constexpr (!VALUE) {
+        gsum[0] = mine[1];
+        gsum[1] = mine[2];
+        gsum[2] = mine[3];
+    }
 }
 
 // s, gsum -> sigma, g = d sigma / d p, n = -g / (|g| + 1e-8)

@@ -1,0 +1,155 @@
+"""Level-set mesh extraction (csrc/isosurface.hip): surface nets over a tile's density, or over a caller's value
+lattice.  The reference has no mesh extraction; the definition is the comment of include/scanerf_hip.h.
+
+    surface_nets(values, level, origin, spacing)        the dense op on a value array [nx+1, ny+1, nz+1]
+    extract_mesh(features, ..., n, level)               the tile's density level set; route="fused" never stores the lattice,
+                                                        route="dense" composes lattice points -> render.sigma_normals_points ->
+                                                        liveness -> the dense op (the witness, and fine for small lattices)
+
+Both return a Mesh: vertices [V,3] f32 (world), faces [F,3] i32 (counter-clockwise seen from the outside), cells [V,3] i32 (the owning
+cell of each vertex), lattice [V,3] f32 (the vertices in lattice coordinates) and, on request, normals [V,3] f32.  Two launches with
+one host read of (V, F) between them; no CPU path."""
+import collections
+import ctypes
+
+import numpy as np
+import torch
+
+from . import render
+from ._capi import check, dev_ptr, lib, stream
+
+Mesh = collections.namedtuple("Mesh", "vertices faces cells lattice normals")
+ROUTES = ("fused", "dense")
+_f32 = torch.float32
+
+
+def _lattice_size(n):
+    n = [int(v) for v in n]
+    if len(n) != 3:
+        raise RuntimeError(f"scanerf: n must hold 3 cell counts, got {n}")
+    return n
+
+
+def _scratch(device, n):
+    nbytes = int(lib().scanerf_isosurface_scratch_bytes(*n))
+    if nbytes == 0:
+        raise RuntimeError(f"scanerf: lattice n={tuple(n)} is not supported (every n_k >= 1, fewer than 2^31 cells and points): "
+                           + lib().scanerf_last_error().decode("utf-8", "replace"))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+
+def _totals(scratch):
+    """The one host read: (V, F) as the count pass left them."""
+    V, F = (int(v) for v in scratch[:16].view(torch.int64).tolist())
+    if V >= 2 ** 31 // 3 or F >= 2 ** 31 // 3:
+        raise RuntimeError(f"scanerf: the mesh has V={V} vertices and F={F} faces: too many for int32 indices")
+    return V, F
+
+
+def _outputs(device, V, F):
+    return (torch.empty((V, 3), dtype=_f32, device=device), torch.empty((F, 3), dtype=torch.int32, device=device),
+            torch.empty((V, 3), dtype=torch.int32, device=device), torch.empty((V, 3), dtype=_f32, device=device))
+
+
+def _host3(v, name):
+    if isinstance(v, torch.Tensor):
+        v = v.detach().cpu().tolist()
+    return render._host3(v, name)
+
+
+def _f32_div(a, b):
+    """a / b as one float32 division (what the kernels' host side forms), as a Python float."""
+    return float(np.float32(a) / np.float32(b))
+
+
+def surface_nets(values, level, origin=(0.0, 0.0, 0.0), spacing=(1.0, 1.0, 1.0)):
+    """The dense op: values [nx+1, ny+1, nz+1] f32 on the GPU, inside = values > level (level > 0), vertex = origin + L * spacing."""
+    if not isinstance(values, torch.Tensor) or values.dim() != 3:
+        raise RuntimeError("scanerf: values must be a [nx+1, ny+1, nz+1] tensor")
+    p = dev_ptr(values, _f32, "values")
+    n = [int(s) - 1 for s in values.shape]
+    o, sp = _host3(origin, "origin"), _host3(spacing, "spacing")
+    scratch, nbytes = _scratch(values.device, n)
+    check(lib().scanerf_isosurface_count_dense(p, *n, float(level), scratch.data_ptr(), nbytes, stream()), "isosurface_count_dense")
+    V, F = _totals(scratch)
+    vertices, faces, cells, lattice = _outputs(values.device, V, F)
+    if V:
+        check(lib().scanerf_isosurface_emit_dense(p, *n, float(level), o, sp, scratch.data_ptr(), nbytes, vertices.data_ptr(), faces.data_ptr(),
+                                                  cells.data_ptr(), lattice.data_ptr(), V, F, stream()), "isosurface_emit_dense")
+    return Mesh(vertices, faces, cells, lattice, None)
+
+
+def lattice_positions(n, device):
+    """Contracted positions [(nx+1)(ny+1)(nz+1), 3] of the lattice points, x fastest last: x = float(i) * (2 / n) - 1, two roundings."""
+    axes = [torch.arange(n[k] + 1, device=device, dtype=_f32) * _f32_div(2.0, n[k]) - 1.0 for k in range(3)]
+    return torch.stack(torch.meshgrid(*axes, indexing="ij"), -1).reshape(-1, 3).contiguous()
+
+
+def live_points(n, occupied_grid):
+    """[nx+1, ny+1, nz+1] bool: the lattice points that lie in the closed extent of an occupied sampler cell -- point i lies in cell c of
+    an axis iff c n <= i G <= (c + 1) n, in integers."""
+    occ = occupied_grid.to(_f32)
+    for k in range(3):
+        G = int(occupied_grid.shape[k])
+        iG = torch.arange(n[k] + 1, device=occ.device, dtype=torch.int64)[:, None] * G
+        c = torch.arange(G, device=occ.device, dtype=torch.int64)[None, :]
+        member = ((c * n[k] <= iG) & (iG <= (c + 1) * n[k])).to(_f32)      # [n_k + 1, G_k]
+        occ = torch.movedim(torch.tensordot(member, torch.movedim(occ, k, 0), dims=1), 0, k)
+    return occ > 0
+
+
+def _contracted(lattice, n):
+    h = [_f32_div(2.0, n[k]) for k in range(3)]
+    return (lattice * torch.tensor(h, dtype=_f32, device=lattice.device) - 1.0).contiguous()
+
+
+def extract_mesh(features, resolutions, blob, weight_feature, occupied_grid, log2dim, occ_corner, occ_size, n, level, normals=False,
+                 route="fused"):
+    """The level set sigma == level of a tile's density as a triangle mesh.  features [16,T,2] f32 / f16, resolutions [16,3], blob (the
+    flat decoder blob), weight_feature [32], occupied_grid bool [2^log2dim], occ_corner / occ_size: the tile box (3 floats each),
+    n: cells per axis of the lattice over it.  normals=True adds render.sigma_normals_points' normals at the vertices
+    (axis_scale = 4 / (2 occ_size))."""
+    if route not in ROUTES:
+        raise RuntimeError(f"scanerf: route must be one of {ROUTES}, got {route!r}")
+    n = _lattice_size(n)
+    T, mid = render._normals_common(features, resolutions, blob, weight_feature)
+    occ = dev_ptr(occupied_grid, (torch.bool, torch.uint8), "occupied_grid")
+    log2dim = [int(v) for v in (log2dim.tolist() if isinstance(log2dim, torch.Tensor) else log2dim)]
+    if len(log2dim) != 3 or tuple(occupied_grid.shape) != tuple(2 ** k for k in log2dim):
+        raise RuntimeError(f"scanerf: occupied_grid {tuple(occupied_grid.shape)} does not match log2dim {log2dim}")
+    corner, size = _host3(occ_corner, "occ_corner"), _host3(occ_size, "occ_size")
+    if not all(s > 0 for s in size):
+        raise RuntimeError(f"scanerf: occ_size must be positive, got {list(size)}")
+    if not float(level) > 0:
+        raise RuntimeError(f"scanerf: level={level} must be > 0")
+    device = features.device
+    if route == "dense":
+        sigma, _, _ = render.sigma_normals_points(lattice_positions(n, device), features, resolutions, blob, weight_feature)
+        values = torch.where(live_points(n, occupied_grid).reshape(-1), sigma, torch.zeros_like(sigma)).reshape(n[0] + 1, n[1] + 1, n[2] + 1)
+        step = [_f32_div(size[k], n[k]) for k in range(3)]
+        mesh = surface_nets(values.contiguous(), level, list(corner), step)
+    else:
+        l2d = (ctypes.c_int32 * 3)(*log2dim)
+        scratch, nbytes = _scratch(device, n)
+        head = (*mid, T, occ, l2d, int(occupied_grid.numel()), *n, float(level))
+        check(lib().scanerf_isosurface_count(*head, scratch.data_ptr(), nbytes, stream()), "isosurface_count")
+        V, F = _totals(scratch)
+        vertices, faces, cells, lattice = _outputs(device, V, F)
+        if V:
+            check(lib().scanerf_isosurface_emit(*head, corner, size, scratch.data_ptr(), nbytes, vertices.data_ptr(), faces.data_ptr(),
+                                                cells.data_ptr(), lattice.data_ptr(), V, F, stream()), "isosurface_emit")
+        mesh = Mesh(vertices, faces, cells, lattice, None)
+    if normals:
+        if mesh.vertices.shape[0]:
+            _, _, nrm = render.sigma_normals_points(_contracted(mesh.lattice, n), features, resolutions, blob, weight_feature,
+                                                    axis_scale=[_f32_div(4.0, 2.0 * s) for s in size])
+        else:
+            nrm = torch.empty((0, 3), dtype=_f32, device=device)
+        mesh = mesh._replace(normals=nrm)
+    return mesh
+
+
+def cells_per_axis(occ_size, longest):
+    """Lattice for a box: `longest` cells along its longest side, the other sides by the box's aspect (at least 1)."""
+    size = [float(v) for v in (occ_size.detach().cpu().tolist() if isinstance(occ_size, torch.Tensor) else occ_size)]
+    return [max(1, int(round(int(longest) * s / max(size)))) for s in size]

@@ -358,6 +358,21 @@ class TileModel(nn.Module):
                 img["normal"][sl] = (n + 1.0) / 2.0 * vf[:, None]
         return img
 
+    # ---- geometry out: the density's level set as a triangle mesh (the reference has none) ------------------------
+    @torch.no_grad()
+    def extract_mesh(self, n, level, global_step=None, normals=True, route="fused"):
+        """Surface nets over the tile box on a lattice of n = (nx, ny, nz) cells (an int: that many along the longest side, the others
+        by the box's aspect), inside = sigma > level -> meshing.Mesh (world-space vertices, faces, cells, lattice, normals).
+        global_step: the coarse-to-fine mask of that step; None = no mask, as the normals and the renderer read the table."""
+        from . import meshing
+        if self.n_levels != 16:
+            raise RuntimeError("scanerf: the mesh extraction needs 16 levels (the reference hard-codes them)")
+        if isinstance(n, int):
+            n = meshing.cells_per_axis(self.occ_size, n)
+        wf = torch.ones(32, dtype=torch.float32, device=self.device) if global_step is None else self.weight_feature(global_step)
+        return meshing.extract_mesh(self.gather_table().detach(), self.resolution, self.decoder.blob().detach().contiguous(), wf,
+                                    self.occupied_grid, self.log2dim, self.occ_corner, self.occ_size, n, level, normals=normals, route=route)
+
     # ---- optimiser on the table: fused sparse Adam (only touched entries move) --------------
     @torch.no_grad()
     def table_adam(self, lr, betas=(0.9, 0.99), eps=1e-15):

@@ -1,0 +1,66 @@
+#!/usr/bin/env python3
+"""Level-set mesh extraction of exported tiles: one PLY per tile.
+
+    python tools/extract_mesh.py TILEDIR [TILEDIR ...] --level SIGMA [--cells-per-axis 256] [--out DIR] [--route fused|dense] [--gpu 0]
+
+TILEDIR holds feature.npz and decoder.pth as renderer.export_tile writes and renderer.load_tile reads them.  The lattice covers the
+tile box (the inner half of the exported 2x box) with --cells-per-axis cells along its longest side and the other sides by the box's
+aspect; the surface is sigma == --level (sigma units, > 0), extracted only where the tile's sampler is occupied, and written with
+formats.write_ply to DIR/<name of TILEDIR>.ply (default: TILEDIR/mesh.ply).  The files read back through formats.read_ply,
+fastmesh.FastMesh and tools/build_tiles.py.
+
+Tile meshes abut at the faces of their tile boxes, where each is left open, and overlap in the tiles' margins.  Stitching them into
+one mesh is out of scope here."""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def parser():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0],
+                                 epilog="Tile meshes abut at tile-box faces (open there) and overlap in the margins; they are not stitched.")
+    ap.add_argument("tiles", metavar="TILEDIR", nargs="+", help="directories with feature.npz and decoder.pth")
+    ap.add_argument("--level", type=float, required=True, help="density of the level set (sigma units, > 0)")
+    ap.add_argument("--cells-per-axis", type=int, default=256, help="lattice cells along the tile box's longest side")
+    ap.add_argument("--out", default=None, metavar="DIR", help="write DIR/<tile name>.ply instead of TILEDIR/mesh.ply")
+    ap.add_argument("--route", choices=("fused", "dense"), default="fused", help="dense: the composed route (small lattices only)")
+    ap.add_argument("--gpu", type=int, default=0)
+    return ap
+
+
+def extract_tile(tile, cells, level, device, route="fused"):
+    """tile: renderer.load_tile's dict -> meshing.Mesh (no normals: formats.write_ply stores positions and faces)."""
+    import numpy as np
+    import torch
+
+    from scanerf_amd import meshing, renderer
+    t = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt).to(device).contiguous()
+    corner, size = renderer.render_box(np.asarray(tile["block_corner"], np.float32), np.asarray(tile["block_size"], np.float32))
+    log2dim = [int(v) for v in np.asarray(tile["grid_log2dim"]).reshape(-1)]
+    occ = t(np.asarray(tile["occupied_grid"]).reshape([2 ** k for k in log2dim]), torch.bool)
+    return meshing.extract_mesh(t(tile["features"], torch.float16), t(tile["resolution"], torch.int32), t(tile["blob"], torch.float32),
+                                torch.ones(32, dtype=torch.float32, device=device), occ, log2dim, corner.tolist(), size.tolist(),
+                                meshing.cells_per_axis(size.tolist(), cells), level, normals=False, route=route)
+
+
+def main(argv=None):
+    args = parser().parse_args(argv)
+    import scanerf_amd  # noqa: F401
+    from scanerf_amd import formats, renderer
+    device = f"cuda:{args.gpu}"
+    if args.out:
+        os.makedirs(args.out, exist_ok=True)
+    for path in args.tiles:
+        mesh = extract_tile(renderer.load_tile(path), args.cells_per_axis, args.level, device, args.route)
+        name = os.path.basename(os.path.normpath(path))
+        out = os.path.join(args.out, name + ".ply") if args.out else os.path.join(path, "mesh.ply")
+        formats.write_ply(out, mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy())
+        print(f"{out}: {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} faces")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
