@@ -171,7 +171,7 @@ def lib():
         if st["status"] != "passed":
             import warnings
             warnings.warn(f"scanerf: {LIB_PATH} is NOT the audited build (ISA audit: {st['status']}; {st.get('why', '')}).  Its kernels' "
-                          "listings were not checked against the validated ones (csrc/isa_manifest.json, DESIGN.md 4.10: no "
+                          "listings were not checked against the validated ones (csrc/isa_manifest.json, DESIGN.md §4.1 (last paragraph); profiles/DESIGN_r04_experiment_log.md §4.10: no "
                           "packed-f32 instructions, pinned listings): launch-to-launch reproducibility is not established for it.",
                           RuntimeWarning, stacklevel=2)
     return _lib

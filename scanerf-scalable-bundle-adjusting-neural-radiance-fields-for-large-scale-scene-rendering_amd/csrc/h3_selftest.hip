@@ -78,7 +78,7 @@ __global__ void __launch_bounds__(64) k_h3_selftest(const float *packed, const f
 
 // ~300 KB of straight-line code on every CU (no LDS, three registers): after it no other kernel's instructions are left in the
 // 64 KB instruction caches.  Test infrastructure: launch-to-launch comparisons with this in between are the screen for faults
-// that only show when a kernel starts on cold instruction caches (tools/fault_probe.py).
+// that only show when a kernel starts on cold instruction caches (DESIGN.md §4.1 (last paragraph); profiles/DESIGN_r04_experiment_log.md §4.10, tools/fault_probe.py).
 __global__ void __launch_bounds__(512, 2) k_icache_sweep(float *sink, int never)
 {
     float a = (float)threadIdx.x, b = 1.0f;

@@ -36,7 +36,7 @@ __host__ __device__ constexpr int h3_ku(int t, int h, int j) { return 16 * t + 8
 // the f32 tail lies past 64 KB, beyond the immediate of an LDS read: one address register per weight / bias read, ~35 of them
 // live across the sample loop (render-time kernel 25 -> 4 spilled registers, frame 105 -> 99 ms; training forward 51 -> 0 spills
 // together with -fno-slp-vectorize, 3.35 -> 3.10 ms).  Round 2 withdrew it from the training forward because that build wrote a
-// wrong encoder output in ~6 % of cold first launches; round 3 traced the fault to packed-f32 weight pairs, not to
+// wrong encoder output in ~6 % of cold first launches; round 3 traced the fault to packed-f32 weight pairs (DESIGN.md §4.1 (last paragraph); profiles/DESIGN_r04_experiment_log.md §4.10), not to
 // this addressing.
 #ifndef H3_OPAQUE_ADDR
 #define H3_OPAQUE_ADDR 0
@@ -62,7 +62,7 @@ struct HL {
 // because the compiler does not select these forms; the `s_nop 1` tied to the lo registers stands in for the two wait states the
 // hazard recogniser would put between a vector instruction it can see and a matrix instruction reading its result.
 // (Round 2 tried v_fma_mix_f32 here, -4 % on the render-time frame, and withdrew it because the training step then differed
-// between runs: that build still held packed-f32 instructions, the cause found in round 3 -- DESIGN.md 4.10.)
+// between runs: that build still held packed-f32 instructions, the cause found in round 3 -- DESIGN.md §4.1 (last paragraph); profiles/DESIGN_r04_experiment_log.md §4.10.)
 __device__ __forceinline__ HL split8(const v16f &v, int t)
 {
     HL o;

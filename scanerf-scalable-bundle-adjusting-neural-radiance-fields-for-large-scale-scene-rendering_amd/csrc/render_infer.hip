@@ -1,5 +1,8 @@
 // render_infer.hip -- pts_inference / bg_pts_inference_v2, the hot loop of the multi-tile novel-view render (gfx950), in its
 // three arithmetic forms.  The per-ray ops around it are render_time.hip; what both units use is render_time_common.h.
+// The per-sample tile geometry -- slot list, position in a tile, blend weight, cell and occupancy, table coordinate, output
+// stage -- has ONE definition, render_infer_device.h (shared with pts_normals, render_normals_tiles.hip); the kernels here are
+// what differs between them: how samples are grouped, where the decoder's operands come from, what is in flight when.
 //
 // Reference behaviour: hashgrid/src/rendering_kernel.cu:467-621 and :1012-1171.  Built with -ffp-contract=off, as render_time.hip.
 //
@@ -19,7 +22,7 @@
 #define H3_OPAQUE_ADDR 1  // (render_h3.h: one base register for the decoder image reads; measured clean on this kernel, tools/render_soak.py)
 #include "render_h3.h"
 #include "render_t16.h"
-#include "render_time_common.h"
+#include "render_infer_device.h"
 
 using namespace scanerf;
 
@@ -61,6 +64,8 @@ __global__ void __launch_bounds__(256, 2) k_pts_inference(InferArgs a)
         }
         const float dnorm = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
         const float z = a.z_vals[ec];
+        float wp[3];
+        world_point(o, z, d, wp);
         float delta;  // what multiplies sigma in alpha = 1 - exp(-sigma*delta)
         if (BG) delta = (s == a.S - 1) ? 10000000.0f : a.z_vals[ec + 1] - z;   // :1045-1047: raw depth step
         else delta = a.dists[ec] * dnorm;                                       // :557
@@ -81,32 +86,18 @@ __global__ void __launch_bounds__(256, 2) k_pts_inference(InferArgs a)
                 // tile-space position, blend weight, occupancy
                 float p01[3], w = 0.0f;
                 bool run = mine;
+                const float *cb = a.t.corners + 3 * b, *sb = a.t.sizes + 3 * b;
                 if (BG) {
-                    // L-infinity contraction of the 2x-box coordinates (:1056-1096), then [-2,2] -> [0,1]
-                    float q[3];
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) q[c] = 2.0f * ((o[c] + z * d[c]) - a.t.corners[3 * b + c]) / a.t.sizes[3 * b + c] - 1.0f;
-                    const float linf = fmaxf(fabsf(q[0]), fmaxf(fabsf(q[1]), fabsf(q[2])));
-                    const float ratio = (2.0f - 1.0f / linf) / linf;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) p01[c] = (q[c] * ratio + 2.0f) / 4.0f;
+                    bg_p01(wp, cb, sb, p01);
                 } else {
-                    float pt[3], dis[3];
-                    int loc[3];
-                    const int l2d[3] = { a.t.log2dim[3 * b], a.t.log2dim[3 * b + 1], a.t.log2dim[3 * b + 2] };
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        pt[c] = ((o[c] + z * d[c]) - a.t.corners[3 * b + c]) / a.t.sizes[3 * b + c];
-                        dis[c] = (0.5f - fabsf(pt[c] - 0.5f)) * a.t.sizes[3 * b + c];
-                        const int r = 1 << l2d[c];
-                        int cc = (int)(pt[c] * (float)r);
-                        loc[c] = cc < 0 ? 0 : (cc > r - 1 ? r - 1 : cc);
-                        p01[c] = pt[c] / 2.0f + 0.25f;  // tile -> the middle half of the 2x box (:548)
-                    }
-                    w = xz_weight(dis[0], dis[2]);
+                    float pt[3];
+                    tile_point(wp, cb, sb, pt);
+                    fg_p01(pt, p01);
+                    w = tile_weight(pt, sb);
+                    const int64_t cell = tile_cell(a.t, b, pt);
                     if (mine) {
                         weight += w;
-                        run = a.t.occ[a.t.grid_starts[b] + cell_offset(loc, l2d[1], l2d[2])] != 0;
+                        run = a.t.occ[cell] != 0;
                     }
                 }
                 if (!__any(run)) continue;  // wave-uniform
@@ -154,7 +145,7 @@ __global__ void __launch_bounds__(256, 2) k_pts_inference(InferArgs a)
 }
 
 
-// ---- pieces of the software-pipelined group loop of k_pts_inference_chunks ------------------------------------------------
+// ---- pieces of the group loops of k_pts_inference_chunks (pipelined, and plain in the experiments build) ----------------------
 // acc += w * (float)(low / high half of an f16 pair): one instruction instead of a conversion and an fma, the same value.  The
 // result stays in acc's register, which ordinary instructions have written before (render_h3.h, h3_residual_lo: inline asm is
 // invisible to the hazard recogniser, so it must not be handed a register that a matrix instruction in flight may own).
@@ -183,6 +174,12 @@ struct GroupPrep {
     bool run;
 };
 
+// a foreground sample's four slots, packed
+__device__ __forceinline__ uint2 load_slots(const InferArgs &a, uint32_t e)
+{
+    return *reinterpret_cast<const uint2 *>(a.block_idxs + (size_t)e * kMaxPtsBlocks);
+}
+
 template <bool BG>
 __device__ __forceinline__ void group_load(const InferArgs &a, int64_t total, int64_t base, int sl, GroupIn &in)
 {
@@ -201,91 +198,109 @@ __device__ __forceinline__ void group_load(const InferArgs &a, int64_t total, in
     } else {
         in.last = false;
         in.aux = a.dists[ec];
-        const uint2 raw = *reinterpret_cast<const uint2 *>(a.block_idxs + (size_t)ec * kMaxPtsBlocks);
+        const uint2 raw = load_slots(a, ec);
         in.s0 = raw.x;
         in.s1 = raw.y;
     }
 }
 
-// Same arithmetic as the group loop below (rendering_kernel.cu:499-557 / :1040-1060).  Returns whether any sample of the
-// group runs the decoder of tile b (wave-uniform).
+// What a loaded group needs for the step of tile b (rendering_kernel.cu:499-557 / :1040-1060): the table coordinate p01 and
+// st = { direction[3], depth step, blend weight of b, 1 / sum of the blend weights }.  Returns whether any sample of the group
+// runs the decoder of tile b (wave-uniform).
 template <bool BG>
 __device__ __forceinline__ bool group_prep(const InferArgs &a, int b, const float cb[3], const float sb[3], const GroupIn &in,
-                                           GroupPrep &P, float p01[3], float (*park)[64], int lane)
+                                           GroupPrep &P, float p01[3], float st[6])
 {
-    // (direction, depth step, blend weight and 1/sum of weights wait in LDS for the output stage -- registers the compiler
-    // would otherwise spill to scratch, whose reloads wait behind the gathers in flight)
-    float d[3], delta;
-    int16_t slot[kMaxPtsBlocks] = { -1, -1, -1, -1 };
+    int slot[kMaxPtsBlocks] = { -1, -1, -1, -1 };
     bool mine = false;
     if (BG) {
         mine = in.in_range && (int)in.s0 == b;
     } else if (in.in_range) {
-        slot[0] = (int16_t)(in.s0 & 0xffffu); slot[1] = (int16_t)(in.s0 >> 16);
-        slot[2] = (int16_t)(in.s1 & 0xffffu); slot[3] = (int16_t)(in.s1 >> 16);
-        bool ended = false;
-#pragma unroll
-        for (int k = 0; k < kMaxPtsBlocks; ++k) {
-            ended |= slot[k] == -1;
-            if (ended) slot[k] = -1;
-            mine |= slot[k] == b;
-        }
+        slot_list(make_uint2(in.s0, in.s1), slot);
+        mine = slots_list_tile(slot, b);
     }
     P.run = false;
     if (!__any(mine)) return false;
-    float o[3];
+    float o[3], d[3], wp[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         o[k] = a.rays_o[3 * in.i + k];
         d[k] = a.rays_d[3 * in.i + k];
     }
-    const float z = in.z;
-    float w_b = 0.0f, weight = 0.0f;
+    world_point(o, in.z, d, wp);
+    float delta, w_b = 0.0f, weight = 0.0f;
     bool run = mine;
     if (BG) {
-        delta = in.last ? 10000000.0f : in.aux - z;  // :1045-1047: raw depth step
-        float q[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) q[c] = 2.0f * ((o[c] + z * d[c]) - cb[c]) / sb[c] - 1.0f;
-        const float linf = fmaxf(fabsf(q[0]), fmaxf(fabsf(q[1]), fabsf(q[2])));
-        const float ratio = (2.0f - 1.0f / linf) / linf;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) p01[c] = (q[c] * ratio + 2.0f) / 4.0f;
+        delta = in.last ? 10000000.0f : in.aux - in.z;  // :1045-1047: raw depth step
+        bg_p01(wp, cb, sb, p01);
     } else {
-        const float dnorm = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-        delta = in.aux * dnorm;  // :557
-#pragma unroll
-        for (int k = 0; k < kMaxPtsBlocks; ++k) {
-            const int bk = slot[k];
-            if (bk == -1) continue;
-            float dis[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float sz = a.t.sizes[3 * bk + c];
-                const float pt = ((o[c] + z * d[c]) - a.t.corners[3 * bk + c]) / sz;
-                dis[c] = (0.5f - fabsf(pt - 0.5f)) * sz;
-            }
-            const float w = xz_weight(dis[0], dis[2]);
-            weight += w;
-            if (bk == b) w_b = w;
-        }
-        int loc[3];
-        const int l2d[3] = { a.t.log2dim[3 * b], a.t.log2dim[3 * b + 1], a.t.log2dim[3 * b + 2] };
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float pt = ((o[c] + z * d[c]) - cb[c]) / sb[c];
-            const int r = 1 << l2d[c];
-            const int cc = (int)(pt * (float)r);
-            loc[c] = cc < 0 ? 0 : (cc > r - 1 ? r - 1 : cc);
-            p01[c] = pt / 2.0f + 0.25f;
-        }
-        if (mine) run = a.t.occ[a.t.grid_starts[b] + cell_offset(loc, l2d[1], l2d[2])] != 0;
+        delta = in.aux * sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);  // :557
+        run = fg_sample(a.t, slot, b, cb, sb, wp, mine, p01, w_b, weight);
     }
     P.e = in.e;
     P.run = run;
-    park[0][lane] = d[0]; park[1][lane] = d[1]; park[2][lane] = d[2];
-    park[3][lane] = delta; park[4][lane] = w_b; park[5][lane] = weight > 0 ? 1.0f / weight : 1.0f;
+    st[0] = d[0]; st[1] = d[1]; st[2] = d[2];
+    st[3] = delta; st[4] = w_b; st[5] = inv_weight(weight);
     return __any(run);
+}
+
+// the output stage of a decoded sample of the 32-sample-tile kernel: bg writes, fg adds tile b's share
+template <bool BG>
+__device__ __forceinline__ void group_store(const InferArgs &a, uint32_t e, const SampleOut &so, float delta, float w_b, float inv)
+{
+    const float pa = 1.0f - expf(-1.0f * so.sigma * delta);
+    if (BG) store_bg(a.out_dif, a.out_spec, a.out_alpha, e, pa, so);
+    else add_fg(a.out_dif, a.out_spec, a.out_alpha, e, w_b, pa, inv, so);
+}
+
+// Step 1 of both chunk-major kernels: the tiles that the samples of this wave's NG groups of W list, OR-ed into tileset[0..1]
+// (bit t = tile t); all slot loads of the wave in flight together.  W = 32: the wave's upper half sits out.
+// slots(e, unsampled) -> a foreground sample's packed slot list (load_slots, or tracing_slots).
+// A background sample without a tile at this blend step gets its zeros here (the caller need not clear them).  ZERO: so does a
+// foreground sample that lists no tile (:569-571), unless `slots` calls it unsampled -- the 16-sample-tile kernel, where every
+// other sample is WRITTEN by the step of its first listed tile and added to by the later ones, so that the caller's arrays need
+// no clearing pass (7.4 GB per launch at 1920x1080x128); the 32-sample-tile kernel adds into arrays the host cleared.
+template <bool BG, int W, int NG, bool ZERO, typename Slots>
+__device__ __forceinline__ void chunk_tileset(const InferArgs &a, int64_t wbase, int64_t total, int lane, uint32_t *tileset, Slots slots)
+{
+    uint32_t mlo = 0, mhi = 0;
+    auto mark = [&](int t) {
+        if (t >= 0) {
+            if (t < 32) mlo |= 1u << t;
+            else mhi |= 1u << (t - 32);
+        }
+    };
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        const int64_t e = wbase + g * W + (lane & (W - 1));
+        if (e >= total || lane >= W) continue;
+        const uint32_t e32 = (uint32_t)e;
+        if (BG) {
+            int ri, rs;
+            pt_decompose(e32, (uint32_t)a.B, (uint32_t)a.S, a.sm, ri, rs);
+            const int tb = a.block_idxs[ri * kMaxPtsBlocks + a.step];
+            mark(tb);
+            if (tb < 0) zero_sample(a.out_dif, a.out_spec, a.out_alpha, e);
+        } else {
+            bool unsampled = false;
+            int slot[kMaxPtsBlocks];
+            slots_unpack(slots(e32, unsampled), slot);
+            // (slot_list's rule -- the list ends at the first -1 -- as nested branches: this loop is unrolled NG times, and
+            // rewriting the list's tail first costs ~12 instructions per group)
+            mark(slot[0]);
+            if (slot[0] != -1) { mark(slot[1]); if (slot[1] != -1) { mark(slot[2]); if (slot[2] != -1) mark(slot[3]); } }
+            if (ZERO && slot[0] == -1 && !unsampled) zero_sample(a.out_dif, a.out_spec, a.out_alpha, e);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        mlo |= __shfl_xor(mlo, off, 64);
+        mhi |= __shfl_xor(mhi, off, 64);
+    }
+    if (lane == 0) {
+        if (mlo) atomicOr(&tileset[0], mlo);
+        if (mhi) atomicOr(&tileset[1], mhi);
+    }
 }
 
 // First half of encode8_01<F16, 8, STRAIGHT>: the 64 corner loads of a group go out (raw f16 pairs; uniform level base + a
@@ -375,50 +390,8 @@ __global__ void __launch_bounds__(kChunkThreads, 1) k_pts_inference_chunks(Infer
         if (threadIdx.x < 2) tileset[threadIdx.x] = 0;
         __syncthreads();  // (also: the previous chunk's last tile step is complete)
         const int64_t wbase = (chunk * kChunkGroups + (int64_t)wave * kWaveGroups) * 32;
-        {   // 1. the tiles this chunk's samples list: all slot loads of the wave in flight together
-            uint32_t mlo = 0, mhi = 0;
-            auto mark = [&](int t) {
-                if (t >= 0) {
-                    if (t < 32) mlo |= 1u << t;
-                    else mhi |= 1u << (t - 32);
-                }
-            };
-#pragma unroll
-            for (int g = 0; g < kWaveGroups; ++g) {
-                const int64_t e = wbase + g * 32 + sl;
-                if (e >= total || h != 0) continue;
-                const uint32_t e32 = (uint32_t)e;
-                if (BG) {
-                    int ri, rs;
-                    pt_decompose(e32, (uint32_t)a.B, (uint32_t)a.S, a.sm, ri, rs);
-                    const int tb = a.block_idxs[ri * kMaxPtsBlocks + a.step];
-                    mark(tb);
-                    if (tb < 0) {  // no background tile at this blend step: the sample's outputs are zero (the caller need not clear them)
-                        a.out_alpha[e] = 0.0f;
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) {
-                            a.out_dif[3 * e + c] = 0.0f;
-                            a.out_spec[3 * e + c] = 0.0f;
-                        }
-                    }
-                } else {
-                    const uint2 raw = *reinterpret_cast<const uint2 *>(a.block_idxs + (size_t)e32 * kMaxPtsBlocks);
-                    const int s0 = (int16_t)(raw.x & 0xffffu), s1 = (int16_t)(raw.x >> 16), s2 = (int16_t)(raw.y & 0xffffu),
-                              s3 = (int16_t)(raw.y >> 16);
-                    mark(s0);  // the list stops at the first -1 (rendering_kernel.cu:499)
-                    if (s0 != -1) { mark(s1); if (s1 != -1) { mark(s2); if (s2 != -1) mark(s3); } }
-                }
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                mlo |= __shfl_xor(mlo, off, 64);
-                mhi |= __shfl_xor(mhi, off, 64);
-            }
-            if (lane == 0) {
-                if (mlo) atomicOr(&tileset[0], mlo);
-                if (mhi) atomicOr(&tileset[1], mhi);
-            }
-        }
+        // 1. the tiles this chunk's samples list
+        chunk_tileset<BG, 32, kWaveGroups, false>(a, wbase, total, lane, tileset, [&](uint32_t e, bool &) { return load_slots(a, e); });
         __syncthreads();
         uint64_t todo = (uint64_t)tileset[0] | ((uint64_t)tileset[1] << 32);
       while (todo) {  // 2. one step per listed tile, ascending
@@ -438,13 +411,14 @@ __global__ void __launch_bounds__(kChunkThreads, 1) k_pts_inference_chunks(Infer
             cb[c] = a.t.corners[3 * b + c];
             sb[c] = a.t.sizes[3 * b + c];
         }
+        // the wave's groups of this chunk (a ragged last one included)
+        const int64_t rem = total - wbase;
+        const int ng = rem <= 0 ? 0 : (int)(rem >= (int64_t)kWaveGroups * 32 ? kWaveGroups : (rem + 31) / 32);
+        const char *table = (const char *)a.tables + (size_t)b * 16 * a.T * 4;
       if constexpr (PIPE) {
         // Software pipeline over the wave's groups that run this tile's decoder: while group g is decoded, the 64 corner
         // loads of the next running group and the per-sample inputs of the group after it are in flight (the kernel is bound
         // by the round trips of these loads, not by their number -- DESIGN.md 4.8).
-        const int64_t rem = total - wbase;
-        const int ng = rem <= 0 ? 0 : (int)(rem >= (int64_t)kWaveGroups * 32 ? kWaveGroups : (rem + 31) / 32);
-        const char *table = (const char *)a.tables + (size_t)b * 16 * a.T * 4;
         int rso = 6 * h;  // (opaque, or every rscale address becomes its own lane-dependent register instead of base + immediate)
         asm volatile("" : "+v"(rso));
         const float *rsh = rscale + rso;
@@ -456,7 +430,14 @@ __global__ void __launch_bounds__(kChunkThreads, 1) k_pts_inference_chunks(Infer
         if (ng > 0) group_load<BG>(a, total, wbase, sl, in);
         auto advance = [&](GroupPrep &P, int sl_) -> bool {  // the next group with samples to decode; keeps one group of inputs ahead
             while (g_in < ng) {
-                const bool r = group_prep<BG>(a, b, cb, sb, in, P, p01, ppark[wave][sl_], lane);
+                // (direction, depth step, blend weight and 1/sum of weights wait in LDS for the output stage -- registers the
+                // compiler would otherwise spill to scratch, whose reloads wait behind the gathers in flight)
+                float st[6];
+                const bool r = group_prep<BG>(a, b, cb, sb, in, P, p01, st);
+                if (r) {
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) ppark[wave][sl_][k][lane] = st[k];
+                }
                 ++g_in;
                 if (g_in < ng) group_load<BG>(a, total, wbase + (int64_t)g_in * 32, sl, in);
                 if (r) return true;
@@ -482,133 +463,26 @@ __global__ void __launch_bounds__(kChunkThreads, 1) k_pts_inference_chunks(Infer
                 h3_dinit(lds, lane, sh, dinit);
             }
             const SampleOut so = decode_tile_h3(lds, lane, x, dinit);
-            if (cur.run && h == 0) {
-                const uint32_t e = cur.e;
-                const float delta = pk[3][lane], w_b = pk[4][lane], inv = pk[5][lane];
-                const float pa = 1.0f - expf(-1.0f * so.sigma * delta);
-                if (BG) {
-                    a.out_alpha[e] = pa;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        a.out_dif[3 * (size_t)e + c] = pa * so.dif[c];
-                        a.out_spec[3 * (size_t)e + c] = pa * (so.tint[c] * so.spec[c]);
-                    }
-                } else {
-                    a.out_alpha[e] += (w_b * pa) * inv;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        a.out_dif[3 * (size_t)e + c] += (w_b * pa * so.dif[c]) * inv;
-                        a.out_spec[3 * (size_t)e + c] += (w_b * pa * (so.tint[c] * so.spec[c])) * inv;
-                    }
-                }
-            }
+            if (cur.run && h == 0) group_store<BG>(a, cur.e, so, pk[3][lane], pk[4][lane], pk[5][lane]);
             cur = nxt;
             slot_cur ^= 1;
             have = more;
         }
       } else {
+        // the same steps one group at a time: nothing in flight across the decoder
+        GroupIn in;
+        GroupPrep cur;
+        float p01[3], st[6];
 #pragma unroll 1
-      for (int g = 0; g < kWaveGroups; ++g) {
-        const int64_t base = wbase + g * 32;
-        if (base >= total) break;
-        const int64_t e = base + sl;
-        const bool in_range = e < total;
-        const int64_t ec = in_range ? e : total - 1;
-        // (32-bit division: the host keeps B*S below 2^31 for this kernel; a 64-bit one costs ~100 instructions per group)
-        int i, s;
-        pt_decompose((uint32_t)ec, (uint32_t)a.B, (uint32_t)a.S, a.sm, i, s);
-        // does this sample list tile b?  (fg: the slot list stops at the first -1, rendering_kernel.cu:499)
-        int16_t slot[kMaxPtsBlocks] = { -1, -1, -1, -1 };
-        bool mine = false;
-        if (BG) {
-            mine = in_range && a.block_idxs[i * kMaxPtsBlocks + a.step] == b;
-        } else if (in_range) {
-            const uint2 raw = *reinterpret_cast<const uint2 *>(a.block_idxs + ec * kMaxPtsBlocks);
-            slot[0] = (int16_t)(raw.x & 0xffffu); slot[1] = (int16_t)(raw.x >> 16);
-            slot[2] = (int16_t)(raw.y & 0xffffu); slot[3] = (int16_t)(raw.y >> 16);
-            bool ended = false;
-#pragma unroll
-            for (int k = 0; k < kMaxPtsBlocks; ++k) {
-                ended |= slot[k] == -1;
-                if (ended) slot[k] = -1;
-                mine |= slot[k] == b;
-            }
+        for (int g = 0; g < ng; ++g) {
+            group_load<BG>(a, total, wbase + (int64_t)g * 32, sl, in);
+            if (!group_prep<BG>(a, b, cb, sb, in, cur, p01, st)) continue;  // wave-uniform: nothing of this group is occupied (the outputs stay as they are)
+            v16f x;
+            encode8_01<SCANERF_F16, RT_GATHER_BATCH, RT_STRAIGHT>(table, a.res + (size_t)b * 48, a.T, h, p01, cur.run, x);
+            const float d[3] = { st[0], st[1], st[2] };
+            const SampleOut so = decode_tile_h3<true>(lds, lane, x, nullptr, d, 0.0f);
+            if (cur.run && h == 0) group_store<BG>(a, cur.e, so, st[3], st[4], st[5]);
         }
-        if (!__any(mine)) continue;  // wave-uniform
-        float o[3], d[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            o[k] = a.rays_o[3 * i + k];
-            d[k] = a.rays_d[3 * i + k];
-        }
-        const float dnorm = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-        const float z = a.z_vals[ec];
-        float delta;
-        if (BG) delta = (s == a.S - 1) ? 10000000.0f : a.z_vals[ec + pt_sample_stride(a.B, a.sm)] - z;   // :1045-1047: raw depth step
-        else delta = a.dists[ec] * dnorm;                                       // :557
-        float p01[3], w_b = 0.0f, weight = 0.0f;
-        bool run = mine;
-        if (BG) {
-            float q[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) q[c] = 2.0f * ((o[c] + z * d[c]) - cb[c]) / sb[c] - 1.0f;
-            const float linf = fmaxf(fabsf(q[0]), fmaxf(fabsf(q[1]), fabsf(q[2])));
-            const float ratio = (2.0f - 1.0f / linf) / linf;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) p01[c] = (q[c] * ratio + 2.0f) / 4.0f;
-        } else {
-            // blend weights of every listed tile (occupied or not, :523-541), this tile's cell and position
-#pragma unroll
-            for (int k = 0; k < kMaxPtsBlocks; ++k) {
-                const int bk = slot[k];
-                if (bk == -1) continue;
-                float dis[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float sz = a.t.sizes[3 * bk + c];
-                    const float pt = ((o[c] + z * d[c]) - a.t.corners[3 * bk + c]) / sz;
-                    dis[c] = (0.5f - fabsf(pt - 0.5f)) * sz;
-                }
-                const float w = xz_weight(dis[0], dis[2]);
-                weight += w;
-                if (bk == b) w_b = w;
-            }
-            int loc[3];
-            const int l2d[3] = { a.t.log2dim[3 * b], a.t.log2dim[3 * b + 1], a.t.log2dim[3 * b + 2] };
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float pt = ((o[c] + z * d[c]) - cb[c]) / sb[c];
-                const int r = 1 << l2d[c];
-                const int cc = (int)(pt * (float)r);
-                loc[c] = cc < 0 ? 0 : (cc > r - 1 ? r - 1 : cc);
-                p01[c] = pt / 2.0f + 0.25f;  // tile -> the middle half of the 2x box (:548)
-            }
-            if (mine) run = a.t.occ[a.t.grid_starts[b] + cell_offset(loc, l2d[1], l2d[2])] != 0;
-        }
-        if (!__any(run)) continue;  // wave-uniform: nothing of this group is occupied (the outputs stay as they are)
-        v16f x;
-        encode8_01<SCANERF_F16, RT_GATHER_BATCH, RT_STRAIGHT>((const char *)a.tables + (size_t)b * 16 * a.T * 4, a.res + (size_t)b * 48, a.T, h, p01, run, x);
-        const SampleOut so = decode_tile_h3<true>(lds, lane, x, nullptr, d, 0.0f);
-        if (run && h == 0) {
-            const float pa = 1.0f - expf(-1.0f * so.sigma * delta);
-            if (BG) {
-                a.out_alpha[e] = pa;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    a.out_dif[3 * e + c] = pa * so.dif[c];
-                    a.out_spec[3 * e + c] = pa * (so.tint[c] * so.spec[c]);
-                }
-            } else {
-                const float inv = weight > 0 ? 1.0f / weight : 1.0f;
-                a.out_alpha[e] += (w_b * pa) * inv;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    a.out_dif[3 * e + c] += (w_b * pa * so.dif[c]) * inv;
-                    a.out_spec[3 * e + c] += (w_b * pa * (so.tint[c] * so.spec[c])) * inv;
-                }
-            }
-        }
-      }
       }
       }
     }
@@ -744,70 +618,19 @@ __global__ void __launch_bounds__(kT16Threads, 4) k_pts_inference_t16(InferArgs 
             }
             if (threadIdx.x < 16) reinterpret_cast<float *>(shrows + 64 * kShRows)[threadIdx.x] = 0.0f;   // the row of the lanes with q >= 2
         }
-        {   // 1. the tiles this chunk's samples list
-            uint32_t mlo = 0, mhi = 0;
-            auto mark = [&](int t) {
-                if (t >= 0) {
-                    if (t < 32) mlo |= 1u << t;
-                    else mhi |= 1u << (t - 32);
-                }
-            };
-#pragma unroll
-            for (int g = 0; g < kT16WaveGroups; ++g) {
-                const int64_t e = wbase + g * 64 + lane;
-                if (e >= total) continue;
-                const uint32_t e32 = (uint32_t)e;
-                if (BG) {
-                    int ri, rs;
-                    pt_decompose(e32, (uint32_t)a.B, (uint32_t)a.S, a.sm, ri, rs);
-                    const int tb = a.block_idxs[ri * kMaxPtsBlocks + a.step];
-                    mark(tb);
-                    if (tb < 0) {  // no background tile at this blend step: the sample's outputs are zero (the caller need not clear them)
-                        a.out_alpha[e] = 0.0f;
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) {
-                            a.out_dif[3 * e + c] = 0.0f;
-                            a.out_spec[3 * e + c] = 0.0f;
-                        }
-                    }
-                } else {
-                    uint2 raw;
-                    bool unsampled = false;
-                    if constexpr (TR) {
-                        int ri, rs;
-                        pt_decompose(e32, (uint32_t)a.B, (uint32_t)a.S, a.sm, ri, rs);
-                        raw = tracing_slots(a, ri, a.z_vals[e]);
-                        // (sample_points fills a ray's depths from index 0: a first depth of -1 = a ray without samples in this pass,
-                        // which the accumulation under the same flag does not read)
-                        unsampled = a.skip_unsampled && a.z_vals[pt_index(ri, 0, a.B, a.S, a.sm)] == -1.0f;
-                    } else {
-                        raw = *reinterpret_cast<const uint2 *>(a.block_idxs + (size_t)e32 * kMaxPtsBlocks);
-                    }
-                    const int s0 = (int16_t)(raw.x & 0xffffu), s1 = (int16_t)(raw.x >> 16), s2 = (int16_t)(raw.y & 0xffffu),
-                              s3 = (int16_t)(raw.y >> 16);
-                    mark(s0);  // the list stops at the first -1 (rendering_kernel.cu:499)
-                    if (s0 != -1) { mark(s1); if (s1 != -1) { mark(s2); if (s2 != -1) mark(s3); } }
-                    else if (!unsampled) {   // no tile: zeros (:569-571).  Every other sample is WRITTEN by the step of its first listed tile and added
-                             // to by the later ones, so the caller's arrays need no clearing pass (7.4 GB per launch at 1920x1080x128)
-                        a.out_alpha[e] = 0.0f;
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) {
-                            a.out_dif[3 * e + c] = 0.0f;
-                            a.out_spec[3 * e + c] = 0.0f;
-                        }
-                    }
-                }
+        // 1. the tiles this chunk's samples list; samples without a tile get their zeros here
+        chunk_tileset<BG, 64, kT16WaveGroups, true>(a, wbase, total, lane, tileset, [&](uint32_t e, bool &unsampled) {
+            if constexpr (TR) {
+                int ri, rs;
+                pt_decompose(e, (uint32_t)a.B, (uint32_t)a.S, a.sm, ri, rs);
+                // (sample_points fills a ray's depths from index 0: a first depth of -1 = a ray without samples in this pass,
+                // which the accumulation under the same flag does not read)
+                unsampled = a.skip_unsampled && a.z_vals[pt_index(ri, 0, a.B, a.S, a.sm)] == -1.0f;
+                return tracing_slots(a, ri, a.z_vals[e]);
+            } else {
+                return load_slots(a, e);
             }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                mlo |= __shfl_xor(mlo, off, 64);
-                mhi |= __shfl_xor(mhi, off, 64);
-            }
-            if (lane == 0) {
-                if (mlo) atomicOr(&tileset[0], mlo);
-                if (mhi) atomicOr(&tileset[1], mhi);
-            }
-        }
+        });
         __syncthreads();
         uint64_t todo = (uint64_t)tileset[0] | ((uint64_t)tileset[1] << 32);
         while (todo) {  // 2. one step per listed tile, ascending
@@ -842,85 +665,36 @@ __global__ void __launch_bounds__(kT16Threads, 4) k_pts_inference_t16(InferArgs 
                 // (32-bit index arithmetic: the host keeps B*S below 2^31 for this kernel)
                 int i, s;
                 pt_decompose(ec, (uint32_t)a.B, (uint32_t)a.S, a.sm, i, s);
-                // does this sample list tile b?  (fg: the slot list stops at the first -1, rendering_kernel.cu:499)
-                int16_t slot[kMaxPtsBlocks] = { -1, -1, -1, -1 };
+                // does this sample list tile b?
+                int slot[kMaxPtsBlocks] = { -1, -1, -1, -1 };
                 bool mine = false, first = false;   // first: b is the sample's first listed tile (fg): this step writes, later ones add
                 if (BG) {
                     mine = in_range && a.block_idxs[i * kMaxPtsBlocks + a.step] == b;
                 } else if (in_range) {
-                    const uint2 raw = TR ? tracing_slots(a, i, a.z_vals[ec]) : *reinterpret_cast<const uint2 *>(a.block_idxs + (size_t)ec * kMaxPtsBlocks);
-                    slot[0] = (int16_t)(raw.x & 0xffffu); slot[1] = (int16_t)(raw.x >> 16);
-                    slot[2] = (int16_t)(raw.y & 0xffffu); slot[3] = (int16_t)(raw.y >> 16);
+                    slot_list(TR ? tracing_slots(a, i, a.z_vals[ec]) : load_slots(a, ec), slot);
                     first = slot[0] == b;
-                    bool ended = false;
-#pragma unroll
-                    for (int k = 0; k < kMaxPtsBlocks; ++k) {
-                        ended |= slot[k] == -1;
-                        if (ended) slot[k] = -1;
-                        mine |= slot[k] == b;
-                    }
+                    mine = slots_list_tile(slot, b);
                 }
                 if (!__any(mine)) continue;  // wave-uniform
-                float o[3], d[3];
+                float o[3], d[3], wp[3];
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
                     o[k] = a.rays_o[3 * i + k];
                     d[k] = a.rays_d[3 * i + k];
                 }
                 const float z = a.z_vals[ec];
+                world_point(o, z, d, wp);
                 float delta;
                 if (BG) delta = (s == a.S - 1) ? 10000000.0f : a.z_vals[ec + (uint32_t)pt_sample_stride(a.B, a.sm)] - z;   // :1045-1047: raw depth step
                 else delta = a.dists[ec] * sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);                               // :557
                 float p01[3], w_b = 0.0f, weight = 0.0f;
                 bool run = mine;
-                if (BG) {
-                    float qq[3];
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) qq[c] = 2.0f * ((o[c] + z * d[c]) - cb[c]) / sb[c] - 1.0f;
-                    const float linf = fmaxf(fabsf(qq[0]), fmaxf(fabsf(qq[1]), fabsf(qq[2])));
-                    const float ratio = (2.0f - 1.0f / linf) / linf;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) p01[c] = (qq[c] * ratio + 2.0f) / 4.0f;
-                } else {
-                    // blend weights of every listed tile (occupied or not, :523-541), this tile's cell and position
-#pragma unroll
-                    for (int k = 0; k < kMaxPtsBlocks; ++k) {
-                        const int bk = slot[k];
-                        if (bk == -1) continue;
-                        float dis[3];
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) {
-                            const float sz = a.t.sizes[3 * bk + c];
-                            const float pt = ((o[c] + z * d[c]) - a.t.corners[3 * bk + c]) / sz;
-                            dis[c] = (0.5f - fabsf(pt - 0.5f)) * sz;
-                        }
-                        const float w = xz_weight(dis[0], dis[2]);
-                        weight += w;
-                        if (bk == b) w_b = w;
-                    }
-                    int loc[3];
-                    const int l2d[3] = { a.t.log2dim[3 * b], a.t.log2dim[3 * b + 1], a.t.log2dim[3 * b + 2] };
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const float pt = ((o[c] + z * d[c]) - cb[c]) / sb[c];
-                        const int r = 1 << l2d[c];
-                        const int cc = (int)(pt * (float)r);
-                        loc[c] = cc < 0 ? 0 : (cc > r - 1 ? r - 1 : cc);
-                        p01[c] = pt / 2.0f + 0.25f;  // tile -> the middle half of the 2x box (:548)
-                    }
-                    if (mine) run = a.t.occ[a.t.grid_starts[b] + cell_offset(loc, l2d[1], l2d[2])] != 0;
-                }
-                if (!BG && first && !run) {   // listed but not occupied here: the sample's value starts at zero
-                    a.out_alpha[ec] = 0.0f;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        a.out_dif[3 * (size_t)ec + c] = 0.0f;
-                        a.out_spec[3 * (size_t)ec + c] = 0.0f;
-                    }
-                }
+                if (BG) bg_p01(wp, cb, sb, p01);
+                else run = fg_sample(a.t, slot, b, cb, sb, wp, mine, p01, w_b, weight);
+                if (!BG && first && !run) zero_sample(a.out_dif, a.out_spec, a.out_alpha, ec);   // listed but not occupied here: the sample's value starts at zero
                 const uint64_t rm = __ballot(run);
                 if (!rm) continue;  // wave-uniform: nothing of this group is occupied
-                const float inv = weight > 0 ? 1.0f / weight : 1.0f;
+                const float inv = inv_weight(weight);
                 int shrow = i - r0;   // this sample's ray's row (bytes); the host launches SHT only where every chunk's range fits
                 shrow = 64 * (shrow < kShRows ? shrow : kShRows);
 #pragma unroll 1
@@ -952,26 +726,20 @@ __global__ void __launch_bounds__(kT16Threads, 4) k_pts_inference_t16(InferArgs 
                         so = decode_tile_s16<false, decltype(gate), FOLD>(lds, lane, xa, xb, dd, 0.0f, nullptr, gate);
                     }
                     if (BG) {
-                        if (act && q == 0) {
-                            const float pa = pa_keep;
-                            a.out_alpha[es] = pa;
-#pragma unroll
-                            for (int c = 0; c < 3; ++c) {
-                                a.out_dif[3 * (size_t)es + c] = pa * so.dif[c];
-                                a.out_spec[3 * (size_t)es + c] = pa * (so.tint[c] * so.spec[c]);
-                            }
-                        }
+                        if (act && q == 0) store_bg(a.out_dif, a.out_spec, a.out_alpha, es, pa_keep, so);
                     } else {
                         const float wb = __shfl(w_b, src, 64), iv = __shfl(inv, src, 64);
                         const bool fst = __shfl((int)first, src, 64) != 0;
                         if (act && q == 0) {
-                            const float pa = pa_keep;
-                            // (0 + x == x exactly: writing x where the cleared array held 0 gives the bits the += gave)
-                            a.out_alpha[es] = (fst ? 0.0f : a.out_alpha[es]) + (wb * pa) * iv;
+                            float v[7];
+                            fg_values(wb, pa_keep, iv, so, v);
+                            // the first listed tile's step writes, later ones add (0 + x == x exactly: writing x where the
+                            // cleared array held 0 gives the bits the += gave)
+                            a.out_alpha[es] = (fst ? 0.0f : a.out_alpha[es]) + v[6];
 #pragma unroll
                             for (int c = 0; c < 3; ++c) {
-                                a.out_dif[3 * (size_t)es + c] = (fst ? 0.0f : a.out_dif[3 * (size_t)es + c]) + (wb * pa * so.dif[c]) * iv;
-                                a.out_spec[3 * (size_t)es + c] = (fst ? 0.0f : a.out_spec[3 * (size_t)es + c]) + (wb * pa * (so.tint[c] * so.spec[c])) * iv;
+                                a.out_dif[3 * (size_t)es + c] = (fst ? 0.0f : a.out_dif[3 * (size_t)es + c]) + v[c];
+                                a.out_spec[3 * (size_t)es + c] = (fst ? 0.0f : a.out_spec[3 * (size_t)es + c]) + v[3 + c];
                             }
                         }
                     }

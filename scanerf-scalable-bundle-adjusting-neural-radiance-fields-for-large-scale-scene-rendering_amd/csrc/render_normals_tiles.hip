@@ -1,7 +1,8 @@
 // render_normals_tiles.hip -- normal maps of the multi-tile novel-view render: pts_normals blends the tiles' density
 // normals per sample exactly as pts_inference blends their colours (rendering_kernel.cu:467-581), accumulate_normal composites them
 // per ray by accumulate_color's rule (:624-702).  The reference has no multi-tile normal; the definition is scanerf_hip.h's.
-// Built with -ffp-contract=off, as render_time.hip and render_infer.hip: the position, weight and cell expressions are theirs.
+// Built with -ffp-contract=off, as render_time.hip and render_infer.hip: the slot list, position, weight, cell and table
+// coordinate are render_infer_device.h's, the one definition that both units evaluate.
 //
 // The per-sample mathematics is normals.hip's (normals_device.h: one gather pass with the three position tangents, the 64 x 32
 // first-layer product on v_mfma_f32_32x32x2_f32, the density path in closed form).  New here: the tile varies per lane and per
@@ -16,7 +17,7 @@
 // A sample's slots are therefore processed in an order that depends on its wave's other samples; each slot's contribution is
 // parked (LDS, lane-private) and summed afterwards in SLOT order, so a sample's bits do not depend on layout, ray order or launch.
 #include "normals_device.h"
-#include "render_time_common.h"
+#include "render_infer_device.h"
 
 using namespace scanerf;
 
@@ -64,17 +65,7 @@ __global__ void __launch_bounds__(kTnThreads) __attribute__((amdgpu_waves_per_eu
         pt_decompose(ec, (uint32_t)a.B, (uint32_t)a.S, a.sm, i, s);
         // the slot list: ends at the first -1 (:499); a tile index outside [0, nb) ends it too (nothing is read for it)
         int slot[kMaxPtsBlocks] = { -1, -1, -1, -1 };
-        if (in_range) {
-            const uint2 raw = *reinterpret_cast<const uint2 *>(a.block_idxs + (size_t)ec * kMaxPtsBlocks);
-            slot[0] = (int16_t)(raw.x & 0xffffu); slot[1] = (int16_t)(raw.x >> 16);
-            slot[2] = (int16_t)(raw.y & 0xffffu); slot[3] = (int16_t)(raw.y >> 16);
-            bool ended = false;
-#pragma unroll
-            for (int k = 0; k < kMaxPtsBlocks; ++k) {
-                ended |= slot[k] < 0 || slot[k] >= nb;
-                if (ended) slot[k] = -1;
-            }
-        }
+        if (in_range) slot_list_bounded(*reinterpret_cast<const uint2 *>(a.block_idxs + (size_t)ec * kMaxPtsBlocks), nb, slot);
         float *o3 = a.out + 3 * (size_t)ec;
         if (!__any(slot[0] != -1)) {   // wave-uniform: nothing listed in the whole group (unsampled rays, z == -1)
             if (in_range) o3[0] = o3[1] = o3[2] = 0.0f;
@@ -82,12 +73,13 @@ __global__ void __launch_bounds__(kTnThreads) __attribute__((amdgpu_waves_per_eu
         }
         float wp[3] = { 0.0f, 0.0f, 0.0f }, delta = 0.0f;   // world position; what multiplies sigma in pa
         if (slot[0] != -1) {
-            float d[3];
+            float o[3], d[3];
 #pragma unroll
-            for (int k = 0; k < 3; ++k) d[k] = a.rays_d[3 * (size_t)i + k];
-            const float z = a.z_vals[ec];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) wp[k] = a.rays_o[3 * (size_t)i + k] + z * d[k];
+            for (int k = 0; k < 3; ++k) {
+                o[k] = a.rays_o[3 * (size_t)i + k];
+                d[k] = a.rays_d[3 * (size_t)i + k];
+            }
+            world_point(o, a.z_vals[ec], d, wp);
             delta = a.dists[ec] * sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);   // :557
         }
         // blend weights of every listed tile (they count whether or not the cell is occupied) and the slots that run
@@ -98,21 +90,11 @@ __global__ void __launch_bounds__(kTnThreads) __attribute__((amdgpu_waves_per_eu
             const int bk = slot[k];
             float w = 0.0f;
             if (bk != -1) {
-                float dis[3];
-                int loc[3];
-                const int l2d[3] = { a.t.log2dim[3 * bk], a.t.log2dim[3 * bk + 1], a.t.log2dim[3 * bk + 2] };
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    const float sz = a.t.sizes[3 * bk + q];
-                    const float pt = (wp[q] - a.t.corners[3 * bk + q]) / sz;
-                    dis[q] = (0.5f - fabsf(pt - 0.5f)) * sz;
-                    const int r = 1 << l2d[q];
-                    const int cc = (int)(pt * (float)r);
-                    loc[q] = cc < 0 ? 0 : (cc > r - 1 ? r - 1 : cc);
-                }
-                w = xz_weight(dis[0], dis[2]);
+                float pt[3];
+                tile_point(wp, a.t.corners + 3 * bk, a.t.sizes + 3 * bk, pt);
+                w = tile_weight(pt, a.t.sizes + 3 * bk);
                 weight += w;
-                if (a.t.occ[a.t.grid_starts[bk] + cell_offset(loc, l2d[1], l2d[2])] != 0) pend |= 1u << k;
+                if (a.t.occ[tile_cell(a.t, bk, pt)] != 0) pend |= 1u << k;
             }
             lds[TL_W + k * 64 + lane] = w;
         }
@@ -151,11 +133,13 @@ __global__ void __launch_bounds__(kTnThreads) __attribute__((amdgpu_waves_per_eu
                 n_lanes += (unsigned int)__popcll(__ballot(mine));
             }
             float asc[3], p01[3] = { 0.0f, 0.0f, 0.0f };   // (lanes without this tile: cell 0 of every level, one line per level)
+            // (component by component, each beside its 2 / size: with tile_point / fg_p01 over the three at once the counted
+            // kernel spills two registers more)
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
                 const float sz = a.t.sizes[3 * b + q];
                 asc[q] = 2.0f / sz;   // the contracted coordinate is 2 pts - 1
-                if (mine) p01[q] = (wp[q] - a.t.corners[3 * b + q]) / sz / 2.0f + 0.25f;   // :548
+                if (mine) p01[q] = fg_coord(tile_coord(wp[q], a.t.corners[3 * b + q], sz));   // :548
             }
             float sg, gsum[3], sigma, g[3], n[3];
             density_grad<SCANERF_F16, true>(lds, (const char *)a.tables + (size_t)b * 16 * a.T * 4, a.T, asc, c, lane, p01, sg, gsum);

@@ -1,4 +1,4 @@
-"""What is the wrong value?  (the forward kernel built with H3_OPAQUE_ADDR=1 writes, in ~1 of 500 cold launches,
+"""What is the wrong value?  (DESIGN.md §4.1 (last paragraph); profiles/DESIGN_r04_experiment_log.md §4.10: the forward kernel built with H3_OPAQUE_ADDR=1 writes, in ~1 of 500 cold launches,
 one wrong encoder output for lanes 48-63 of a tile.)  For every faulty x-stash element: the right value, the wrong value, and the
 candidates -- the 8 corner values of the half-wave's LAST level (15: the loads whose destination registers the copy reuses)."""
 import os, sys, torch

@@ -12,7 +12,7 @@ DEV = "cuda:0"
 
 def test_the_library_under_test_is_the_audited_build():
     """The reproducibility these tests establish belongs to ONE compiled listing per kernel (csrc/isa_manifest.json; no packed-f32
-    arithmetic).  A library built around the audit (SCANERF_SKIP_ISA_AUDIT=1) or changed after it is refused here."""
+    arithmetic, DESIGN.md §4.1 (last paragraph); profiles/DESIGN_r04_experiment_log.md §4.10).  A library built around the audit (SCANERF_SKIP_ISA_AUDIT=1) or changed after it is refused here."""
     import scanerf_amd  # noqa: F401
     from scanerf_amd import _capi
     st = _capi.audit_state()
@@ -123,7 +123,7 @@ def test_forward_with_cold_instruction_caches_is_bit_reproducible(dt, pose):
     """The forward that also counts the scatter plan (and, pose: writes the position-Jacobian stash), 8 192 rays x 128 samples,
     300 launches with the instruction caches swept before each one (scanerf_icache_sweep: 300 KB of straight-line code on every
     CU).  This is the condition under which the forward built with packed-f32 (w, w) weight pairs lost one corner's term in lanes
-    48-63 of a tile in 8 % of the launches (tools/fault_probe.py: the sweep alone brings the fault out, poisoning
+    48-63 of a tile in 8 % of the launches (DESIGN.md §4.1 (last paragraph); profiles/DESIGN_r04_experiment_log.md §4.10; tools/fault_probe.py: the sweep alone brings the fault out, poisoning
     every register and all LDS between launches does not).  Back-to-back launches of one kernel never showed it."""
     from conftest import need_symbol
     need_symbol("scanerf_icache_sweep")
@@ -159,7 +159,7 @@ def test_forward_with_cold_instruction_caches_is_bit_reproducible(dt, pose):
 def test_whole_training_step_is_bit_reproducible(fgbg, pose):
     """The default step end to end -- forward that counts the scatter plan, t16 backward emitting 8-byte records, integer
     accumulate + sparse Adam -- run twelve times from the same state on 8 192 rays x 128 samples, each time on a FRESH model (cold
-    caches, new allocations: the context in which a re-allocated forward kernel failed in ~6 % of the first launches):
+    caches, new allocations: the context in which a re-allocated forward kernel failed in ~6 % of the first launches, DESIGN.md §4.1 (last paragraph); profiles/DESIGN_r04_experiment_log.md §4.10):
     table, moments and decoder after three iterations agree bit for bit (no float atomics anywhere on the path; the
     reference's scatter is not reproducible).  Also the foreground + background iteration (two record sets, one Adam), and both
     with pose gradients (Jacobian-stash forward, POSE backward; the ray gradients are hashed too)."""

@@ -63,12 +63,12 @@ def from_layout(a, lay):
     return np.swapaxes(a, 1, 2).reshape(a.shape[0] * 32, a.shape[1], *a.shape[3:])[:B]
 
 
-def run_pts_normals(name, ins, lay):
-    """pts_normals on the case's inputs in the layout, the output prefilled with NaN -> [B,S,3] numpy"""
+def run_pts_normals(name, ins, lay, counts=None):
+    """pts_normals on the case's inputs in the layout, the output prefilled with NaN -> [B,S,3] numpy (counts: the counted launch)"""
     rays = (g(pad32(ins["o"])), g(pad32(ins["d"]))) if lay == 2 else (g(ins["o"]), g(ins["d"]))
     z, dd, bi = (g(to_layout(ins[k], lay)) for k in ("z", "dd", "bi"))
     out = torch.full(tuple(z.shape) + (3,), float("nan"), device=DEV)
-    ops().pts_normals(*rays, z, dd, bi, *dev_scene(name), out, sample_major=lay)
+    ops().pts_normals(*rays, z, dd, bi, *dev_scene(name), out, sample_major=lay, counts=counts)
     return from_layout(n(out), lay)
 
 
@@ -86,6 +86,15 @@ def test_pts_normals_per_sample(name, S, order):
     assert none.sum() > 0 and not got[2].reshape(-1, 3)[none].any()
     assert np.array_equal(got[0], got[1]) and np.array_equal(got[0], got[2]), "the layouts differ"
     assert np.array_equal(got[2], run_pts_normals(name, ins, 2)), "two launches differ"
+    # the counted launch (the measurement entry point's own kernel instance) must give the same bits: that is the check.  The
+    # counters (groups that ran a tile, stagings, passes of the tile loop, lanes with a sample in them) are only held to what any
+    # correct count satisfies; a miscounted staging or pass inside these ranges would go unnoticed
+    counts = torch.zeros(4, dtype=torch.int32, device=DEV)
+    assert np.array_equal(got[2], run_pts_normals(name, ins, 2, counts=counts)), "the counted launch differs"
+    groups, stagings, passes, lanes = (int(c) for c in n(counts))
+    pin = r64["pin"]
+    assert 0 < groups <= -(-BP * S // 64) and 1 <= stagings <= passes and groups <= passes and 0 < lanes <= 64 * passes
+    assert lanes >= int((pin["listed"] & pin["occ"]).sum()), "an occupied listed slot was not served"
     if name == "G9Z":   # the zero-table tile alone: no normal at all
         pin = r64["pin"]
         only = (pin["listed"].sum(1) == 1) & pin["occ"][:, 0] & (pin["b"][:, 0] == R.ZERO_TILE)

@@ -213,7 +213,7 @@ def test_pipelined_group_loop_gives_the_bits_of_the_plain_one(monkeypatch):
     assert piped[2].max() > 0.05 and piped[5].max() > 0.05
     for a, b in zip(piped, plain):
         assert np.array_equal(a, b)
-    # and launch after launch (no atomics on this path: any difference is a hazard the generated code does not cover);
+    # and launch after launch (no atomics on this path: any difference is a hazard the generated code does not cover, DESIGN.md §4.1 (last paragraph); profiles/DESIGN_r04_experiment_log.md §4.10);
     # other work in between, so that the tables are not always warm
     monkeypatch.delenv("SCANERF_RENDER_PIPE", raising=False)
     scratch = torch.empty(256 << 20, dtype=torch.uint8, device=DEV)
@@ -224,10 +224,18 @@ def test_pipelined_group_loop_gives_the_bits_of_the_plain_one(monkeypatch):
             assert np.array_equal(a, b), f"launch {rep} differs"
 
 
-@pytest.mark.parametrize("B,S", [(1000, 72), (3000, 16)])
-def test_inference_that_derives_its_slot_lists_equals_prepare_points_then_pts_inference(B, S):
+# (fold: the images carry the activation constant, the default; the "-plain" cases run the unfolded 16-sample-tile kernels, which
+# nothing else in the suite launches)
+FOLD_CASES = [pytest.param(1000, 72, True, id="1000-72"), pytest.param(3000, 16, True, id="3000-16"),
+              pytest.param(1000, 72, False, id="1000-72-plain"), pytest.param(3000, 16, False, id="3000-16-plain")]
+
+
+@pytest.mark.parametrize("B,S,fold", FOLD_CASES)
+def test_inference_that_derives_its_slot_lists_equals_prepare_points_then_pts_inference(monkeypatch, B, S, fold):
     """pts_inference_tracing (one launch, no block_idxs array) against prepare_points + pts_inference: bit for bit, with a third
     of the rays stopped; and every sample written whatever the arrays held."""
+    from scanerf_amd.hashgrid.lib import HASHGRID as _HG
+    monkeypatch.setattr(_HG, "FOLD_ACTIVATION", fold)
     c = _inference_case(B, S, seed=13).ctx
     H = c["H"]
     running = (torch.arange(B, device=DEV) % 3 != 1).contiguous()
@@ -281,8 +289,8 @@ def test_tiles_of_zero_opacity_skip_the_directional_layers_and_change_nothing(mo
         np.testing.assert_allclose(a, b, rtol=2e-5, atol=2e-6)
 
 
-@pytest.mark.parametrize("B,S", [(1000, 72), (517, 128), (3000, 16)])
-def test_sixteen_sample_tile_kernel_against_the_32_sample_one(monkeypatch, B, S):
+@pytest.mark.parametrize("B,S,fold", FOLD_CASES[:1] + [pytest.param(517, 128, True, id="517-128")] + FOLD_CASES[1:])
+def test_sixteen_sample_tile_kernel_against_the_32_sample_one(monkeypatch, B, S, fold):
     """k_pts_inference_t16 (default: 16-sample tiles, four waves per SIMD, the chunk's SH operands in LDS) against
     k_pts_inference_chunks (SCANERF_RENDER_ARITH=h3): both evaluate the split-f16 decoder, with different k-step groupings, so
     they agree to f32 rounding; the SH rows change where the harmonics are evaluated, not their bits (SCANERF_RENDER_SH_ROWS=0:
@@ -290,6 +298,7 @@ def test_sixteen_sample_tile_kernel_against_the_32_sample_one(monkeypatch, B, S)
     default repeats launch after launch."""
     from conftest import experiments_build
     from scanerf_amd.hashgrid.lib import HASHGRID as _HG
+    monkeypatch.setattr(_HG, "FOLD_ACTIVATION", fold)
     run = _inference_case(B, S, seed=11)
     monkeypatch.delenv("SCANERF_RENDER_SH_ROWS", raising=False)
     t16 = run()

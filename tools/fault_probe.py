@@ -1,5 +1,5 @@
 """Which per-CU state does the withdrawn forward build's wrong encoder output depend on, and what IS the wrong value?
-(DESIGN.md 4.10.  Run with SCANERF_LIB=<pkg>/lib/debug/libscanerf_hip_<tag>.so -- built by
+(DESIGN.md §4.1 (last paragraph); profiles/DESIGN_r04_experiment_log.md §4.10.  Run with SCANERF_LIB=<pkg>/lib/debug/libscanerf_hip_<tag>.so -- built by
 `tools/build_variant.py <tag> render="-DH3_OPAQUE_ADDR=1 -fslp-vectorize"` -- for the withdrawn build, without it for the shipped
 one.  Needs tools/probe/libstate_poison.so: built here on first use, `hipcc --offload-arch=gfx950 -shared -fPIC`.)
 

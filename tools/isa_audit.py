@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""ISA audit of the hazard-sensitive kernels: the training / render-time kernels have been validated
+"""ISA audit of the hazard-sensitive kernels (DESIGN.md §4.1 (last paragraph); profiles/DESIGN_r04_experiment_log.md §4.10): the training / render-time kernels have been validated
 launch-to-launch bit-identical for ONE compiled listing each.  This tool pins those listings: per kernel of the audited
 translation units the spilled-register count, the instruction count and a digest of the instruction stream, next to the
 compiler version, in <pkg>/csrc/isa_manifest.json.
@@ -8,7 +8,7 @@ compiler version, in <pkg>/csrc/isa_manifest.json.
                                    under another compiler build it passes with status "unvalidated" when no packed-f32 is found)
     tools/isa_audit.py --update   (after re-validating on the GPU: tests/test_gpu_determinism.py + tools/fault_probe.py)
 
-Rule checked besides the digests (found the hard way):
+Rule checked besides the digests (found the hard way, DESIGN.md §4.1 (last paragraph); profiles/DESIGN_r04_experiment_log.md §4.10):
   * no kernel of a unit that runs matrix instructions holds packed-f32 arithmetic (v_pk_mul/add/fma_f32): those units are
     compiled with -fno-slp-vectorize.
 It reads the code objects out of the built .o files (llvm-objdump --offloading), never recompiles.
@@ -108,7 +108,7 @@ def main():
             write_state("failed", now, bad + why)
             raise SystemExit("isa_audit: " + "\n  ".join(bad + why))
         write_state("unvalidated", now, why)
-        print("isa_audit: WARNING: " + why[0] + "\n  no packed-f32 instruction in any kernel (the rule of DESIGN.md 4.10 holds); the "
+        print("isa_audit: WARNING: " + why[0] + "\n  no packed-f32 instruction in any kernel (the rule of DESIGN.md §4.1 (last paragraph); profiles/DESIGN_r04_experiment_log.md §4.10 holds); the "
               "library is marked UNVALIDATED: re-run tests/test_gpu_determinism.py + tools/fault_probe.py on the GPU, then "
               "tools/isa_audit.py --update", file=sys.stderr)
         return
@@ -123,7 +123,7 @@ def main():
                 bad.append(f"{u}: {k}: listing differs from the validated one (spills {r[k]['spills']} -> {n[k]['spills']}, "
                            f"instructions {r[k]['instructions']} -> {n[k]['instructions']})")
     if bad:
-        msg = ("isa_audit: the built kernels are not the validated listings (DESIGN.md 4.10):\n  " + "\n  ".join(bad) +
+        msg = ("isa_audit: the built kernels are not the validated listings (the rule: DESIGN.md 4.1, last paragraph; how it was found: profiles/DESIGN_r04_experiment_log.md 4.10):\n  " + "\n  ".join(bad) +
                "\nRe-validate on the GPU (python -m pytest tests/test_gpu_determinism.py; python tools/fault_probe.py) and then run "
                "tools/isa_audit.py --update; SCANERF_SKIP_ISA_AUDIT=1 builds anyway.")
         if os.environ.get("SCANERF_SKIP_ISA_AUDIT") == "1":

@@ -1,5 +1,5 @@
 // pk_hazard_probe.hip -- does a consumer that follows a packed-f32 instruction at the distance LLVM's hazard recogniser allows
-// for ANY vector instruction read the packed result correctly on gfx950?  (run ONCE: the loop inside is the soak.)
+// for ANY vector instruction read the packed result correctly on gfx950?  (DESIGN.md §4.1 (last paragraph); profiles/DESIGN_r04_experiment_log.md §4.10; run ONCE: the loop inside is the soak.)
 //   hipcc --offload-arch=gfx950 -O2 -o pk_hazard_probe pk_hazard_probe.hip && ./pk_hazard_probe
 // Producer (explicit registers, no compiler in between):  PK: v_pk_mul_f32 v[200:201] / v[202:203];  SC: four v_mul_f32 (control)
 // Gap: GAP wait states (s_nop GAP-1; 0 = back to back).  LLVM pads "VALU writes VGPR -> MFMA reads it" to 2 (s_waitcnt / s_nop).

@@ -1,4 +1,4 @@
-// state_poison.hip -- investigation tool: kernels that change ONE kind of per-CU state between two launches
+// state_poison.hip -- investigation tool (DESIGN.md §4.1 (last paragraph); profiles/DESIGN_r04_experiment_log.md §4.10): kernels that change ONE kind of per-CU state between two launches
 // of the kernel under test, so that a launch-to-launch difference can be pinned on that state:
 //   poison_regs_lds(pattern): every workgroup writes `pattern` into all 256 VGPRs of each of its 8 waves (512 threads,
 //                             2 waves per SIMD = the occupancy of the training kernels) and into all 160 KB of LDS;

@@ -1,6 +1,6 @@
 """The same 1920x1080 view of a 4-tile scene rendered N times (2.7e8 foreground + 2.7e8 background sample slots per frame): every
 frame must equal the first bit for bit (no atomics on the render-time path; a difference is a hazard the generated code does not
-cover).  A scratch buffer is rewritten between frames so that the tables are not always warm."""
+cover, DESIGN.md §4.1 (last paragraph); profiles/DESIGN_r04_experiment_log.md §4.10).  A scratch buffer is rewritten between frames so that the tables are not always warm."""
 import hashlib, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
