@@ -724,6 +724,41 @@ int scanerf_isosurface_emit(const void *features, int feat_dtype, const int32_t 
                             long long occ_cells, int nx, int ny, int nz, float level, const float *occ_corner /*[3] host*/,
                             const float *occ_size /*[3] host*/, const void *scratch, size_t scratch_bytes, float *vertices,
                             int32_t *faces, int32_t *cells, float *lattice, int V, int F, scanerf_stream_t stream);
+/* Scene mesh: ONE mesh of a tiled scene -- the level set of the field the multi-tile renderer draws, the tiles'
+ *   densities blended per point with scanerf_pts_inference's xz-distance weights, on one lattice over a world box.  The reference has
+ *   no counterpart; the definition is this comment.  float32, every product and every sum separately rounded, integers where named.
+ *   Lattice: the world box box_corner / box_size ([3] host each, box_size > 0) with n = (nx, ny, nz) cells; step_k = box_size_k /
+ *     float(n_k) (one division, on the host); point (i,j,k) lies at wp_k = box_corner_k + float(i_k) * step_k; a vertex with the
+ *     lattice coordinate L at box_corner + L * step, as in the dense op.
+ *   Tiles: the renderer's arrays as scanerf_pts_normals takes them -- tables_f16 [nb,16,T,2], blobs [nb][SCANERF_PARAMSIZE] (flat
+ *     decoder blobs), resolution [nb,16,3], occ / grid_starts / log2dim (the tiles' OWN occupancy grids, the ones
+ *     scanerf_pts_inference tests, not the dilated sampling grid), corners / sizes [nb,3] (the render boxes); weight_feature == 1.
+ *   Per point, the tiles b = 0 .. nb-1 in ascending index:
+ *     pts = (wp - corner_b) / size_b;  the point LISTS b iff 0 <= pts_c <= 1 on all three axes.  There is no cap of four: a lattice
+ *       point has no slot list, every tile that holds it counts (prepare_points keeps the first four; a point of six coincident
+ *       tiles lists six here);
+ *     dis = (0.5 - |pts - 0.5|) size_b;  w_b = xz_weight(dis.x, dis.z);  W += w_b whether or not the cell is occupied;
+ *     b CONTRIBUTES iff its occupancy cell (scanerf_pts_inference's loc = clamp(int(pts 2^log2dim_b)) and cell offset) is set; then
+ *       sigma_b = the density at the contracted coordinate x_c = 2 pts_c - 1 -- the bits scanerf_sigma_normals_points returns for
+ *       that x with tile b's table, blob and resolutions (the per-tile extraction's coordinate, not scanerf_pts_inference's
+ *       p01 = pts / 2 + 0.25 locator: the two differ by one rounding at cell borders) -- and num += w_b sigma_b.
+ *   Field: v = num * (W > 0 ? 1 / W : 1); 0 where no tile is listed or none contributes.  Inside: v > level, level > 0.
+ *     Classification, vertices, quads, winding, output order and the two passes are those above, unchanged; the surface is open only
+ *     at the faces of the world box.  The DENSITY blend is the small-step limit of the renderer's blend of the opacities
+ *     1 - exp(-sigma_b delta) (as delta -> 0 it is delta sum_b w_b sigma_b / W): the level set is that of the density the rendered
+ *     images integrate, with their seam behaviour.
+ *   A point's sums are ordered by tile index alone: its bits do not depend on the brick that evaluates it nor on the launch.
+ *   scratch: scanerf_isosurface_scratch_bytes(nx,ny,nz), unchanged.  Any nb >= 1.  Refused before any launch: null pointers, nb < 1,
+ *     T not a power of two, box_size <= 0 or not finite, level <= 0, a lattice or scratch the dense op refuses. */
+int scanerf_isosurface_count_tiles(const void *tables_f16, const float *blobs, const int32_t *resolution, const uint8_t *occ,
+                                   const int64_t *grid_starts, const int32_t *log2dim, const float *corners, const float *sizes, int T,
+                                   int nb, const float *box_corner /*[3] host*/, const float *box_size /*[3] host*/, int nx, int ny,
+                                   int nz, float level, void *scratch, size_t scratch_bytes, scanerf_stream_t stream);
+int scanerf_isosurface_emit_tiles(const void *tables_f16, const float *blobs, const int32_t *resolution, const uint8_t *occ,
+                                  const int64_t *grid_starts, const int32_t *log2dim, const float *corners, const float *sizes, int T,
+                                  int nb, const float *box_corner /*[3] host*/, const float *box_size /*[3] host*/, int nx, int ny,
+                                  int nz, float level, const void *scratch, size_t scratch_bytes, float *vertices, int32_t *faces,
+                                  int32_t *cells, float *lattice, int V, int F, scanerf_stream_t stream);
 
 #define SCANERF_RAY_OUT 16
 

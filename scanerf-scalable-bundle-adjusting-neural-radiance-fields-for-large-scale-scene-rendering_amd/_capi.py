@@ -114,6 +114,8 @@ PROTOTYPES = {
     "scanerf_isosurface_emit_dense": ("I", "PIIIFPPPZPPPPIIP", REQ),
     "scanerf_isosurface_count": ("I", "PIPPPIPPLIIIFPZP", REQ),
     "scanerf_isosurface_emit": ("I", "PIPPPIPPLIIIFPPPZPPPPIIP", REQ),
+    "scanerf_isosurface_count_tiles": ("I", "PPPPPPPPIIPPIIIFPZP", REQ),
+    "scanerf_isosurface_emit_tiles": ("I", "PPPPPPPPIIPPIIIFPZPPPPIIP", REQ),
 }
 SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if required]
 OPTIONAL_SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if not required]

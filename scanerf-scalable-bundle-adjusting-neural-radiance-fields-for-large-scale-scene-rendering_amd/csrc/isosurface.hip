@@ -20,7 +20,17 @@
 //
 // A point on a brick border is evaluated by every brick that holds it (9^3 / 8^3: 42 % more evaluations than points); its bits are
 // the same in each, because a lane's density depends on nothing but its own position.
+//
+// Three value sources fill a brick (IsoSrc): the caller's array, one tile's density, and -- the scene mesh, DESIGN.md 4.15 -- the
+// densities of a whole tile set blended with the renderer's weights (render_infer_device.h) on a lattice over a world box.  The
+// scene fill walks the tiles whose box reaches the brick in ascending index; per tile it forms position, membership, weight and
+// occupancy bit of the brick's points (no table read), adds the weight into a second LDS array, and only where some point
+// contributes stages that tile's operands (nrm_stage, kept across bricks) and runs the 64-point density passes, adding w sigma into
+// val.  A point's sums are ordered by tile index alone: its bits depend neither on the brick that evaluates it nor on the launch.
+// Everything behind the fill -- classification, count, scan, emit -- is shared.  The one-tile and dense kernels keep their bool
+// template parameter: their mangled names key the validated listings of csrc/isa_manifest.json.
 #include "normals_device.h"
+#include "render_infer_device.h"
 
 namespace scanerf {
 namespace {
@@ -32,6 +42,8 @@ constexpr int kIsoPasses = (kIsoPts + 63) / 64;   // 12
 constexpr int kIsoMaxBlocks = kNumCU * 12;        // three one-wave workgroups per SIMD (140 VGPRs, 12.6 KB of LDS each), grid-stride beyond
 constexpr int kIsoScanThreads = 1024;
 constexpr size_t kIsoHead = 64;                   // scratch: totals (int64 V, int64 F), padded
+
+enum IsoSrc { ISO_LOAD = 0, ISO_TILE = 1, ISO_TILES = 2 };   // the caller's array; one tile's density; a tile set's blended density
 
 struct IsoArgs {
     const float *values;   // dense op: [nx+1, ny+1, nz+1]
@@ -80,6 +92,14 @@ __device__ __forceinline__ float iso_position(int i, float h)
     return m - 1.0f;
 }
 
+// world position of the lattice coordinate L (a vertex, or a lattice point's index): the multiply and the sum separately rounded
+__device__ __forceinline__ float iso_world(float origin, float L, float step)
+{
+#pragma clang fp contract(off)
+    const float m = L * step;
+    return origin + m;
+}
+
 __device__ __forceinline__ void iso_brick_origin(const IsoArgs &a, int brick, int b0[3])
 {
     const int bz = brick % a.nb[2], r = brick / a.nb[2];
@@ -89,9 +109,11 @@ __device__ __forceinline__ void iso_brick_origin(const IsoArgs &a, int brick, in
 }
 
 // the brick's 9^3 values -> val (LDS); false: no live point (nothing else was read)
-template <int DT, bool DENSE>
+template <int DT, IsoSrc SRC>
 __device__ __forceinline__ bool iso_fill(const IsoArgs &a, const float *lds, float *val, int lane, float c, const int b0[3])
 {
+    static_assert(SRC == ISO_LOAD || SRC == ISO_TILE, "the scene source has its own fill: iso_fill_tiles");
+    constexpr bool DENSE = SRC == ISO_LOAD;
     bool any = DENSE;
 #pragma unroll 1
     for (int pass = 0; pass < kIsoPasses; ++pass) {
@@ -150,6 +172,136 @@ __device__ __forceinline__ bool iso_quad(const IsoArgs &a, bool valid, const int
     return valid && ((ins ^ far) & 1u) && cc[O1] >= 1 && cc[O2] >= 1;
 }
 
+// count pass of one brick behind its fill: the active-cell mask and the vertex / quad counts (any == false: nothing is active)
+__device__ __forceinline__ void iso_count_brick(const IsoArgs &a, const float *val, const int b0[3], int brick, int lane, bool any)
+{
+    unsigned long long word = 0ull;
+    int vc = 0, qc = 0;
+    if (any) {
+        for (int w = 0; w < kIsoB; ++w) {
+            int cc[3];
+            float cv[8];
+            unsigned ins;
+            const bool valid = iso_cell(a, val, b0, w, lane, cc, cv, ins);
+            const unsigned long long m = __ballot(valid && ins != 0u && ins != 0xffu);
+            if (lane == w) word = m;
+            vc += __popcll(m);
+            qc += __popcll(__ballot(iso_quad<0>(a, valid, cc, ins))) + __popcll(__ballot(iso_quad<1>(a, valid, cc, ins))) +
+                  __popcll(__ballot(iso_quad<2>(a, valid, cc, ins)));
+        }
+    }
+    if (lane < kIsoB) a.mask[(size_t)brick * kIsoB + lane] = word;
+    if (lane == 0) {
+        a.vbase[brick] = vc;
+        a.qbase[brick] = qc;
+    }
+}
+
+// ---- the scene source (the definition: include/scanerf_hip.h)
+struct IsoTilesArgs {
+    IsoArgs g;             // lattice, level, scratch, outputs; origin / step: the world box's corner and size / n
+    const void *tables;    // [nb,16,T,2] f16
+    const float *blobs;    // [nb, SCANERF_PARAMSIZE]
+    const int32_t *res;    // [nb,16,3]
+    Tiles t;
+};
+
+constexpr int kIsoVal = kIsoPts + 7;   // floats of a brick's value array in LDS
+
+__device__ __forceinline__ float iso_contracted(float pt)
+{
+#pragma clang fp contract(off)
+    const float m = 2.0f * pt;
+    return m - 1.0f;
+}
+
+__device__ __forceinline__ float iso_add_product(float acc, float w, float s)
+{
+#pragma clang fp contract(off)
+    const float m = w * s;
+    return acc + m;
+}
+
+// The brick's 9^3 blended values -> val, the weight sums in wsum (both LDS); false: no point of the brick contributes for any tile
+// (no table and no decoder was read).  staged / c: the tile whose operands lds holds and its constant, kept across bricks.
+__device__ __forceinline__ bool iso_fill_tiles(const IsoTilesArgs &a, float *lds, float *val, float *wsum, int lane, const int b0[3],
+                                               int &staged, float &c)
+{
+#pragma clang fp contract(off)   // (the sums below take products of render_infer_device.h's functions: separately rounded)
+    const IsoArgs &g = a.g;
+    for (int p = lane; p < kIsoVal; p += 64) {
+        val[p] = 0.0f;
+        wsum[p] = 0.0f;
+    }
+    // The brick's world extent.  Position, tile coordinate and membership are monotone in the lattice index (step, size > 0 and every
+    // operation rounds monotonically), so a tile lists a point of the brick only if it passes this test at the brick's end points.
+    float wlo[3], whi[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int last = b0[k] + kIsoB < g.n[k] ? b0[k] + kIsoB : g.n[k];
+        wlo[k] = iso_world(g.origin[k], (float)b0[k], g.step[k]);
+        whi[k] = iso_world(g.origin[k], (float)last, g.step[k]);
+    }
+    bool any = false;
+    for (int base = 0; base < a.t.nb; base += 64) {
+        const int bt = base + lane;
+        bool reach = bt < a.t.nb;
+        if (reach) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float ck = a.t.corners[3 * bt + k], sk = a.t.sizes[3 * bt + k];
+                reach = reach && tile_coord(wlo[k], ck, sk) <= 1.0f && tile_coord(whi[k], ck, sk) >= 0.0f;
+            }
+        }
+        unsigned long long cand = __ballot(reach);
+        while (cand != 0ull) {   // wave-uniform, ascending tile index
+            const int b = base + __ffsll((long long)cand) - 1;
+            cand &= cand - 1ull;
+            const float *cb = a.t.corners + 3 * b, *sb = a.t.sizes + 3 * b;
+#pragma unroll 1
+            for (int pass = 0; pass < kIsoPasses; ++pass) {
+                const int p = pass * 64 + lane;
+                const int lx = p / (kIsoP * kIsoP), r = p - lx * (kIsoP * kIsoP), ly = r / kIsoP, lz = r - ly * kIsoP;
+                const int i = b0[0] + lx, j = b0[1] + ly, k = b0[2] + lz;
+                const bool in = p < kIsoPts && i <= g.n[0] && j <= g.n[1] && k <= g.n[2];
+                const float wp[3] = { iso_world(g.origin[0], (float)i, g.step[0]), iso_world(g.origin[1], (float)j, g.step[1]),
+                                      iso_world(g.origin[2], (float)k, g.step[2]) };
+                float pt[3];
+                tile_point(wp, cb, sb, pt);
+                const bool listed = in && pt[0] >= 0.0f && pt[0] <= 1.0f && pt[1] >= 0.0f && pt[1] <= 1.0f && pt[2] >= 0.0f && pt[2] <= 1.0f;
+                const float w = tile_weight(pt, sb);
+                const int64_t cell = tile_cell(a.t, b, pt);   // (for every lane: render_infer_device.h)
+                if (listed) wsum[p] = wsum[p] + w;            // the weight counts whether or not the cell is occupied
+                const bool run = listed && a.t.occ[cell] != 0;
+                if (__ballot(run) == 0ull) continue;          // wave-uniform
+                if (b != staged) {
+                    __syncthreads();   // (one wave: the reads of the tile staged before are done)
+                    const float *blob = a.blobs + (size_t)b * SCANERF_PARAMSIZE;
+                    nrm_stage<false>(lds, blob, nullptr, a.res + (size_t)b * 48, lane);
+                    c = nrm_c(blob);
+                    staged = b;
+                    __syncthreads();
+                }
+                float x[3] = { 0.0f, 0.0f, 0.0f };   // (lanes that do not run: the one-tile fill's dead lanes)
+                if (run) {
+                    x[0] = iso_contracted(pt[0]);
+                    x[1] = iso_contracted(pt[1]);
+                    x[2] = iso_contracted(pt[2]);
+                }
+                const float unused[3] = { 0.0f, 0.0f, 0.0f };
+                float s, gsum[3];
+                density_grad<SCANERF_F16, false, true>(lds, (const char *)a.tables + (size_t)b * 16 * a.g.T * 4, a.g.T, unused, c, lane, x, s, gsum);
+                if (run) val[p] = iso_add_product(val[p], w, nrm_softplus(s));
+                any = true;
+            }
+        }
+    }
+    if (any) {
+        for (int p = lane; p < kIsoPts; p += 64) val[p] = val[p] * inv_weight(wsum[p]);
+    }
+    return any;
+}
+
 template <int DT, bool DENSE>
 __global__ void __launch_bounds__(64) k_iso_count(IsoArgs a)
 {
@@ -166,8 +318,9 @@ __global__ void __launch_bounds__(64) k_iso_count(IsoArgs a)
         int b0[3];
         iso_brick_origin(a, brick, b0);
         __syncthreads();   // (the previous brick's reads of val are done)
-        const bool any = iso_fill<DT, DENSE>(a, lds, val, lane, c, b0);
+        const bool any = iso_fill<DT, DENSE ? ISO_LOAD : ISO_TILE>(a, lds, val, lane, c, b0);
         __syncthreads();
+        // (iso_count_brick's statements, spelled out: through the helper this kernel compiles to another listing than the validated one)
         unsigned long long word = 0ull;
         int vc = 0, qc = 0;
         if (any) {
@@ -188,6 +341,23 @@ __global__ void __launch_bounds__(64) k_iso_count(IsoArgs a)
             a.vbase[brick] = vc;
             a.qbase[brick] = qc;
         }
+    }
+}
+
+__global__ void __launch_bounds__(64) k_iso_count_tiles(IsoTilesArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float lds[NL_TOTAL];
+    __shared__ float val[kIsoVal], wsum[kIsoVal];
+    const int lane = threadIdx.x;
+    int staged = -1;
+    float c = 0.0f;
+    for (int brick = blockIdx.x; brick < a.g.nbricks; brick += gridDim.x) {
+        int b0[3];
+        iso_brick_origin(a.g, brick, b0);
+        __syncthreads();   // (the previous brick's reads of val are done)
+        const bool any = iso_fill_tiles(a, lds, val, wsum, lane, b0, staged, c);
+        __syncthreads();
+        iso_count_brick(a.g, val, b0, brick, lane, any);
     }
 }
 
@@ -274,13 +444,6 @@ __device__ __forceinline__ void iso_cell_vertex(const int cc[3], const float cv[
     L[2] = sum[2] / fc;
 }
 
-__device__ __forceinline__ float iso_world(float origin, float L, float step)
-{
-#pragma clang fp contract(off)
-    const float m = L * step;
-    return origin + m;
-}
-
 template <int A>
 __device__ __forceinline__ void iso_emit_quad(const IsoArgs &a, const int cc[3], unsigned ins, int slot)
 {
@@ -310,6 +473,41 @@ __device__ __forceinline__ void iso_emit_quad(const IsoArgs &a, const int cc[3],
     f[5] = id[3];
 }
 
+// emit pass of one brick behind its fill: vertices from v0 on, quads from q0 on (below = the lanes before this one)
+__device__ __forceinline__ void iso_emit_brick(const IsoArgs &a, const float *val, const int b0[3], int lane, unsigned long long below,
+                                               int v0, int q0)
+{
+    int vrun = v0, qrun = q0;
+    for (int w = 0; w < kIsoB; ++w) {
+        int cc[3];
+        float cv[8];
+        unsigned ins;
+        const bool valid = iso_cell(a, val, b0, w, lane, cc, cv, ins);
+        const bool active = valid && ins != 0u && ins != 0xffu;
+        const unsigned long long m = __ballot(active);
+        if (active) {
+            const int vid = vrun + __popcll(m & below);
+            float L[3];
+            iso_cell_vertex(cc, cv, a.level, L);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                a.vertices[3 * (size_t)vid + k] = iso_world(a.origin[k], L[k], a.step[k]);
+                a.cells[3 * (size_t)vid + k] = cc[k];
+                if (a.lattice) a.lattice[3 * (size_t)vid + k] = L[k];
+            }
+        }
+        vrun += __popcll(m);
+        const bool qa = iso_quad<0>(a, valid, cc, ins), qb = iso_quad<1>(a, valid, cc, ins), qc = iso_quad<2>(a, valid, cc, ins);
+        const unsigned long long ma = __ballot(qa), mb = __ballot(qb), mc = __ballot(qc);
+        if (qa) iso_emit_quad<0>(a, cc, ins, qrun + __popcll(ma & below));
+        qrun += __popcll(ma);
+        if (qb) iso_emit_quad<1>(a, cc, ins, qrun + __popcll(mb & below));
+        qrun += __popcll(mb);
+        if (qc) iso_emit_quad<2>(a, cc, ins, qrun + __popcll(mc & below));
+        qrun += __popcll(mc);
+    }
+}
+
 template <int DT, bool DENSE>
 __global__ void __launch_bounds__(64) k_iso_emit(IsoArgs a)
 {
@@ -330,8 +528,9 @@ __global__ void __launch_bounds__(64) k_iso_emit(IsoArgs a)
         int b0[3];
         iso_brick_origin(a, brick, b0);
         __syncthreads();
-        iso_fill<DT, DENSE>(a, lds, val, lane, c, b0);
+        iso_fill<DT, DENSE ? ISO_LOAD : ISO_TILE>(a, lds, val, lane, c, b0);
         __syncthreads();
+        // (iso_emit_brick's statements, spelled out: as in k_iso_count)
         int vrun = v0, qrun = q0;
         for (int w = 0; w < kIsoB; ++w) {
             int cc[3];
@@ -361,6 +560,26 @@ __global__ void __launch_bounds__(64) k_iso_emit(IsoArgs a)
             if (qc) iso_emit_quad<2>(a, cc, ins, qrun + __popcll(mc & below));
             qrun += __popcll(mc);
         }
+    }
+}
+
+__global__ void __launch_bounds__(64) k_iso_emit_tiles(IsoTilesArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float lds[NL_TOTAL];
+    __shared__ float val[kIsoVal], wsum[kIsoVal];
+    const int lane = threadIdx.x;
+    int staged = -1;
+    float c = 0.0f;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int brick = blockIdx.x; brick < a.g.nbricks; brick += gridDim.x) {
+        const int v0 = a.g.vbase[brick], v1 = a.g.vbase[brick + 1], q0 = a.g.qbase[brick], q1 = a.g.qbase[brick + 1];
+        if (v1 == v0 || v0 < 0 || q0 < 0 || v1 > a.g.V || q1 > a.g.F / 2) continue;   // (as k_iso_emit)
+        int b0[3];
+        iso_brick_origin(a.g, brick, b0);
+        __syncthreads();
+        iso_fill_tiles(a, lds, val, wsum, lane, b0, staged, c);
+        __syncthreads();
+        iso_emit_brick(a.g, val, b0, lane, below, v0, q0);
     }
 }
 
@@ -464,10 +683,70 @@ int iso_launch_emit(const char *op, const IsoArgs &a, int feat_dtype, hipStream_
     return check_launch(op);
 }
 
+// the scene source's arguments (everything but lattice, scratch and outputs); origin / step: the world box
+int iso_check_tiles(const char *op, IsoTilesArgs &a, const void *tables_f16, const float *blobs, const int32_t *resolution,
+                    const uint8_t *occ, const int64_t *grid_starts, const int32_t *log2dim, const float *corners, const float *sizes, int T,
+                    int nb, const float *box_corner, const float *box_size, int nx, int ny, int nz)
+{
+    SCANERF_REQUIRE(nb >= 1, "%s: nb=%d (at least one tile)", op, nb);
+    SCANERF_REQUIRE(T >= 2 && (T & (T - 1)) == 0, "%s: T=%d must be a power of two", op, T);
+    SCANERF_REQUIRE(tables_f16 && blobs && resolution && occ && grid_starts && log2dim && corners && sizes, "%s: null pointer", op);
+    SCANERF_REQUIRE(box_corner && box_size, "%s: null pointer (box_corner / box_size)", op);
+    SCANERF_REQUIRE(((uintptr_t)tables_f16 & 15) == 0, "%s: tables must be 16-byte aligned", op);
+    const int n[3] = { nx, ny, nz };
+    for (int k = 0; k < 3; ++k) {
+        SCANERF_REQUIRE(box_size[k] > 0.0f && box_size[k] <= 3.0e38f, "%s: box_size[%d]=%g must be positive and finite", op, k,
+                        (double)box_size[k]);
+        a.g.origin[k] = box_corner[k];
+        a.g.step[k] = box_size[k] / (float)n[k];
+    }
+    a.tables = tables_f16; a.blobs = blobs; a.res = resolution; a.g.T = T;
+    a.t = make_tiles(corners, sizes, occ, grid_starts, log2dim, nb);
+    return 0;
+}
+
 }  // namespace
 }  // namespace scanerf
 
 using namespace scanerf;
+
+SCANERF_API int scanerf_isosurface_count_tiles(const void *tables_f16, const float *blobs, const int32_t *resolution, const uint8_t *occ,
+                                               const int64_t *grid_starts, const int32_t *log2dim, const float *corners,
+                                               const float *sizes, int T, int nb, const float *box_corner, const float *box_size, int nx,
+                                               int ny, int nz, float level, void *scratch, size_t scratch_bytes, scanerf_stream_t stream)
+{
+    const char *op = "isosurface_count_tiles";
+    IsoTilesArgs a = {};
+    if (int e = iso_check_lattice(op, nx, ny, nz, level)) return e;
+    if (int e = iso_check_tiles(op, a, tables_f16, blobs, resolution, occ, grid_starts, log2dim, corners, sizes, T, nb, box_corner, box_size,
+                                nx, ny, nz))
+        return e;
+    if (int e = iso_common(op, a.g, nx, ny, nz, level, scratch, scratch_bytes)) return e;
+    hipLaunchKernelGGL(k_iso_count_tiles, dim3(iso_blocks(a.g)), dim3(64), 0, (hipStream_t)stream, a);
+    if (int e = check_launch(op)) return e;
+    hipLaunchKernelGGL(k_iso_scan, dim3(1), dim3(kIsoScanThreads), 0, (hipStream_t)stream, a.g.vbase, a.g.qbase, a.g.nbricks,
+                       (long long *)scratch);
+    return check_launch(op);
+}
+
+SCANERF_API int scanerf_isosurface_emit_tiles(const void *tables_f16, const float *blobs, const int32_t *resolution, const uint8_t *occ,
+                                              const int64_t *grid_starts, const int32_t *log2dim, const float *corners,
+                                              const float *sizes, int T, int nb, const float *box_corner, const float *box_size, int nx,
+                                              int ny, int nz, float level, const void *scratch, size_t scratch_bytes, float *vertices,
+                                              int32_t *faces, int32_t *cells, float *lattice, int V, int F, scanerf_stream_t stream)
+{
+    const char *op = "isosurface_emit_tiles";
+    IsoTilesArgs a = {};
+    if (int e = iso_check_lattice(op, nx, ny, nz, level)) return e;
+    if (int e = iso_check_tiles(op, a, tables_f16, blobs, resolution, occ, grid_starts, log2dim, corners, sizes, T, nb, box_corner, box_size,
+                                nx, ny, nz))
+        return e;
+    if (int e = iso_common(op, a.g, nx, ny, nz, level, const_cast<void *>(scratch), scratch_bytes)) return e;
+    if (int e = iso_check_outputs(op, a.g, box_corner, box_size, vertices, faces, cells, lattice, V, F)) return e;
+    if (V == 0) return 0;
+    hipLaunchKernelGGL(k_iso_emit_tiles, dim3(iso_blocks(a.g)), dim3(64), 0, (hipStream_t)stream, a);
+    return check_launch(op);
+}
 
 SCANERF_API size_t scanerf_isosurface_scratch_bytes(int nx, int ny, int nz)
 {

@@ -5,8 +5,10 @@ lattice.  The reference has no mesh extraction; the definition is the comment of
     extract_mesh(features, ..., n, level)               the tile's density level set; route="fused" never stores the lattice,
                                                         route="dense" composes lattice points -> render.sigma_normals_points ->
                                                         liveness -> the dense op (the witness, and fine for small lattices)
+    extract_scene_mesh(tables, ..., box, n, level)      ONE mesh of a tiled scene: the level set of the tiles' densities blended with
+                                                        the multi-tile renderer's weights on a lattice over a world box
 
-Both return a Mesh: vertices [V,3] f32 (world), faces [F,3] i32 (counter-clockwise seen from the outside), cells [V,3] i32 (the owning
+All return a Mesh: vertices [V,3] f32 (world), faces [F,3] i32 (counter-clockwise seen from the outside), cells [V,3] i32 (the owning
 cell of each vertex), lattice [V,3] f32 (the vertices in lattice coordinates) and, on request, normals [V,3] f32.  Two launches with
 one host read of (V, F) between them; no CPU path."""
 import collections
@@ -147,6 +149,100 @@ def extract_mesh(features, resolutions, blob, weight_feature, occupied_grid, log
             nrm = torch.empty((0, 3), dtype=_f32, device=device)
         mesh = mesh._replace(normals=nrm)
     return mesh
+
+
+# ---- one mesh of a tiled scene: the level set of the tiles' blended density -----------------------------------
+def _scene_field_dense(feature_tables, resolutions, blobs, corners, sizes, occupied_grid, grid_starts, log2dim, corner, size, n):
+    """The witness of the fused scene route: the definition of include/scanerf_hip.h op by op.  World positions, membership, weights,
+    cells and occupancy in numpy float32 on the host (IEEE by construction; every quantity but the weight is a product of per-axis
+    terms), sigma_b from render.sigma_normals_points at the contributing points of each tile, the blend in ascending tile index.
+    -> values [nx+1, ny+1, nz+1] f32 (numpy)."""
+    f32 = np.float32
+    device = feature_tables.device
+    host = lambda t, dt: np.ascontiguousarray(t.detach().cpu().numpy()).astype(dt)
+    cn, sz, occ = host(corners, f32), host(sizes, f32), host(occupied_grid, bool).reshape(-1)
+    starts, l2d = host(grid_starts, np.int64), host(log2dim, np.int64)
+    wp = [f32(corner[k]) + np.arange(n[k] + 1, dtype=f32) * (f32(size[k]) / f32(n[k])) for k in range(3)]
+    assert all(a.dtype == f32 for a in wp)
+    shape = tuple(m + 1 for m in n)
+    num, W = np.zeros(shape, f32), np.zeros(shape, f32)
+    ones = torch.ones(32, dtype=_f32, device=device)
+    for b in range(cn.shape[0]):
+        pt = [(wp[k] - cn[b, k]) / sz[b, k] for k in range(3)]
+        inb = [(p >= 0) & (p <= 1) for p in pt]
+        listed = inb[0][:, None, None] & inb[1][None, :, None] & inb[2][None, None, :]
+        if not listed.any():
+            continue
+        dis = [(f32(0.5) - np.abs(p - f32(0.5))) * sz[b, k] for k, p in enumerate(pt)]
+        dx, dz = dis[0][:, None], dis[2][None, :]
+        w2 = np.where((dx != 0) & (dz != 0), dx * dz, np.where(dx != 0, dx, np.where(dz != 0, dz, f32(0)))).astype(f32)   # xz_weight
+        w = np.broadcast_to(w2[:, None, :], shape)
+        W = np.where(listed, W + w, W).astype(f32)
+        loc = []
+        for k in range(3):
+            r = 1 << int(l2d[b, k])
+            with np.errstate(invalid="ignore", over="ignore"):
+                cc = (pt[k] * f32(r)).astype(f32)
+            loc.append(np.clip(np.where(np.isfinite(cc), cc, 0).astype(np.int64), 0, r - 1))    # C (int): truncation, then the clamp
+        off = (loc[0][:, None, None] << int(l2d[b, 1] + l2d[b, 2])) | (loc[1][None, :, None] << int(l2d[b, 2])) | loc[2][None, None, :]
+        run = listed & occ[starts[b] + off]
+        if not run.any():
+            continue
+        idx = np.argwhere(run)
+        x = np.stack([(f32(2.0) * pt[k] - f32(1.0))[idx[:, k]] for k in range(3)], 1).astype(f32)
+        sigma, _, _ = render.sigma_normals_points(torch.from_numpy(x).to(device), feature_tables[b], resolutions[b], blobs[b], ones)
+        prod = (w[run] * sigma.cpu().numpy()).astype(f32)
+        num[run] = num[run] + prod
+    inv = np.where(W > 0, f32(1.0) / np.where(W > 0, W, f32(1.0)), f32(1.0)).astype(f32)
+    return (num * inv).astype(f32)
+
+
+def extract_scene_mesh(feature_tables, resolutions, blobs, corners, sizes, occupied_grid, grid_starts, log2dim, box_corner, box_size, n,
+                       level, route="fused"):
+    """One mesh of a tiled scene: the level set of the field the multi-tile renderer draws -- the tiles' densities blended per lattice
+    point with the renderer's xz-distance weights -- on a lattice of n cells over the world box box_corner / box_size (the definition:
+    include/scanerf_hip.h, scanerf_isosurface_count_tiles).  The tile arrays are TileSetRenderer's: feature_tables [nb,16,T,2] f16,
+    resolutions [nb,16,3] i32, blobs [nb,13994], corners / sizes [nb,3] (render boxes), occupied_grid (the tiles' own grids,
+    concatenated), grid_starts [nb] i64, log2dim [nb,3] i32.  -> Mesh with normals None.  route="fused" never stores the lattice;
+    route="dense" composes host geometry -> render.sigma_normals_points per tile -> blend -> surface_nets (the witness)."""
+    if route not in ROUTES:
+        raise RuntimeError(f"scanerf: route must be one of {ROUTES}, got {route!r}")
+    n = _lattice_size(n)
+    tabs = dev_ptr(feature_tables, torch.float16, "feature_tables")
+    if feature_tables.dim() != 4 or feature_tables.shape[1] != 16 or feature_tables.shape[3] != 2:
+        raise RuntimeError(f"scanerf: feature_tables must be [nb,16,T,2], got {tuple(feature_tables.shape)}")
+    nb, T = int(feature_tables.shape[0]), int(feature_tables.shape[2])
+    if nb < 1:
+        raise RuntimeError("scanerf: a scene mesh needs at least one tile")
+    if T < 2 or T & (T - 1):
+        raise RuntimeError(f"scanerf: the table size T={T} must be a power of two")
+    from . import _capi
+    ptrs = []
+    for t, dt, name, shape in ((blobs, _f32, "blobs", (nb, _capi.PARAMSIZE)), (resolutions, torch.int32, "resolutions", (nb, 16, 3)),
+                               (occupied_grid, (torch.bool, torch.uint8), "occupied_grid", None), (grid_starts, torch.int64, "grid_starts", (nb,)),
+                               (log2dim, torch.int32, "log2dim", (nb, 3)), (corners, _f32, "corners", (nb, 3)), (sizes, _f32, "sizes", (nb, 3))):
+        ptrs.append(dev_ptr(t, dt, name))
+        if shape is not None and tuple(t.shape) != shape:
+            raise RuntimeError(f"scanerf: {name} must be {list(shape)}, got {list(t.shape)}")
+    corner, size = _host3(box_corner, "box_corner"), _host3(box_size, "box_size")
+    if not all(0 < s < float("inf") for s in size):
+        raise RuntimeError(f"scanerf: box_size must be positive, got {list(size)}")
+    if not float(level) > 0:
+        raise RuntimeError(f"scanerf: level={level} must be > 0")
+    device = feature_tables.device
+    if route == "dense":
+        values = _scene_field_dense(feature_tables, resolutions, blobs, corners, sizes, occupied_grid, grid_starts, log2dim, corner, size, n)
+        step = [_f32_div(size[k], n[k]) for k in range(3)]
+        return surface_nets(torch.from_numpy(values).to(device).contiguous(), level, list(corner), step)
+    scratch, nbytes = _scratch(device, n)
+    head = (tabs, *ptrs, T, nb, corner, size, *n, float(level))
+    check(lib().scanerf_isosurface_count_tiles(*head, scratch.data_ptr(), nbytes, stream()), "isosurface_count_tiles")
+    V, F = _totals(scratch)
+    vertices, faces, cells, lattice = _outputs(device, V, F)
+    if V:
+        check(lib().scanerf_isosurface_emit_tiles(*head, scratch.data_ptr(), nbytes, vertices.data_ptr(), faces.data_ptr(), cells.data_ptr(),
+                                                  lattice.data_ptr(), V, F, stream()), "isosurface_emit_tiles")
+    return Mesh(vertices, faces, cells, lattice, None)
 
 
 def cells_per_axis(occ_size, longest):

@@ -248,3 +248,21 @@ class TileSetRenderer:
         dif, spec, depth, transp, *nm = self.render_rays(o, d, **kw)
         return (dif.reshape(H, W, 3), spec.reshape(H, W, 3), depth.reshape(H, W, 1), transp.reshape(H, W, 1),
                 *(x.reshape(H, W, 3) for x in nm))
+
+    def scene_box(self):
+        """(corner, size), 3 floats each: the bounding box of the tiles' render boxes."""
+        lo = self.block_corner.min(0).values.cpu().numpy().astype(np.float32)
+        hi = (self.block_corner + self.block_size).max(0).values.cpu().numpy().astype(np.float32)
+        return lo.tolist(), (hi - lo).tolist()
+
+    @torch.no_grad()
+    def extract_mesh(self, level, cells_per_axis=256, box=None, route="fused"):
+        """ONE mesh of the whole scene: the level set sigma == level of the density this renderer draws, the tiles' densities blended
+        per point with the render-time weights (meshing.extract_scene_mesh).  box = (corner, size) of the world box
+        the lattice covers (default: scene_box()), with cells_per_axis cells along its longest side.  -> meshing.Mesh."""
+        from . import meshing
+        corner, size = self.scene_box() if box is None else box
+        size = [float(v) for v in size]
+        return meshing.extract_scene_mesh(self.feature_tables, self.resolution, self.params, self.block_corner, self.block_size,
+                                          self.occupied_grid, self.grid_starts, self.grid_log2dim, corner, size,
+                                          meshing.cells_per_axis(size, cells_per_axis), level, route=route)

@@ -1,0 +1,48 @@
+#!/usr/bin/env python3
+"""ONE mesh of a tiled scene: the level set of the tiles' blended density, written as a PLY.
+
+    python tools/extract_scene_mesh.py TILEDIR [TILEDIR ...] --level SIGMA [--cells-per-axis 256]
+                                       [--box X Y Z SX SY SZ] --out FILE.ply [--route fused|dense] [--gpu 0]
+
+Every TILEDIR holds feature.npz and decoder.pth as renderer.export_tile writes and renderer.load_tile reads them; together they are
+the scene renderer.TileSetRenderer draws.  The field is the one it draws: the tiles' densities blended per point with the render-time
+xz-distance weights, so the surface runs through the tile faces and margins as the rendered images do, closed there, open only at
+the faces of the world box.  The lattice covers --box (corner and size in world units; default: the bounding box of the tiles' render
+boxes) with --cells-per-axis cells along its longest side.  tools/extract_mesh.py writes one open mesh per tile instead."""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def parser():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("tiles", metavar="TILEDIR", nargs="+", help="directories with feature.npz and decoder.pth: the tiles of one scene")
+    ap.add_argument("--level", type=float, required=True, help="density of the level set (sigma units, > 0)")
+    ap.add_argument("--cells-per-axis", type=int, default=256, help="lattice cells along the world box's longest side")
+    ap.add_argument("--box", type=float, nargs=6, default=None, metavar=("X", "Y", "Z", "SX", "SY", "SZ"),
+                    help="world box of the lattice: corner and size (default: the bounding box of the tiles' render boxes)")
+    ap.add_argument("--out", required=True, metavar="FILE.ply")
+    ap.add_argument("--route", choices=("fused", "dense"), default="fused", help="dense: the composed route (small lattices only)")
+    ap.add_argument("--gpu", type=int, default=0)
+    return ap
+
+
+def main(argv=None):
+    args = parser().parse_args(argv)
+    import scanerf_amd  # noqa: F401
+    from scanerf_amd import formats, renderer
+    rnd = renderer.TileSetRenderer(f"cuda:{args.gpu}", [renderer.load_tile(p) for p in args.tiles])
+    box = None if args.box is None else (args.box[:3], args.box[3:])
+    mesh = rnd.extract_mesh(args.level, args.cells_per_axis, box=box, route=args.route)
+    out_dir = os.path.dirname(os.path.abspath(args.out))
+    os.makedirs(out_dir, exist_ok=True)
+    formats.write_ply(args.out, mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy())
+    print(f"{args.out}: {len(args.tiles)} tiles, {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} faces")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
