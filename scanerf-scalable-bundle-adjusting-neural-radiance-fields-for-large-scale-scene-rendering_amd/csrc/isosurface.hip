@@ -27,8 +27,9 @@
 // occupancy bit of the brick's points (no table read), adds the weight into a second LDS array, and only where some point
 // contributes stages that tile's operands (nrm_stage, kept across bricks) and runs the 64-point density passes, adding w sigma into
 // val.  A point's sums are ordered by tile index alone: its bits depend neither on the brick that evaluates it nor on the launch.
-// Everything behind the fill -- classification, count, scan, emit -- is shared.  The one-tile and dense kernels keep their bool
-// template parameter: their mangled names key the validated listings of csrc/isa_manifest.json.
+// The source is a template parameter of the two brick kernels, k_iso_count<SRC, DT> and k_iso_emit<SRC, DT>, and reaches no further
+// than iso_fill<SRC, DT>: everything behind the fill -- classification, count, scan, emit -- is written once, as is the host side
+// (one args struct, one check chain and one launch dispatch behind the six launching exports).
 #include "normals_device.h"
 #include "render_infer_device.h"
 
@@ -38,6 +39,7 @@ namespace {
 constexpr int kIsoB = 8;                          // cells of a brick per axis
 constexpr int kIsoP = kIsoB + 1;                  // points
 constexpr int kIsoPts = kIsoP * kIsoP * kIsoP;    // 729
+constexpr int kIsoVal = kIsoPts + 7;              // floats of a brick's value array in LDS
 constexpr int kIsoPasses = (kIsoPts + 63) / 64;   // 12
 constexpr int kIsoMaxBlocks = kNumCU * 12;        // three one-wave workgroups per SIMD (140 VGPRs, 12.6 KB of LDS each), grid-stride beyond
 constexpr int kIsoScanThreads = 1024;
@@ -46,16 +48,19 @@ constexpr size_t kIsoHead = 64;                   // scratch: totals (int64 V, i
 enum IsoSrc { ISO_LOAD = 0, ISO_TILE = 1, ISO_TILES = 2 };   // the caller's array; one tile's density; a tile set's blended density
 
 struct IsoArgs {
-    const float *values;   // dense op: [nx+1, ny+1, nz+1]
-    const void *features;
-    const int32_t *resolutions;
-    const float *blob, *wf;
-    const uint8_t *occ;
+    const float *values;          // ISO_LOAD: [nx+1, ny+1, nz+1]
+    const void *features;         // ISO_TILE: [16,T,2] f32 / f16; ISO_TILES: [nb,16,T,2] f16
+    const int32_t *resolutions;   // [16,3]; [nb,16,3]
+    const float *blob;            // the flat decoder blob; [nb, SCANERF_PARAMSIZE]
+    const float *wf;              // ISO_TILE: weight_feature [32]
+    const uint8_t *occ;           // ISO_TILE: the sampler's occupancy grid, G cells per axis
+    Tiles t;                      // ISO_TILES (the definition: include/scanerf_hip.h)
     int T, G[3];
     int n[3], nb[3], nbricks;
-    float level, h[3], origin[3], step[3];
-    unsigned long long *mask;   // [nbricks][8]
-    int *vbase, *qbase;         // [nbricks + 1] each: counts, after the scan exclusive sums
+    float level, h[3];
+    float origin[3], step[3];     // world position of lattice coordinate L: origin + L step (ISO_TILES: the world box's corner, size / n)
+    unsigned long long *mask;     // [nbricks][8]
+    int *vbase, *qbase;           // [nbricks + 1] each: counts, after the scan exclusive sums
     float *vertices, *lattice;
     int *faces, *cells;
     int V, F;
@@ -100,6 +105,20 @@ __device__ __forceinline__ float iso_world(float origin, float L, float step)
     return origin + m;
 }
 
+__device__ __forceinline__ float iso_contracted(float pt)
+{
+#pragma clang fp contract(off)
+    const float m = 2.0f * pt;
+    return m - 1.0f;
+}
+
+__device__ __forceinline__ float iso_add_product(float acc, float w, float s)
+{
+#pragma clang fp contract(off)
+    const float m = w * s;
+    return acc + m;
+}
+
 __device__ __forceinline__ void iso_brick_origin(const IsoArgs &a, int brick, int b0[3])
 {
     const int bz = brick % a.nb[2], r = brick / a.nb[2];
@@ -108,41 +127,158 @@ __device__ __forceinline__ void iso_brick_origin(const IsoArgs &a, int brick, in
     b0[2] = bz * kIsoB;
 }
 
-// the brick's 9^3 values -> val (LDS); false: no live point (nothing else was read)
-template <int DT, IsoSrc SRC>
-__device__ __forceinline__ bool iso_fill(const IsoArgs &a, const float *lds, float *val, int lane, float c, const int b0[3])
+// point p of the brick -> its lattice index; false: past the brick's 729 points or outside the lattice
+__device__ __forceinline__ bool iso_point(const IsoArgs &a, const int b0[3], int p, int &i, int &j, int &k)
 {
-    static_assert(SRC == ISO_LOAD || SRC == ISO_TILE, "the scene source has its own fill: iso_fill_tiles");
-    constexpr bool DENSE = SRC == ISO_LOAD;
-    bool any = DENSE;
+    const int lx = p / (kIsoP * kIsoP), r = p - lx * (kIsoP * kIsoP), ly = r / kIsoP, lz = r - ly * kIsoP;
+    i = b0[0] + lx;
+    j = b0[1] + ly;
+    k = b0[2] + lz;
+    return p < kIsoPts && i <= a.n[0] && j <= a.n[1] && k <= a.n[2];
+}
+
+// ISO_TILES: the brick's 9^3 blended values -> val, the weight sums in wsum (both LDS); false: no point of the brick contributes for
+// any tile (no table and no decoder was read).  staged / c: the tile whose operands lds holds and its constant, kept across bricks.
+__device__ __forceinline__ bool iso_fill_tiles(const IsoArgs &a, float *lds, float *val, float *wsum, int lane, const int b0[3],
+                                               int &staged, float &c)
+{
+#pragma clang fp contract(off)   // (the sums below take products of render_infer_device.h's functions: separately rounded)
+    for (int p = lane; p < kIsoVal; p += 64) {
+        val[p] = 0.0f;
+        wsum[p] = 0.0f;
+    }
+    // The brick's world extent.  Position, tile coordinate and membership are monotone in the lattice index (step, size > 0 and every
+    // operation rounds monotonically), so a tile lists a point of the brick only if it passes this test at the brick's end points.
+    float wlo[3], whi[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int last = b0[k] + kIsoB < a.n[k] ? b0[k] + kIsoB : a.n[k];
+        wlo[k] = iso_world(a.origin[k], (float)b0[k], a.step[k]);
+        whi[k] = iso_world(a.origin[k], (float)last, a.step[k]);
+    }
+    bool any = false;
+    for (int base = 0; base < a.t.nb; base += 64) {
+        const int bt = base + lane;
+        bool reach = bt < a.t.nb;
+        if (reach) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float ck = a.t.corners[3 * bt + k], sk = a.t.sizes[3 * bt + k];
+                reach = reach && tile_coord(wlo[k], ck, sk) <= 1.0f && tile_coord(whi[k], ck, sk) >= 0.0f;
+            }
+        }
+        unsigned long long cand = __ballot(reach);
+        while (cand != 0ull) {   // wave-uniform, ascending tile index
+            const int b = base + __ffsll((long long)cand) - 1;
+            cand &= cand - 1ull;
+            const float *cb = a.t.corners + 3 * b, *sb = a.t.sizes + 3 * b;
 #pragma unroll 1
-    for (int pass = 0; pass < kIsoPasses; ++pass) {
-        const int p = pass * 64 + lane;
-        const int lx = p / (kIsoP * kIsoP), r = p - lx * (kIsoP * kIsoP), ly = r / kIsoP, lz = r - ly * kIsoP;
-        const int i = b0[0] + lx, j = b0[1] + ly, k = b0[2] + lz;
-        const bool in = p < kIsoPts && i <= a.n[0] && j <= a.n[1] && k <= a.n[2];
-        float v = 0.0f;
-        if constexpr (DENSE) {
-            if (in) v = a.values[((size_t)i * (a.n[1] + 1) + j) * (a.n[2] + 1) + k];
-        } else {
-            const bool live = in && iso_point_live(a, i, j, k);
-            if (__ballot(live) != 0ull) {   // wave-uniform: every lane takes part in the product
-                float x[3] = { 0.0f, 0.0f, 0.0f };
-                if (live) {
-                    x[0] = iso_position(i, a.h[0]);
-                    x[1] = iso_position(j, a.h[1]);
-                    x[2] = iso_position(k, a.h[2]);
+            for (int pass = 0; pass < kIsoPasses; ++pass) {
+                const int p = pass * 64 + lane;
+                int i, j, k;
+                const bool in = iso_point(a, b0, p, i, j, k);
+                const float wp[3] = { iso_world(a.origin[0], (float)i, a.step[0]), iso_world(a.origin[1], (float)j, a.step[1]),
+                                      iso_world(a.origin[2], (float)k, a.step[2]) };
+                float pt[3];
+                tile_point(wp, cb, sb, pt);
+                const bool listed = in && pt[0] >= 0.0f && pt[0] <= 1.0f && pt[1] >= 0.0f && pt[1] <= 1.0f && pt[2] >= 0.0f && pt[2] <= 1.0f;
+                const float w = tile_weight(pt, sb);
+                const int64_t cell = tile_cell(a.t, b, pt);   // (for every lane: render_infer_device.h)
+                if (listed) wsum[p] = wsum[p] + w;            // the weight counts whether or not the cell is occupied
+                const bool run = listed && a.t.occ[cell] != 0;
+                if (__ballot(run) == 0ull) continue;          // wave-uniform
+                if (b != staged) {
+                    __syncthreads();   // (one wave: the reads of the tile staged before are done)
+                    const float *blob = a.blob + (size_t)b * SCANERF_PARAMSIZE;
+                    nrm_stage<false>(lds, blob, nullptr, a.resolutions + (size_t)b * 48, lane);
+                    c = nrm_c(blob);
+                    staged = b;
+                    __syncthreads();
+                }
+                float x[3] = { 0.0f, 0.0f, 0.0f };   // (lanes that do not run: the one-tile fill's dead lanes)
+                if (run) {
+                    x[0] = iso_contracted(pt[0]);
+                    x[1] = iso_contracted(pt[1]);
+                    x[2] = iso_contracted(pt[2]);
                 }
                 const float unused[3] = { 0.0f, 0.0f, 0.0f };
                 float s, gsum[3];
-                density_grad<DT, false, true>(lds, a.features, a.T, unused, c, lane, x, s, gsum);
-                if (live) v = nrm_softplus(s);
+                density_grad<SCANERF_F16, false, true>(lds, (const char *)a.features + (size_t)b * 16 * a.T * 4, a.T, unused, c, lane, x, s, gsum);
+                if (run) val[p] = iso_add_product(val[p], w, nrm_softplus(s));
                 any = true;
             }
         }
-        if (p < kIsoPts) val[p] = v;
+    }
+    if (any) {
+        for (int p = lane; p < kIsoPts; p += 64) val[p] = val[p] * inv_weight(wsum[p]);
     }
     return any;
+}
+
+// A brick kernel's LDS: the decoder operands of the staged tile, the brick's values and, for the tile set alone, its weight sums
+// (2.9, 12.6 and 15.5 KB for the three sources; a source pays for no array it does not use)
+template <IsoSrc SRC>
+struct IsoLds {
+    float operands[SRC == ISO_LOAD ? 0 : NL_TOTAL] __attribute__((aligned(16)));
+    float val[kIsoVal];
+    float wsum[SRC == ISO_TILES ? kIsoVal : 0];
+};
+
+// which tile's operands the LDS holds (-1: none yet) and that tile's constant: kept by a kernel across its bricks
+struct IsoStaged {
+    int tile;
+    float c;
+};
+
+// ISO_TILE stages its one tile here, once; ISO_TILES stages in the fill, tile after tile
+template <IsoSrc SRC>
+__device__ __forceinline__ IsoStaged iso_begin(const IsoArgs &a, IsoLds<SRC> &s, int lane)
+{
+    IsoStaged st = { -1, 0.0f };
+    if constexpr (SRC == ISO_TILE) {
+        nrm_stage(s.operands, a.blob, a.wf, a.resolutions, lane);
+        st.c = nrm_c(a.blob);
+    }
+    __syncthreads();
+    return st;
+}
+
+// the brick's 9^3 values -> s.val; false: no live point (ISO_TILES: no contributing one) -- nothing else was read
+template <IsoSrc SRC, int DT>
+__device__ __forceinline__ bool iso_fill(const IsoArgs &a, IsoLds<SRC> &s, IsoStaged &st, int lane, const int b0[3])
+{
+    if constexpr (SRC == ISO_TILES) {
+        return iso_fill_tiles(a, s.operands, s.val, s.wsum, lane, b0, st.tile, st.c);
+    } else {
+        bool any = SRC == ISO_LOAD;
+#pragma unroll 1
+        for (int pass = 0; pass < kIsoPasses; ++pass) {
+            const int p = pass * 64 + lane;
+            int i, j, k;
+            const bool in = iso_point(a, b0, p, i, j, k);
+            float v = 0.0f;
+            if constexpr (SRC == ISO_LOAD) {
+                if (in) v = a.values[((size_t)i * (a.n[1] + 1) + j) * (a.n[2] + 1) + k];
+            } else {
+                const bool live = in && iso_point_live(a, i, j, k);
+                if (__ballot(live) != 0ull) {   // wave-uniform: every lane takes part in the product
+                    float x[3] = { 0.0f, 0.0f, 0.0f };
+                    if (live) {
+                        x[0] = iso_position(i, a.h[0]);
+                        x[1] = iso_position(j, a.h[1]);
+                        x[2] = iso_position(k, a.h[2]);
+                    }
+                    const float unused[3] = { 0.0f, 0.0f, 0.0f };
+                    float sg, gsum[3];
+                    density_grad<DT, false, true>(s.operands, a.features, a.T, unused, st.c, lane, x, sg, gsum);
+                    if (live) v = nrm_softplus(sg);
+                    any = true;
+                }
+            }
+            if (p < kIsoPts) s.val[p] = v;
+        }
+        return any;
+    }
 }
 
 // cell (w, lane >> 3, lane & 7) of the brick: its corner values (corner = dx << 2 | dy << 1 | dz), inside bits, and whether the
@@ -172,155 +308,19 @@ __device__ __forceinline__ bool iso_quad(const IsoArgs &a, bool valid, const int
     return valid && ((ins ^ far) & 1u) && cc[O1] >= 1 && cc[O2] >= 1;
 }
 
-// count pass of one brick behind its fill: the active-cell mask and the vertex / quad counts (any == false: nothing is active)
-__device__ __forceinline__ void iso_count_brick(const IsoArgs &a, const float *val, const int b0[3], int brick, int lane, bool any)
-{
-    unsigned long long word = 0ull;
-    int vc = 0, qc = 0;
-    if (any) {
-        for (int w = 0; w < kIsoB; ++w) {
-            int cc[3];
-            float cv[8];
-            unsigned ins;
-            const bool valid = iso_cell(a, val, b0, w, lane, cc, cv, ins);
-            const unsigned long long m = __ballot(valid && ins != 0u && ins != 0xffu);
-            if (lane == w) word = m;
-            vc += __popcll(m);
-            qc += __popcll(__ballot(iso_quad<0>(a, valid, cc, ins))) + __popcll(__ballot(iso_quad<1>(a, valid, cc, ins))) +
-                  __popcll(__ballot(iso_quad<2>(a, valid, cc, ins)));
-        }
-    }
-    if (lane < kIsoB) a.mask[(size_t)brick * kIsoB + lane] = word;
-    if (lane == 0) {
-        a.vbase[brick] = vc;
-        a.qbase[brick] = qc;
-    }
-}
-
-// ---- the scene source (the definition: include/scanerf_hip.h)
-struct IsoTilesArgs {
-    IsoArgs g;             // lattice, level, scratch, outputs; origin / step: the world box's corner and size / n
-    const void *tables;    // [nb,16,T,2] f16
-    const float *blobs;    // [nb, SCANERF_PARAMSIZE]
-    const int32_t *res;    // [nb,16,3]
-    Tiles t;
-};
-
-constexpr int kIsoVal = kIsoPts + 7;   // floats of a brick's value array in LDS
-
-__device__ __forceinline__ float iso_contracted(float pt)
-{
-#pragma clang fp contract(off)
-    const float m = 2.0f * pt;
-    return m - 1.0f;
-}
-
-__device__ __forceinline__ float iso_add_product(float acc, float w, float s)
-{
-#pragma clang fp contract(off)
-    const float m = w * s;
-    return acc + m;
-}
-
-// The brick's 9^3 blended values -> val, the weight sums in wsum (both LDS); false: no point of the brick contributes for any tile
-// (no table and no decoder was read).  staged / c: the tile whose operands lds holds and its constant, kept across bricks.
-__device__ __forceinline__ bool iso_fill_tiles(const IsoTilesArgs &a, float *lds, float *val, float *wsum, int lane, const int b0[3],
-                                               int &staged, float &c)
-{
-#pragma clang fp contract(off)   // (the sums below take products of render_infer_device.h's functions: separately rounded)
-    const IsoArgs &g = a.g;
-    for (int p = lane; p < kIsoVal; p += 64) {
-        val[p] = 0.0f;
-        wsum[p] = 0.0f;
-    }
-    // The brick's world extent.  Position, tile coordinate and membership are monotone in the lattice index (step, size > 0 and every
-    // operation rounds monotonically), so a tile lists a point of the brick only if it passes this test at the brick's end points.
-    float wlo[3], whi[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int last = b0[k] + kIsoB < g.n[k] ? b0[k] + kIsoB : g.n[k];
-        wlo[k] = iso_world(g.origin[k], (float)b0[k], g.step[k]);
-        whi[k] = iso_world(g.origin[k], (float)last, g.step[k]);
-    }
-    bool any = false;
-    for (int base = 0; base < a.t.nb; base += 64) {
-        const int bt = base + lane;
-        bool reach = bt < a.t.nb;
-        if (reach) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float ck = a.t.corners[3 * bt + k], sk = a.t.sizes[3 * bt + k];
-                reach = reach && tile_coord(wlo[k], ck, sk) <= 1.0f && tile_coord(whi[k], ck, sk) >= 0.0f;
-            }
-        }
-        unsigned long long cand = __ballot(reach);
-        while (cand != 0ull) {   // wave-uniform, ascending tile index
-            const int b = base + __ffsll((long long)cand) - 1;
-            cand &= cand - 1ull;
-            const float *cb = a.t.corners + 3 * b, *sb = a.t.sizes + 3 * b;
-#pragma unroll 1
-            for (int pass = 0; pass < kIsoPasses; ++pass) {
-                const int p = pass * 64 + lane;
-                const int lx = p / (kIsoP * kIsoP), r = p - lx * (kIsoP * kIsoP), ly = r / kIsoP, lz = r - ly * kIsoP;
-                const int i = b0[0] + lx, j = b0[1] + ly, k = b0[2] + lz;
-                const bool in = p < kIsoPts && i <= g.n[0] && j <= g.n[1] && k <= g.n[2];
-                const float wp[3] = { iso_world(g.origin[0], (float)i, g.step[0]), iso_world(g.origin[1], (float)j, g.step[1]),
-                                      iso_world(g.origin[2], (float)k, g.step[2]) };
-                float pt[3];
-                tile_point(wp, cb, sb, pt);
-                const bool listed = in && pt[0] >= 0.0f && pt[0] <= 1.0f && pt[1] >= 0.0f && pt[1] <= 1.0f && pt[2] >= 0.0f && pt[2] <= 1.0f;
-                const float w = tile_weight(pt, sb);
-                const int64_t cell = tile_cell(a.t, b, pt);   // (for every lane: render_infer_device.h)
-                if (listed) wsum[p] = wsum[p] + w;            // the weight counts whether or not the cell is occupied
-                const bool run = listed && a.t.occ[cell] != 0;
-                if (__ballot(run) == 0ull) continue;          // wave-uniform
-                if (b != staged) {
-                    __syncthreads();   // (one wave: the reads of the tile staged before are done)
-                    const float *blob = a.blobs + (size_t)b * SCANERF_PARAMSIZE;
-                    nrm_stage<false>(lds, blob, nullptr, a.res + (size_t)b * 48, lane);
-                    c = nrm_c(blob);
-                    staged = b;
-                    __syncthreads();
-                }
-                float x[3] = { 0.0f, 0.0f, 0.0f };   // (lanes that do not run: the one-tile fill's dead lanes)
-                if (run) {
-                    x[0] = iso_contracted(pt[0]);
-                    x[1] = iso_contracted(pt[1]);
-                    x[2] = iso_contracted(pt[2]);
-                }
-                const float unused[3] = { 0.0f, 0.0f, 0.0f };
-                float s, gsum[3];
-                density_grad<SCANERF_F16, false, true>(lds, (const char *)a.tables + (size_t)b * 16 * a.g.T * 4, a.g.T, unused, c, lane, x, s, gsum);
-                if (run) val[p] = iso_add_product(val[p], w, nrm_softplus(s));
-                any = true;
-            }
-        }
-    }
-    if (any) {
-        for (int p = lane; p < kIsoPts; p += 64) val[p] = val[p] * inv_weight(wsum[p]);
-    }
-    return any;
-}
-
-template <int DT, bool DENSE>
+// count pass: per brick the active-cell mask and the vertex / quad counts
+template <IsoSrc SRC, int DT>
 __global__ void __launch_bounds__(64) k_iso_count(IsoArgs a)
 {
-    __shared__ __attribute__((aligned(16))) float lds[DENSE ? 4 : NL_TOTAL];
-    __shared__ float val[kIsoPts + 7];
+    __shared__ IsoLds<SRC> s;
     const int lane = threadIdx.x;
-    float c = 0.0f;
-    if constexpr (!DENSE) {
-        nrm_stage(lds, a.blob, a.wf, a.resolutions, lane);
-        c = nrm_c(a.blob);
-    }
-    __syncthreads();
+    IsoStaged st = iso_begin(a, s, lane);
     for (int brick = blockIdx.x; brick < a.nbricks; brick += gridDim.x) {
         int b0[3];
         iso_brick_origin(a, brick, b0);
         __syncthreads();   // (the previous brick's reads of val are done)
-        const bool any = iso_fill<DT, DENSE ? ISO_LOAD : ISO_TILE>(a, lds, val, lane, c, b0);
+        const bool any = iso_fill<SRC, DT>(a, s, st, lane, b0);
         __syncthreads();
-        // (iso_count_brick's statements, spelled out: through the helper this kernel compiles to another listing than the validated one)
         unsigned long long word = 0ull;
         int vc = 0, qc = 0;
         if (any) {
@@ -328,7 +328,7 @@ __global__ void __launch_bounds__(64) k_iso_count(IsoArgs a)
                 int cc[3];
                 float cv[8];
                 unsigned ins;
-                const bool valid = iso_cell(a, val, b0, w, lane, cc, cv, ins);
+                const bool valid = iso_cell(a, s.val, b0, w, lane, cc, cv, ins);
                 const unsigned long long m = __ballot(valid && ins != 0u && ins != 0xffu);
                 if (lane == w) word = m;
                 vc += __popcll(m);
@@ -341,23 +341,6 @@ __global__ void __launch_bounds__(64) k_iso_count(IsoArgs a)
             a.vbase[brick] = vc;
             a.qbase[brick] = qc;
         }
-    }
-}
-
-__global__ void __launch_bounds__(64) k_iso_count_tiles(IsoTilesArgs a)
-{
-    __shared__ __attribute__((aligned(16))) float lds[NL_TOTAL];
-    __shared__ float val[kIsoVal], wsum[kIsoVal];
-    const int lane = threadIdx.x;
-    int staged = -1;
-    float c = 0.0f;
-    for (int brick = blockIdx.x; brick < a.g.nbricks; brick += gridDim.x) {
-        int b0[3];
-        iso_brick_origin(a.g, brick, b0);
-        __syncthreads();   // (the previous brick's reads of val are done)
-        const bool any = iso_fill_tiles(a, lds, val, wsum, lane, b0, staged, c);
-        __syncthreads();
-        iso_count_brick(a.g, val, b0, brick, lane, any);
     }
 }
 
@@ -473,54 +456,14 @@ __device__ __forceinline__ void iso_emit_quad(const IsoArgs &a, const int cc[3],
     f[5] = id[3];
 }
 
-// emit pass of one brick behind its fill: vertices from v0 on, quads from q0 on (below = the lanes before this one)
-__device__ __forceinline__ void iso_emit_brick(const IsoArgs &a, const float *val, const int b0[3], int lane, unsigned long long below,
-                                               int v0, int q0)
-{
-    int vrun = v0, qrun = q0;
-    for (int w = 0; w < kIsoB; ++w) {
-        int cc[3];
-        float cv[8];
-        unsigned ins;
-        const bool valid = iso_cell(a, val, b0, w, lane, cc, cv, ins);
-        const bool active = valid && ins != 0u && ins != 0xffu;
-        const unsigned long long m = __ballot(active);
-        if (active) {
-            const int vid = vrun + __popcll(m & below);
-            float L[3];
-            iso_cell_vertex(cc, cv, a.level, L);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                a.vertices[3 * (size_t)vid + k] = iso_world(a.origin[k], L[k], a.step[k]);
-                a.cells[3 * (size_t)vid + k] = cc[k];
-                if (a.lattice) a.lattice[3 * (size_t)vid + k] = L[k];
-            }
-        }
-        vrun += __popcll(m);
-        const bool qa = iso_quad<0>(a, valid, cc, ins), qb = iso_quad<1>(a, valid, cc, ins), qc = iso_quad<2>(a, valid, cc, ins);
-        const unsigned long long ma = __ballot(qa), mb = __ballot(qb), mc = __ballot(qc);
-        if (qa) iso_emit_quad<0>(a, cc, ins, qrun + __popcll(ma & below));
-        qrun += __popcll(ma);
-        if (qb) iso_emit_quad<1>(a, cc, ins, qrun + __popcll(mb & below));
-        qrun += __popcll(mb);
-        if (qc) iso_emit_quad<2>(a, cc, ins, qrun + __popcll(mc & below));
-        qrun += __popcll(mc);
-    }
-}
-
-template <int DT, bool DENSE>
+// emit pass: per brick with a vertex, its vertices from the brick's vertex base on and its quads from its quad base on
+template <IsoSrc SRC, int DT>
 __global__ void __launch_bounds__(64) k_iso_emit(IsoArgs a)
 {
-    __shared__ __attribute__((aligned(16))) float lds[DENSE ? 4 : NL_TOTAL];
-    __shared__ float val[kIsoPts + 7];
+    __shared__ IsoLds<SRC> s;
     const int lane = threadIdx.x;
-    float c = 0.0f;
-    if constexpr (!DENSE) {
-        nrm_stage(lds, a.blob, a.wf, a.resolutions, lane);
-        c = nrm_c(a.blob);
-    }
-    __syncthreads();
-    const unsigned long long below = (1ull << lane) - 1ull;
+    IsoStaged st = iso_begin(a, s, lane);
+    const unsigned long long below = (1ull << lane) - 1ull;   // the lanes before this one
     for (int brick = blockIdx.x; brick < a.nbricks; brick += gridDim.x) {
         const int v0 = a.vbase[brick], v1 = a.vbase[brick + 1], q0 = a.qbase[brick], q1 = a.qbase[brick + 1];
         // no vertex: no quad either (a crossing edge makes its cell active).  Outputs smaller than the scratch says: not written.
@@ -528,15 +471,14 @@ __global__ void __launch_bounds__(64) k_iso_emit(IsoArgs a)
         int b0[3];
         iso_brick_origin(a, brick, b0);
         __syncthreads();
-        iso_fill<DT, DENSE ? ISO_LOAD : ISO_TILE>(a, lds, val, lane, c, b0);
+        iso_fill<SRC, DT>(a, s, st, lane, b0);
         __syncthreads();
-        // (iso_emit_brick's statements, spelled out: as in k_iso_count)
         int vrun = v0, qrun = q0;
         for (int w = 0; w < kIsoB; ++w) {
             int cc[3];
             float cv[8];
             unsigned ins;
-            const bool valid = iso_cell(a, val, b0, w, lane, cc, cv, ins);
+            const bool valid = iso_cell(a, s.val, b0, w, lane, cc, cv, ins);
             const bool active = valid && ins != 0u && ins != 0xffu;
             const unsigned long long m = __ballot(active);
             if (active) {
@@ -563,26 +505,7 @@ __global__ void __launch_bounds__(64) k_iso_emit(IsoArgs a)
     }
 }
 
-__global__ void __launch_bounds__(64) k_iso_emit_tiles(IsoTilesArgs a)
-{
-    __shared__ __attribute__((aligned(16))) float lds[NL_TOTAL];
-    __shared__ float val[kIsoVal], wsum[kIsoVal];
-    const int lane = threadIdx.x;
-    int staged = -1;
-    float c = 0.0f;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    for (int brick = blockIdx.x; brick < a.g.nbricks; brick += gridDim.x) {
-        const int v0 = a.g.vbase[brick], v1 = a.g.vbase[brick + 1], q0 = a.g.qbase[brick], q1 = a.g.qbase[brick + 1];
-        if (v1 == v0 || v0 < 0 || q0 < 0 || v1 > a.g.V || q1 > a.g.F / 2) continue;   // (as k_iso_emit)
-        int b0[3];
-        iso_brick_origin(a.g, brick, b0);
-        __syncthreads();
-        iso_fill_tiles(a, lds, val, wsum, lane, b0, staged, c);
-        __syncthreads();
-        iso_emit_brick(a.g, val, b0, lane, below, v0, q0);
-    }
-}
-
+// ---- host side: the checks of the seven exports, in the order they fire, and one launcher per pass
 int64_t iso_bricks(int nx, int ny, int nz)
 {
     return (int64_t)ceil_div(nx, kIsoB) * ceil_div(ny, kIsoB) * ceil_div(nz, kIsoB);
@@ -606,29 +529,7 @@ int iso_check_lattice(const char *op, int nx, int ny, int nz, float level)
     return 0;
 }
 
-// lattice, scratch carving and the brick grid
-int iso_common(const char *op, IsoArgs &a, int nx, int ny, int nz, float level, void *scratch, size_t scratch_bytes)
-{
-    if (int e = iso_check_lattice(op, nx, ny, nz, level)) return e;
-    SCANERF_REQUIRE(scratch, "%s: null pointer (scratch)", op);
-    SCANERF_REQUIRE(((uintptr_t)scratch & 15) == 0, "%s: scratch must be 16-byte aligned", op);
-    const size_t need = iso_scratch_bytes(nx, ny, nz);
-    SCANERF_REQUIRE(scratch_bytes >= need, "%s: scratch holds %zu B, %zu needed (scanerf_isosurface_scratch_bytes)", op, scratch_bytes, need);
-    a.n[0] = nx; a.n[1] = ny; a.n[2] = nz;
-    for (int k = 0; k < 3; ++k) {
-        a.nb[k] = ceil_div(a.n[k], kIsoB);
-        a.h[k] = 2.0f / (float)a.n[k];
-    }
-    a.nbricks = (int)iso_bricks(nx, ny, nz);
-    a.level = level;
-    char *p = (char *)scratch + kIsoHead;
-    a.mask = (unsigned long long *)p;
-    p += (size_t)a.nbricks * kIsoB * sizeof(unsigned long long);
-    a.vbase = (int *)p;
-    a.qbase = a.vbase + a.nbricks + 1;
-    return 0;
-}
-
+// the one-tile source's arguments
 int iso_check_model(const char *op, IsoArgs &a, const void *features, int feat_dtype, const int32_t *resolutions, const float *mlp_blob,
                     const float *weight_feature, int T, const uint8_t *occupied_grid, const int32_t *log2dim, long long occ_cells)
 {
@@ -649,44 +550,10 @@ int iso_check_model(const char *op, IsoArgs &a, const void *features, int feat_d
     return 0;
 }
 
-int iso_check_outputs(const char *op, IsoArgs &a, const float *origin, const float *spacing, float *vertices, int32_t *faces,
-                      int32_t *cells, float *lattice, int V, int F)
-{
-    SCANERF_REQUIRE(V >= 0 && F >= 0 && (F & 1) == 0, "%s: V=%d F=%d (F counts triangles, two per quad)", op, V, F);
-    SCANERF_REQUIRE(origin && spacing, "%s: null pointer (origin / spacing)", op);
-    SCANERF_REQUIRE(V == 0 || (vertices && cells), "%s: null pointer (vertices / cells)", op);
-    SCANERF_REQUIRE(F == 0 || faces, "%s: null pointer (faces)", op);
-    for (int k = 0; k < 3; ++k) a.origin[k] = origin[k];
-    a.vertices = vertices; a.faces = faces; a.cells = cells; a.lattice = lattice; a.V = V; a.F = F;
-    return 0;
-}
-
-int iso_blocks(const IsoArgs &a) { return a.nbricks < kIsoMaxBlocks ? a.nbricks : kIsoMaxBlocks; }
-
-template <bool DENSE>
-int iso_launch_count(const char *op, const IsoArgs &a, int feat_dtype, void *scratch, hipStream_t st)
-{
-    if (DENSE) hipLaunchKernelGGL((k_iso_count<SCANERF_F32, true>), dim3(iso_blocks(a)), dim3(64), 0, st, a);
-    else if (feat_dtype == SCANERF_F32) hipLaunchKernelGGL((k_iso_count<SCANERF_F32, false>), dim3(iso_blocks(a)), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL((k_iso_count<SCANERF_F16, false>), dim3(iso_blocks(a)), dim3(64), 0, st, a);
-    if (int e = check_launch(op)) return e;
-    hipLaunchKernelGGL(k_iso_scan, dim3(1), dim3(kIsoScanThreads), 0, st, a.vbase, a.qbase, a.nbricks, (long long *)scratch);
-    return check_launch(op);
-}
-
-template <bool DENSE>
-int iso_launch_emit(const char *op, const IsoArgs &a, int feat_dtype, hipStream_t st)
-{
-    if (DENSE) hipLaunchKernelGGL((k_iso_emit<SCANERF_F32, true>), dim3(iso_blocks(a)), dim3(64), 0, st, a);
-    else if (feat_dtype == SCANERF_F32) hipLaunchKernelGGL((k_iso_emit<SCANERF_F32, false>), dim3(iso_blocks(a)), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL((k_iso_emit<SCANERF_F16, false>), dim3(iso_blocks(a)), dim3(64), 0, st, a);
-    return check_launch(op);
-}
-
 // the scene source's arguments (everything but lattice, scratch and outputs); origin / step: the world box
-int iso_check_tiles(const char *op, IsoTilesArgs &a, const void *tables_f16, const float *blobs, const int32_t *resolution,
-                    const uint8_t *occ, const int64_t *grid_starts, const int32_t *log2dim, const float *corners, const float *sizes, int T,
-                    int nb, const float *box_corner, const float *box_size, int nx, int ny, int nz)
+int iso_check_tiles(const char *op, IsoArgs &a, const void *tables_f16, const float *blobs, const int32_t *resolution, const uint8_t *occ,
+                    const int64_t *grid_starts, const int32_t *log2dim, const float *corners, const float *sizes, int T, int nb,
+                    const float *box_corner, const float *box_size, int nx, int ny, int nz)
 {
     SCANERF_REQUIRE(nb >= 1, "%s: nb=%d (at least one tile)", op, nb);
     SCANERF_REQUIRE(T >= 2 && (T & (T - 1)) == 0, "%s: T=%d must be a power of two", op, T);
@@ -697,56 +564,88 @@ int iso_check_tiles(const char *op, IsoTilesArgs &a, const void *tables_f16, con
     for (int k = 0; k < 3; ++k) {
         SCANERF_REQUIRE(box_size[k] > 0.0f && box_size[k] <= 3.0e38f, "%s: box_size[%d]=%g must be positive and finite", op, k,
                         (double)box_size[k]);
-        a.g.origin[k] = box_corner[k];
-        a.g.step[k] = box_size[k] / (float)n[k];
+        a.origin[k] = box_corner[k];
+        a.step[k] = box_size[k] / (float)n[k];
     }
-    a.tables = tables_f16; a.blobs = blobs; a.res = resolution; a.g.T = T;
+    a.features = tables_f16; a.blob = blobs; a.resolutions = resolution; a.T = T;
     a.t = make_tiles(corners, sizes, occ, grid_starts, log2dim, nb);
     return 0;
+}
+
+// the emit pass's own arguments.  The world step is `extent` itself for the dense op (its spacing) and extent / n for a box
+struct IsoOut {
+    const float *origin, *extent;
+    float *vertices;
+    int32_t *faces, *cells;
+    float *lattice;
+    int V, F;
+};
+
+int iso_check_outputs(const char *op, IsoSrc src, IsoArgs &a, const IsoOut &o)
+{
+    SCANERF_REQUIRE(o.V >= 0 && o.F >= 0 && (o.F & 1) == 0, "%s: V=%d F=%d (F counts triangles, two per quad)", op, o.V, o.F);
+    SCANERF_REQUIRE(o.origin && o.extent, "%s: null pointer (origin / spacing)", op);
+    SCANERF_REQUIRE(o.V == 0 || (o.vertices && o.cells), "%s: null pointer (vertices / cells)", op);
+    SCANERF_REQUIRE(o.F == 0 || o.faces, "%s: null pointer (faces)", op);
+    for (int k = 0; k < 3; ++k) {
+        a.origin[k] = o.origin[k];
+        a.step[k] = src == ISO_LOAD ? o.extent[k] : o.extent[k] / (float)a.n[k];
+    }
+    a.vertices = o.vertices; a.faces = o.faces; a.cells = o.cells; a.lattice = o.lattice; a.V = o.V; a.F = o.F;
+    return 0;
+}
+
+template <IsoSrc SRC, int DT>
+void iso_launch(bool emit, const IsoArgs &a, hipStream_t st)
+{
+    const dim3 grid(a.nbricks < kIsoMaxBlocks ? a.nbricks : kIsoMaxBlocks);
+    if (emit) hipLaunchKernelGGL((k_iso_emit<SRC, DT>), grid, dim3(64), 0, st, a);
+    else hipLaunchKernelGGL((k_iso_count<SRC, DT>), grid, dim3(64), 0, st, a);
+}
+
+// Everything behind the source's own checks, for all six launching exports: lattice, scratch carving and the brick grid, the emit
+// pass's outputs (out != nullptr), then the pass's kernel for (source, table dtype) -- behind the count kernel the scan.
+int iso_run(const char *op, IsoSrc src, int feat_dtype, IsoArgs &a, int nx, int ny, int nz, float level, void *scratch,
+            size_t scratch_bytes, const IsoOut *out, scanerf_stream_t stream)
+{
+    if (int e = iso_check_lattice(op, nx, ny, nz, level)) return e;
+    SCANERF_REQUIRE(scratch, "%s: null pointer (scratch)", op);
+    SCANERF_REQUIRE(((uintptr_t)scratch & 15) == 0, "%s: scratch must be 16-byte aligned", op);
+    const size_t need = iso_scratch_bytes(nx, ny, nz);
+    SCANERF_REQUIRE(scratch_bytes >= need, "%s: scratch holds %zu B, %zu needed (scanerf_isosurface_scratch_bytes)", op, scratch_bytes, need);
+    SCANERF_REQUIRE(src != ISO_LOAD || a.values, "%s: null pointer (values)", op);
+    a.n[0] = nx; a.n[1] = ny; a.n[2] = nz;
+    for (int k = 0; k < 3; ++k) {
+        a.nb[k] = ceil_div(a.n[k], kIsoB);
+        a.h[k] = 2.0f / (float)a.n[k];
+    }
+    a.nbricks = (int)iso_bricks(nx, ny, nz);
+    a.level = level;
+    char *p = (char *)scratch + kIsoHead;
+    a.mask = (unsigned long long *)p;
+    p += (size_t)a.nbricks * kIsoB * sizeof(unsigned long long);
+    a.vbase = (int *)p;
+    a.qbase = a.vbase + a.nbricks + 1;
+    if (out) {
+        if (int e = iso_check_outputs(op, src, a, *out)) return e;
+        if (out->V == 0) return 0;
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    const bool emit = out != nullptr;
+    if (src == ISO_LOAD) iso_launch<ISO_LOAD, SCANERF_F32>(emit, a, st);
+    else if (src == ISO_TILES) iso_launch<ISO_TILES, SCANERF_F16>(emit, a, st);
+    else if (feat_dtype == SCANERF_F32) iso_launch<ISO_TILE, SCANERF_F32>(emit, a, st);
+    else iso_launch<ISO_TILE, SCANERF_F16>(emit, a, st);
+    if (int e = check_launch(op)) return e;
+    if (emit) return 0;
+    hipLaunchKernelGGL(k_iso_scan, dim3(1), dim3(kIsoScanThreads), 0, st, a.vbase, a.qbase, a.nbricks, (long long *)scratch);
+    return check_launch(op);
 }
 
 }  // namespace
 }  // namespace scanerf
 
 using namespace scanerf;
-
-SCANERF_API int scanerf_isosurface_count_tiles(const void *tables_f16, const float *blobs, const int32_t *resolution, const uint8_t *occ,
-                                               const int64_t *grid_starts, const int32_t *log2dim, const float *corners,
-                                               const float *sizes, int T, int nb, const float *box_corner, const float *box_size, int nx,
-                                               int ny, int nz, float level, void *scratch, size_t scratch_bytes, scanerf_stream_t stream)
-{
-    const char *op = "isosurface_count_tiles";
-    IsoTilesArgs a = {};
-    if (int e = iso_check_lattice(op, nx, ny, nz, level)) return e;
-    if (int e = iso_check_tiles(op, a, tables_f16, blobs, resolution, occ, grid_starts, log2dim, corners, sizes, T, nb, box_corner, box_size,
-                                nx, ny, nz))
-        return e;
-    if (int e = iso_common(op, a.g, nx, ny, nz, level, scratch, scratch_bytes)) return e;
-    hipLaunchKernelGGL(k_iso_count_tiles, dim3(iso_blocks(a.g)), dim3(64), 0, (hipStream_t)stream, a);
-    if (int e = check_launch(op)) return e;
-    hipLaunchKernelGGL(k_iso_scan, dim3(1), dim3(kIsoScanThreads), 0, (hipStream_t)stream, a.g.vbase, a.g.qbase, a.g.nbricks,
-                       (long long *)scratch);
-    return check_launch(op);
-}
-
-SCANERF_API int scanerf_isosurface_emit_tiles(const void *tables_f16, const float *blobs, const int32_t *resolution, const uint8_t *occ,
-                                              const int64_t *grid_starts, const int32_t *log2dim, const float *corners,
-                                              const float *sizes, int T, int nb, const float *box_corner, const float *box_size, int nx,
-                                              int ny, int nz, float level, const void *scratch, size_t scratch_bytes, float *vertices,
-                                              int32_t *faces, int32_t *cells, float *lattice, int V, int F, scanerf_stream_t stream)
-{
-    const char *op = "isosurface_emit_tiles";
-    IsoTilesArgs a = {};
-    if (int e = iso_check_lattice(op, nx, ny, nz, level)) return e;
-    if (int e = iso_check_tiles(op, a, tables_f16, blobs, resolution, occ, grid_starts, log2dim, corners, sizes, T, nb, box_corner, box_size,
-                                nx, ny, nz))
-        return e;
-    if (int e = iso_common(op, a.g, nx, ny, nz, level, const_cast<void *>(scratch), scratch_bytes)) return e;
-    if (int e = iso_check_outputs(op, a.g, box_corner, box_size, vertices, faces, cells, lattice, V, F)) return e;
-    if (V == 0) return 0;
-    hipLaunchKernelGGL(k_iso_emit_tiles, dim3(iso_blocks(a.g)), dim3(64), 0, (hipStream_t)stream, a);
-    return check_launch(op);
-}
 
 SCANERF_API size_t scanerf_isosurface_scratch_bytes(int nx, int ny, int nz)
 {
@@ -758,10 +657,8 @@ SCANERF_API int scanerf_isosurface_count_dense(const float *values, int nx, int 
                                                scanerf_stream_t stream)
 {
     IsoArgs a = {};
-    if (int e = iso_common("isosurface_count_dense", a, nx, ny, nz, level, scratch, scratch_bytes)) return e;
-    SCANERF_REQUIRE(values, "isosurface_count_dense: null pointer (values)");
     a.values = values;
-    return iso_launch_count<true>("isosurface_count_dense", a, SCANERF_F32, scratch, (hipStream_t)stream);
+    return iso_run("isosurface_count_dense", ISO_LOAD, SCANERF_F32, a, nx, ny, nz, level, scratch, scratch_bytes, nullptr, stream);
 }
 
 SCANERF_API int scanerf_isosurface_emit_dense(const float *values, int nx, int ny, int nz, float level, const float *origin,
@@ -769,13 +666,10 @@ SCANERF_API int scanerf_isosurface_emit_dense(const float *values, int nx, int n
                                               int32_t *faces, int32_t *cells, float *lattice, int V, int F, scanerf_stream_t stream)
 {
     IsoArgs a = {};
-    if (int e = iso_common("isosurface_emit_dense", a, nx, ny, nz, level, const_cast<void *>(scratch), scratch_bytes)) return e;
-    SCANERF_REQUIRE(values, "isosurface_emit_dense: null pointer (values)");
-    if (int e = iso_check_outputs("isosurface_emit_dense", a, origin, spacing, vertices, faces, cells, lattice, V, F)) return e;
-    if (V == 0) return 0;
     a.values = values;
-    for (int k = 0; k < 3; ++k) a.step[k] = spacing[k];
-    return iso_launch_emit<true>("isosurface_emit_dense", a, SCANERF_F32, (hipStream_t)stream);
+    const IsoOut out = { origin, spacing, vertices, faces, cells, lattice, V, F };
+    return iso_run("isosurface_emit_dense", ISO_LOAD, SCANERF_F32, a, nx, ny, nz, level, const_cast<void *>(scratch), scratch_bytes, &out,
+                   stream);
 }
 
 SCANERF_API int scanerf_isosurface_count(const void *features, int feat_dtype, const int32_t *resolutions, const float *mlp_blob,
@@ -783,13 +677,12 @@ SCANERF_API int scanerf_isosurface_count(const void *features, int feat_dtype, c
                                          long long occ_cells, int nx, int ny, int nz, float level, void *scratch, size_t scratch_bytes,
                                          scanerf_stream_t stream)
 {
+    const char *op = "isosurface_count";
     IsoArgs a = {};
-    if (int e = iso_check_lattice("isosurface_count", nx, ny, nz, level)) return e;
-    if (int e = iso_check_model("isosurface_count", a, features, feat_dtype, resolutions, mlp_blob, weight_feature, T, occupied_grid, log2dim,
-                                occ_cells))
+    if (int e = iso_check_lattice(op, nx, ny, nz, level)) return e;
+    if (int e = iso_check_model(op, a, features, feat_dtype, resolutions, mlp_blob, weight_feature, T, occupied_grid, log2dim, occ_cells))
         return e;
-    if (int e = iso_common("isosurface_count", a, nx, ny, nz, level, scratch, scratch_bytes)) return e;
-    return iso_launch_count<false>("isosurface_count", a, feat_dtype, scratch, (hipStream_t)stream);
+    return iso_run(op, ISO_TILE, feat_dtype, a, nx, ny, nz, level, scratch, scratch_bytes, nullptr, stream);
 }
 
 SCANERF_API int scanerf_isosurface_emit(const void *features, int feat_dtype, const int32_t *resolutions, const float *mlp_blob,
@@ -798,14 +691,41 @@ SCANERF_API int scanerf_isosurface_emit(const void *features, int feat_dtype, co
                                         const float *occ_size, const void *scratch, size_t scratch_bytes, float *vertices, int32_t *faces,
                                         int32_t *cells, float *lattice, int V, int F, scanerf_stream_t stream)
 {
+    const char *op = "isosurface_emit";
     IsoArgs a = {};
-    if (int e = iso_check_lattice("isosurface_emit", nx, ny, nz, level)) return e;
-    if (int e = iso_check_model("isosurface_emit", a, features, feat_dtype, resolutions, mlp_blob, weight_feature, T, occupied_grid, log2dim,
-                                occ_cells))
+    if (int e = iso_check_lattice(op, nx, ny, nz, level)) return e;
+    if (int e = iso_check_model(op, a, features, feat_dtype, resolutions, mlp_blob, weight_feature, T, occupied_grid, log2dim, occ_cells))
         return e;
-    if (int e = iso_common("isosurface_emit", a, nx, ny, nz, level, const_cast<void *>(scratch), scratch_bytes)) return e;
-    if (int e = iso_check_outputs("isosurface_emit", a, occ_corner, occ_size, vertices, faces, cells, lattice, V, F)) return e;
-    if (V == 0) return 0;
-    for (int k = 0; k < 3; ++k) a.step[k] = occ_size[k] / (float)a.n[k];
-    return iso_launch_emit<false>("isosurface_emit", a, feat_dtype, (hipStream_t)stream);
+    const IsoOut out = { occ_corner, occ_size, vertices, faces, cells, lattice, V, F };
+    return iso_run(op, ISO_TILE, feat_dtype, a, nx, ny, nz, level, const_cast<void *>(scratch), scratch_bytes, &out, stream);
+}
+
+SCANERF_API int scanerf_isosurface_count_tiles(const void *tables_f16, const float *blobs, const int32_t *resolution, const uint8_t *occ,
+                                               const int64_t *grid_starts, const int32_t *log2dim, const float *corners,
+                                               const float *sizes, int T, int nb, const float *box_corner, const float *box_size, int nx,
+                                               int ny, int nz, float level, void *scratch, size_t scratch_bytes, scanerf_stream_t stream)
+{
+    const char *op = "isosurface_count_tiles";
+    IsoArgs a = {};
+    if (int e = iso_check_lattice(op, nx, ny, nz, level)) return e;
+    if (int e = iso_check_tiles(op, a, tables_f16, blobs, resolution, occ, grid_starts, log2dim, corners, sizes, T, nb, box_corner, box_size,
+                                nx, ny, nz))
+        return e;
+    return iso_run(op, ISO_TILES, SCANERF_F16, a, nx, ny, nz, level, scratch, scratch_bytes, nullptr, stream);
+}
+
+SCANERF_API int scanerf_isosurface_emit_tiles(const void *tables_f16, const float *blobs, const int32_t *resolution, const uint8_t *occ,
+                                              const int64_t *grid_starts, const int32_t *log2dim, const float *corners,
+                                              const float *sizes, int T, int nb, const float *box_corner, const float *box_size, int nx,
+                                              int ny, int nz, float level, const void *scratch, size_t scratch_bytes, float *vertices,
+                                              int32_t *faces, int32_t *cells, float *lattice, int V, int F, scanerf_stream_t stream)
+{
+    const char *op = "isosurface_emit_tiles";
+    IsoArgs a = {};
+    if (int e = iso_check_lattice(op, nx, ny, nz, level)) return e;
+    if (int e = iso_check_tiles(op, a, tables_f16, blobs, resolution, occ, grid_starts, log2dim, corners, sizes, T, nb, box_corner, box_size,
+                                nx, ny, nz))
+        return e;
+    const IsoOut out = { box_corner, box_size, vertices, faces, cells, lattice, V, F };
+    return iso_run(op, ISO_TILES, SCANERF_F16, a, nx, ny, nz, level, const_cast<void *>(scratch), scratch_bytes, &out, stream);
 }

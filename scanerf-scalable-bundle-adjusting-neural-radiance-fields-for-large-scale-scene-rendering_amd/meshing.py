@@ -53,6 +53,20 @@ def _outputs(device, V, F):
             torch.empty((V, 3), dtype=torch.int32, device=device), torch.empty((V, 3), dtype=_f32, device=device))
 
 
+def _fused(device, n, count, emit, head, box=()):
+    """The sequence every fused route runs: scratch, the count pass `count`, the one host read of (V, F), the outputs, the emit pass
+    `emit` unless the mesh is empty.  count / emit: the exports' names behind "scanerf_"; head: the arguments both start with;
+    box: what the emit pass takes behind them (the world placement, where the head does not hold it already).  -> Mesh."""
+    scratch, nbytes = _scratch(device, n)
+    check(getattr(lib(), "scanerf_" + count)(*head, scratch.data_ptr(), nbytes, stream()), count)
+    V, F = _totals(scratch)
+    vertices, faces, cells, lattice = _outputs(device, V, F)
+    if V:
+        check(getattr(lib(), "scanerf_" + emit)(*head, *box, scratch.data_ptr(), nbytes, vertices.data_ptr(), faces.data_ptr(),
+                                                cells.data_ptr(), lattice.data_ptr(), V, F, stream()), emit)
+    return Mesh(vertices, faces, cells, lattice, None)
+
+
 def _host3(v, name):
     if isinstance(v, torch.Tensor):
         v = v.detach().cpu().tolist()
@@ -71,14 +85,7 @@ def surface_nets(values, level, origin=(0.0, 0.0, 0.0), spacing=(1.0, 1.0, 1.0))
     p = dev_ptr(values, _f32, "values")
     n = [int(s) - 1 for s in values.shape]
     o, sp = _host3(origin, "origin"), _host3(spacing, "spacing")
-    scratch, nbytes = _scratch(values.device, n)
-    check(lib().scanerf_isosurface_count_dense(p, *n, float(level), scratch.data_ptr(), nbytes, stream()), "isosurface_count_dense")
-    V, F = _totals(scratch)
-    vertices, faces, cells, lattice = _outputs(values.device, V, F)
-    if V:
-        check(lib().scanerf_isosurface_emit_dense(p, *n, float(level), o, sp, scratch.data_ptr(), nbytes, vertices.data_ptr(), faces.data_ptr(),
-                                                  cells.data_ptr(), lattice.data_ptr(), V, F, stream()), "isosurface_emit_dense")
-    return Mesh(vertices, faces, cells, lattice, None)
+    return _fused(values.device, n, "isosurface_count_dense", "isosurface_emit_dense", (p, *n, float(level)), (o, sp))
 
 
 def lattice_positions(n, device):
@@ -132,15 +139,8 @@ def extract_mesh(features, resolutions, blob, weight_feature, occupied_grid, log
         mesh = surface_nets(values.contiguous(), level, list(corner), step)
     else:
         l2d = (ctypes.c_int32 * 3)(*log2dim)
-        scratch, nbytes = _scratch(device, n)
         head = (*mid, T, occ, l2d, int(occupied_grid.numel()), *n, float(level))
-        check(lib().scanerf_isosurface_count(*head, scratch.data_ptr(), nbytes, stream()), "isosurface_count")
-        V, F = _totals(scratch)
-        vertices, faces, cells, lattice = _outputs(device, V, F)
-        if V:
-            check(lib().scanerf_isosurface_emit(*head, corner, size, scratch.data_ptr(), nbytes, vertices.data_ptr(), faces.data_ptr(),
-                                                cells.data_ptr(), lattice.data_ptr(), V, F, stream()), "isosurface_emit")
-        mesh = Mesh(vertices, faces, cells, lattice, None)
+        mesh = _fused(device, n, "isosurface_count", "isosurface_emit", head, (corner, size))
     if normals:
         if mesh.vertices.shape[0]:
             _, _, nrm = render.sigma_normals_points(_contracted(mesh.lattice, n), features, resolutions, blob, weight_feature,
@@ -234,15 +234,8 @@ def extract_scene_mesh(feature_tables, resolutions, blobs, corners, sizes, occup
         values = _scene_field_dense(feature_tables, resolutions, blobs, corners, sizes, occupied_grid, grid_starts, log2dim, corner, size, n)
         step = [_f32_div(size[k], n[k]) for k in range(3)]
         return surface_nets(torch.from_numpy(values).to(device).contiguous(), level, list(corner), step)
-    scratch, nbytes = _scratch(device, n)
     head = (tabs, *ptrs, T, nb, corner, size, *n, float(level))
-    check(lib().scanerf_isosurface_count_tiles(*head, scratch.data_ptr(), nbytes, stream()), "isosurface_count_tiles")
-    V, F = _totals(scratch)
-    vertices, faces, cells, lattice = _outputs(device, V, F)
-    if V:
-        check(lib().scanerf_isosurface_emit_tiles(*head, scratch.data_ptr(), nbytes, vertices.data_ptr(), faces.data_ptr(), cells.data_ptr(),
-                                                  lattice.data_ptr(), V, F, stream()), "isosurface_emit_tiles")
-    return Mesh(vertices, faces, cells, lattice, None)
+    return _fused(device, n, "isosurface_count_tiles", "isosurface_emit_tiles", head)
 
 
 def cells_per_axis(occ_size, longest):
