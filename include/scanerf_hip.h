@@ -759,6 +759,32 @@ int scanerf_isosurface_emit_tiles(const void *tables_f16, const float *blobs, co
                                   int nb, const float *box_corner /*[3] host*/, const float *box_size /*[3] host*/, int nx, int ny,
                                   int nz, float level, const void *scratch, size_t scratch_bytes, float *vertices, int32_t *faces,
                                   int32_t *cells, float *lattice, int V, int F, scanerf_stream_t stream);
+/* Blended density, its gradient and the normal at world points: the field of the scene mesh above and the gradient of
+ *   exactly that function, weight terms included, at points [N,3] f32 (device, world units, any order) -- the scene mesh's vertices,
+ *   for one.  The reference has no counterpart; the definition is this comment.  The tile arrays are those of
+ *   scanerf_isosurface_count_tiles.  float32; every product and every sum below is separately rounded; the per-tile density terms
+ *   carry the bits of scanerf_sigma_normals_points; tiles in ascending index, so a point's bits depend on its own position alone --
+ *   not on its neighbours in the launch, on N or on the launch.
+ *   Per point p and tile b (the expressions of the scene mesh):
+ *     pt = (p - corner_b) / size_b;  the point LISTS b iff 0 <= pt_c <= 1 on all three axes (no cap of four);
+ *     dis_c = (0.5 - |pt_c - 0.5|) size_b,c;  w_b = xz_weight(dis_x, dis_z);  W += w_b, whether or not the cell is occupied;
+ *     the weight's gradient in world units: s_c = +1 if pt_c < 0.5, -1 if pt_c > 0.5, 0 if equal, and by the branch xz_weight takes
+ *       gw_b = (s_x dis_z, 0, s_z dis_x) if dis_x != 0 and dis_z != 0;  (s_x, 0, 0) if only dis_x != 0;  (0, 0, s_z) if only
+ *       dis_z != 0;  0 otherwise;  C += gw_b (every listed tile);
+ *     b CONTRIBUTES iff it is listed and its occupancy cell (clamp(int(pt 2^log2dim_b))) is set; then sigma_b, gsigma_b = what
+ *       scanerf_sigma_normals_points returns as sigma and grad at x_c = 2 pt_c - 1 with tile b's table, blob and resolutions,
+ *       weight_feature == 1 and axis_scale_c = 2.0f / size_b,c;  num += w_b sigma_b;  A_k += w_b gsigma_b,k;  B_k += sigma_b gw_b,k.
+ *   After the last tile, inv = (W > 0 ? 1 / W : 1):
+ *     sigma = v = num inv;   grad_k = ((A_k + B_k) - v C_k) inv;   normal = grad * (-1 / (sqrt((g_x^2 + g_y^2) + g_z^2) + 1e-8)).
+ *   A point that no tile contributes to gets +0.0 in all seven outputs; every element of sigma [N], grad [N,3] (may be null: not
+ *   written) and normal [N,3] is written.  v has the bits of the scene mesh's field at that point.  The branch changes of xz_weight
+ *   and its kink at pt = 0.5 are discontinuities of the renderer's own weight: kept as they are.  This is NOT scanerf_pts_normals'
+ *   quantity: that op blends the tiles' UNIT normals by opacity per sample; this is the gradient of the blended density itself.
+ *   Any nb >= 1.  Refused before any launch: null pointers (but grad), N < 0, nb < 1, T not a power of two >= 2.  N == 0: no launch. */
+int scanerf_scene_sigma_normals_points(const float *points, const void *tables_f16, const float *blobs, const int32_t *resolution,
+                                       const uint8_t *occ, const int64_t *grid_starts, const int32_t *log2dim, const float *corners,
+                                       const float *sizes, int T, int nb, float *sigma, float *grad, float *normal, int N,
+                                       scanerf_stream_t stream);
 
 #define SCANERF_RAY_OUT 16
 

@@ -116,6 +116,7 @@ PROTOTYPES = {
     "scanerf_isosurface_emit": ("I", "PIPPPIPPLIIIFPPPZPPPPIIP", REQ),
     "scanerf_isosurface_count_tiles": ("I", "PPPPPPPPIIPPIIIFPZP", REQ),
     "scanerf_isosurface_emit_tiles": ("I", "PPPPPPPPIIPPIIIFPZPPPPIIP", REQ),
+    "scanerf_scene_sigma_normals_points": ("I", "PPPPPPPPPIIPPPIP", REQ),
 }
 SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if required]
 OPTIONAL_SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if not required]

@@ -168,10 +168,11 @@ _PLY_TYPES = {"char": "i1", "uchar": "u1", "short": "i2", "ushort": "u2", "int":
               "float32": "f4", "float64": "f8"}
 
 
-def read_ply(path):
+def read_ply(path, normals=False):
     """Triangle mesh from an ascii or binary_little_endian PLY -> (vertices [V,3] f32, faces [F,3] i32).
     Reads what plyIO.h's read_plyFile reads: vertex x/y/z and the face list property (vertex_indices /
-    vertex_index); other vertex properties are skipped, faces must be triangles."""
+    vertex_index); other vertex properties are skipped, faces must be triangles.  normals=True: the vertex properties nx/ny/nz as a
+    third array [V,3] f32 (the file must hold them)."""
     with open(path, "rb") as f:
         if f.readline().strip() != b"ply":
             raise ValueError(f"{path}: not a PLY file")
@@ -193,7 +194,8 @@ def read_ply(path):
                 break
         if fmt not in ("ascii", "binary_little_endian"):
             raise ValueError(f"{path}: unsupported PLY format {fmt}")
-        verts = faces = None
+        verts = faces = nrm = None
+        want = "xyz" if not normals else ("x", "y", "z", "nx", "ny", "nz")
         if fmt == "ascii":
             rows = f.read().decode("ascii", "replace").split("\n")
             pos = 0
@@ -204,7 +206,11 @@ def read_ply(path):
                     dt = np.dtype([(p[2], "<" + _PLY_TYPES[p[1]]) for p in e["props"]])
                     data = np.frombuffer(f.read(dt.itemsize * e["count"]), dtype=dt, count=e["count"])
                     if e["name"] == "vertex":
-                        verts = np.stack([data["x"], data["y"], data["z"]], 1).astype(np.float32)
+                        if any(c not in (data.dtype.names or ()) for c in want):
+                            raise ValueError(f"{path}: the vertex element lacks one of {list(want)}")
+                        verts = np.stack([data["x"], data["y"], data["z"]], 1).astype(np.float32).reshape(-1, 3)
+                        if normals:
+                            nrm = np.stack([data["nx"], data["ny"], data["nz"]], 1).astype(np.float32).reshape(-1, 3)
                 else:
                     out = []
                     for _ in range(e["count"]):
@@ -226,8 +232,13 @@ def read_ply(path):
                 pos += e["count"]
                 if e["name"] == "vertex":
                     names = [p[2] for p in e["props"]]
+                    if any(c not in names for c in want):
+                        raise ValueError(f"{path}: the vertex element lacks one of {list(want)}")
                     ix = [names.index(c) for c in "xyz"]
                     verts = np.array([[float(r[i]) for i in ix] for r in chunk], np.float32).reshape(-1, 3)
+                    if normals:
+                        ix = [names.index(c) for c in ("nx", "ny", "nz")]
+                        nrm = np.array([[float(r[i]) for i in ix] for r in chunk], np.float32).reshape(-1, 3)
                 elif e["name"] == "face":
                     faces = []
                     for r in chunk:
@@ -245,24 +256,32 @@ def read_ply(path):
         raise ValueError(f"{path}: needs a vertex and a face element")
     if any(fc is None or len(fc) != 3 for fc in faces):
         raise ValueError(f"{path}: only triangle faces are supported")
-    return verts, np.asarray(faces, np.int32).reshape(-1, 3)
+    faces = np.asarray(faces, np.int32).reshape(-1, 3)
+    return (verts, faces, nrm) if normals else (verts, faces)
 
 
-def write_ply(path, vertices, faces, binary=True):
+def write_ply(path, vertices, faces, binary=True, normals=None):
+    """vertices [V,3] f32, faces [F,3] i32 -> a PLY read_ply reads; normals [V,3]: stored as nx / ny / nz behind x / y / z."""
     vertices, faces = np.asarray(vertices, np.float32), np.asarray(faces, np.int32)
-    hdr = ("ply\nformat %s 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+    if normals is not None:
+        normals = np.asarray(normals, np.float32)
+        if normals.shape != vertices.shape:
+            raise ValueError(f"{path}: normals {normals.shape} do not match vertices {vertices.shape}")
+        vertices = np.concatenate([vertices.reshape(-1, 3), normals.reshape(-1, 3)], 1)
+    hdr = ("ply\nformat %s 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n%s"
            "element face %d\nproperty list uchar int vertex_indices\nend_header\n") % (
-               "binary_little_endian" if binary else "ascii", len(vertices), len(faces))
+               "binary_little_endian" if binary else "ascii", len(vertices),
+               "" if normals is None else "property float nx\nproperty float ny\nproperty float nz\n", len(faces))
     with open(path, "wb") as f:
         f.write(hdr.encode("ascii"))
         if binary:
-            f.write(vertices.astype("<f4").tobytes())
+            f.write(np.ascontiguousarray(vertices).astype("<f4").tobytes())
             rec = np.zeros(len(faces), dtype=[("n", "u1"), ("i", "<i4", (3,))])
             rec["n"], rec["i"] = 3, faces
             f.write(rec.tobytes())
         else:
             for v in vertices:
-                f.write(("%r %r %r\n" % (float(v[0]), float(v[1]), float(v[2]))).encode("ascii"))
+                f.write((" ".join("%r" % float(x) for x in v) + "\n").encode("ascii"))
             for t in faces:
                 f.write(("3 %d %d %d\n" % (t[0], t[1], t[2])).encode("ascii"))
 

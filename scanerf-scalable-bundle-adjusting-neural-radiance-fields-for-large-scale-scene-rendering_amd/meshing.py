@@ -7,6 +7,8 @@ lattice.  The reference has no mesh extraction; the definition is the comment of
                                                         liveness -> the dense op (the witness, and fine for small lattices)
     extract_scene_mesh(tables, ..., box, n, level)      ONE mesh of a tiled scene: the level set of the tiles' densities blended with
                                                         the multi-tile renderer's weights on a lattice over a world box
+    scene_sigma_normals_points(points, tables, ...)     that blended density, its gradient (weight terms included) and the normal at
+                                                        world points: the scene mesh's vertex normals
 
 All return a Mesh: vertices [V,3] f32 (world), faces [F,3] i32 (counter-clockwise seen from the outside), cells [V,3] i32 (the owning
 cell of each vertex), lattice [V,3] f32 (the vertices in lattice coordinates) and, on request, normals [V,3] f32.  Two launches with
@@ -197,17 +199,9 @@ def _scene_field_dense(feature_tables, resolutions, blobs, corners, sizes, occup
     return (num * inv).astype(f32)
 
 
-def extract_scene_mesh(feature_tables, resolutions, blobs, corners, sizes, occupied_grid, grid_starts, log2dim, box_corner, box_size, n,
-                       level, route="fused"):
-    """One mesh of a tiled scene: the level set of the field the multi-tile renderer draws -- the tiles' densities blended per lattice
-    point with the renderer's xz-distance weights -- on a lattice of n cells over the world box box_corner / box_size (the definition:
-    include/scanerf_hip.h, scanerf_isosurface_count_tiles).  The tile arrays are TileSetRenderer's: feature_tables [nb,16,T,2] f16,
-    resolutions [nb,16,3] i32, blobs [nb,13994], corners / sizes [nb,3] (render boxes), occupied_grid (the tiles' own grids,
-    concatenated), grid_starts [nb] i64, log2dim [nb,3] i32.  -> Mesh with normals None.  route="fused" never stores the lattice;
-    route="dense" composes host geometry -> render.sigma_normals_points per tile -> blend -> surface_nets (the witness)."""
-    if route not in ROUTES:
-        raise RuntimeError(f"scanerf: route must be one of {ROUTES}, got {route!r}")
-    n = _lattice_size(n)
+def _scene_tile_args(feature_tables, resolutions, blobs, corners, sizes, occupied_grid, grid_starts, log2dim):
+    """The checks of the tile arrays that every scene op makes, before any launch -> (the eight tile pointers of the exports:
+    tables, blobs, resolution, occ, grid_starts, log2dim, corners, sizes; T; nb)."""
     tabs = dev_ptr(feature_tables, torch.float16, "feature_tables")
     if feature_tables.dim() != 4 or feature_tables.shape[1] != 16 or feature_tables.shape[3] != 2:
         raise RuntimeError(f"scanerf: feature_tables must be [nb,16,T,2], got {tuple(feature_tables.shape)}")
@@ -224,6 +218,23 @@ def extract_scene_mesh(feature_tables, resolutions, blobs, corners, sizes, occup
         ptrs.append(dev_ptr(t, dt, name))
         if shape is not None and tuple(t.shape) != shape:
             raise RuntimeError(f"scanerf: {name} must be {list(shape)}, got {list(t.shape)}")
+    return (tabs, *ptrs), T, nb
+
+
+def extract_scene_mesh(feature_tables, resolutions, blobs, corners, sizes, occupied_grid, grid_starts, log2dim, box_corner, box_size, n,
+                       level, route="fused", normals=False):
+    """One mesh of a tiled scene: the level set of the field the multi-tile renderer draws -- the tiles' densities blended per lattice
+    point with the renderer's xz-distance weights -- on a lattice of n cells over the world box box_corner / box_size (the definition:
+    include/scanerf_hip.h, scanerf_isosurface_count_tiles).  The tile arrays are TileSetRenderer's: feature_tables [nb,16,T,2] f16,
+    resolutions [nb,16,3] i32, blobs [nb,13994], corners / sizes [nb,3] (render boxes), occupied_grid (the tiles' own grids,
+    concatenated), grid_starts [nb] i64, log2dim [nb,3] i32.  -> Mesh; normals=True adds scene_sigma_normals_points' normals at the
+    vertices (the gradient of the blended field itself), otherwise normals is None.  route="fused" never stores the
+    lattice; route="dense" composes host geometry -> render.sigma_normals_points per tile -> blend -> surface_nets (the witness)."""
+    if route not in ROUTES:
+        raise RuntimeError(f"scanerf: route must be one of {ROUTES}, got {route!r}")
+    n = _lattice_size(n)
+    tiles = (feature_tables, resolutions, blobs, corners, sizes, occupied_grid, grid_starts, log2dim)
+    head, T, nb = _scene_tile_args(*tiles)
     corner, size = _host3(box_corner, "box_corner"), _host3(box_size, "box_size")
     if not all(0 < s < float("inf") for s in size):
         raise RuntimeError(f"scanerf: box_size must be positive, got {list(size)}")
@@ -231,11 +242,103 @@ def extract_scene_mesh(feature_tables, resolutions, blobs, corners, sizes, occup
         raise RuntimeError(f"scanerf: level={level} must be > 0")
     device = feature_tables.device
     if route == "dense":
-        values = _scene_field_dense(feature_tables, resolutions, blobs, corners, sizes, occupied_grid, grid_starts, log2dim, corner, size, n)
+        values = _scene_field_dense(*tiles, corner, size, n)
         step = [_f32_div(size[k], n[k]) for k in range(3)]
-        return surface_nets(torch.from_numpy(values).to(device).contiguous(), level, list(corner), step)
-    head = (tabs, *ptrs, T, nb, corner, size, *n, float(level))
-    return _fused(device, n, "isosurface_count_tiles", "isosurface_emit_tiles", head)
+        mesh = surface_nets(torch.from_numpy(values).to(device).contiguous(), level, list(corner), step)
+    else:
+        mesh = _fused(device, n, "isosurface_count_tiles", "isosurface_emit_tiles", (*head, T, nb, corner, size, *n, float(level)))
+    if normals:
+        mesh = mesh._replace(normals=scene_sigma_normals_points(mesh.vertices, *tiles, route=route)[2])
+    return mesh
+
+
+# ---- the blended density's gradient at world points (csrc/scene_normals.hip) -----------------------------------------
+def _scene_normals_dense(points, feature_tables, resolutions, blobs, corners, sizes, occupied_grid, grid_starts, log2dim):
+    """The witness of the fused op: the definition of include/scanerf_hip.h (scanerf_scene_sigma_normals_points) op by op.  Position,
+    membership, weight, weight gradient, cell and occupancy in numpy float32 on the host, (sigma_b, grad sigma_b) from
+    render.sigma_normals_points at the contributing points of each tile, the sums in numpy float32 in the definition's order.
+    -> (sigma [N], grad [N,3], normal [N,3]) numpy f32."""
+    f32 = np.float32
+    device = feature_tables.device
+    host = lambda t, dt: np.ascontiguousarray(t.detach().cpu().numpy()).astype(dt)
+    p = host(points, f32)
+    cn, sz, occ = host(corners, f32), host(sizes, f32), host(occupied_grid, bool).reshape(-1)
+    starts, l2d = host(grid_starts, np.int64), host(log2dim, np.int64)
+    N = p.shape[0]
+    W, num = np.zeros(N, f32), np.zeros(N, f32)
+    A, B, C = np.zeros((N, 3), f32), np.zeros((N, 3), f32), np.zeros((N, 3), f32)
+    contributed = np.zeros(N, bool)
+    ones = torch.ones(32, dtype=_f32, device=device)
+    half, zero = f32(0.5), f32(0)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for b in range(cn.shape[0]):
+            pt = ((p - cn[b]) / sz[b]).astype(f32)
+            listed = ((pt >= 0) & (pt <= 1)).all(1)
+            if not listed.any():
+                continue
+            dis = ((half - np.abs(pt - half)) * sz[b]).astype(f32)
+            dx, dz = dis[:, 0], dis[:, 2]
+            side = np.where(pt < half, f32(1), np.where(pt > half, f32(-1), zero)).astype(f32)
+            both, only_x, only_z = (dx != 0) & (dz != 0), (dx != 0) & ~(dz != 0), ~(dx != 0) & (dz != 0)
+            w = np.where(both, dx * dz, np.where(only_x, dx, np.where(only_z, dz, zero))).astype(f32)             # xz_weight
+            gw = np.zeros((N, 3), f32)
+            gw[:, 0] = np.where(both, side[:, 0] * dz, np.where(only_x, side[:, 0], zero))
+            gw[:, 2] = np.where(both, side[:, 2] * dx, np.where(only_z, side[:, 2], zero))
+            W = np.where(listed, W + w, W).astype(f32)
+            C = np.where(listed[:, None], C + gw, C).astype(f32)
+            r = (1 << l2d[b]).astype(np.int64)
+            cc = (pt * r.astype(f32)).astype(f32)
+            loc = np.clip(np.where(np.isfinite(cc), cc, 0).astype(np.int64), 0, r - 1)                              # C (int), then the clamp
+            off = (loc[:, 0] << int(l2d[b, 1] + l2d[b, 2])) | (loc[:, 1] << int(l2d[b, 2])) | loc[:, 2]
+            run = listed & occ[starts[b] + off]
+            if not run.any():
+                continue
+            x = (f32(2.0) * pt[run] - f32(1.0)).astype(f32)
+            sigma, grad, _ = render.sigma_normals_points(torch.from_numpy(np.ascontiguousarray(x)).to(device), feature_tables[b],
+                                                         resolutions[b], blobs[b], ones,
+                                                         axis_scale=[_f32_div(2.0, sz[b, k]) for k in range(3)], want_grad=True)
+            sigma, grad = sigma.cpu().numpy(), grad.cpu().numpy()
+            num[run] = num[run] + (w[run] * sigma).astype(f32)
+            A[run] = A[run] + (w[run, None] * grad).astype(f32)
+            B[run] = B[run] + (sigma[:, None] * gw[run]).astype(f32)
+            contributed |= run
+        inv = np.where(W > 0, f32(1.0) / np.where(W > 0, W, f32(1.0)), f32(1.0)).astype(f32)
+        v = (num * inv).astype(f32)
+        g = (((A + B) - v[:, None] * C) * inv[:, None]).astype(f32)
+        q = g * g
+        nrm = (g * (f32(-1.0) / (np.sqrt((q[:, 0] + q[:, 1]) + q[:, 2]) + f32(1e-8)))[:, None]).astype(f32)
+    keep = contributed
+    return (np.where(keep, v, zero).astype(f32), np.where(keep[:, None], g, zero).astype(f32),
+            np.where(keep[:, None], nrm, zero).astype(f32))
+
+
+def scene_sigma_normals_points(points, feature_tables, resolutions, blobs, corners, sizes, occupied_grid, grid_starts, log2dim,
+                               want_grad=False, route="fused"):
+    """The blended density of a tiled scene, its gradient and the normal at world points [N,3] f32 (any order; the definition:
+    include/scanerf_hip.h, scanerf_scene_sigma_normals_points): the field extract_scene_mesh cuts, v = sum_b w_b sigma_b / W, and the
+    gradient of exactly that function, the blend weights' gradients included.  The tile arrays are extract_scene_mesh's.
+    -> (sigma [N], grad [N,3] or None, normal [N,3] = -grad / (|grad| + 1e-8)); zeros where no tile contributes.  route="fused": one
+    launch, no per-tile index arrays; route="dense": host geometry -> render.sigma_normals_points per tile -> the sums (the witness)."""
+    if route not in ROUTES:
+        raise RuntimeError(f"scanerf: route must be one of {ROUTES}, got {route!r}")
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError("scanerf: points must be a [N,3] tensor")
+    tiles = (feature_tables, resolutions, blobs, corners, sizes, occupied_grid, grid_starts, log2dim)
+    head, T, nb = _scene_tile_args(*tiles)
+    p = dev_ptr(points, _f32, "points")
+    device, N = points.device, int(points.shape[0])
+    if N == 0:   # (an empty tensor has no address to hand over)
+        empty = torch.empty((0, 3), dtype=_f32, device=device)
+        return torch.empty((0,), dtype=_f32, device=device), (empty.clone() if want_grad else None), empty
+    if route == "dense":
+        sigma, grad, normal = (torch.from_numpy(a).to(device) for a in _scene_normals_dense(points, *tiles))
+        return sigma, (grad if want_grad else None), normal
+    sigma = torch.empty((N,), dtype=_f32, device=device)
+    normal = torch.empty((N, 3), dtype=_f32, device=device)
+    grad = torch.empty((N, 3), dtype=_f32, device=device) if want_grad else None
+    check(lib().scanerf_scene_sigma_normals_points(p, *head, T, nb, sigma.data_ptr(), grad.data_ptr() if want_grad else None,
+                                                   normal.data_ptr(), N, stream()), "scene_sigma_normals_points")
+    return sigma, grad, normal
 
 
 def cells_per_axis(occ_size, longest):
