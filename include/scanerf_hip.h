@@ -786,6 +786,55 @@ int scanerf_scene_sigma_normals_points(const float *points, const void *tables_f
                                        const float *sizes, int T, int nb, float *sigma, float *grad, float *normal, int N,
                                        scanerf_stream_t stream);
 
+/* ---- connected components of a mesh and the filter by component (csrc/mesh_components.hip).  The reference has no
+ *   counterpart; the definition is this comment.  Every quantity is an integer: every result is exact and reproducible bit for bit.
+ *   Inputs: V vertices, faces [F,3] i32 with every index in [0, V) (the caller's duty; the Python layer checks it; a face that breaks it
+ *     is never dereferenced: it joins nothing, counts for nothing and is not kept), optionally cells [V,3] i32 (Mesh.cells).
+ *   Graph: the vertices are the nodes, a face joins its three vertices.  Degenerate faces (two equal indices) and duplicate faces are
+ *     legal and join what they name.
+ *   Label: labels[v] = the smallest vertex index of v's connected component.  It depends on the graph alone -- not on the order of the
+ *     faces or of a face's corners, the launch geometry or timing.  A vertex that no face uses is its own component.
+ *   Table, one row per component, the rows in ascending label order as this library writes them: label; n_vertices; n_faces, a face
+ *     belonging to the component of its FIRST index; with cells, cell_min [3] / cell_max [3] over the component's vertices, and
+ *     extent = max over the axes of (cell_max - cell_min + 1).  Without cells extent counts as 0.
+ *     RANK: the row number after ordering the rows by n_faces descending, ties by label ascending (meshing.mesh_components returns the
+ *     table in that order; the sort is the caller's, one key per row).
+ *   Keep rule, the three conditions joined: a component is kept iff n_faces >= min_faces and extent >= min_extent and (keep_largest
+ *     is None or rank < keep_largest).  Defaults 0, 0, None: everything is kept and the result is the input bit for bit.  min_faces = 1
+ *     alone removes exactly the vertices no face uses.  min_extent > 0 without cells is refused.  The caller forms keep [C] u8 (by
+ *     row, in the library's ascending-label row order) from the table.
+ *   Filtered mesh: the kept vertices in their original relative order; the kept faces (a face is kept with the component of its first
+ *     index, which is the component of all three) in their original relative order with their indices remapped; the per-vertex arrays
+ *     gathered row for row; winding untouched.
+ *   Calls, all on caller-owned memory and the caller's stream:
+ *     scanerf_mesh_components_scratch_bytes(V, F): the scratch (16-byte aligned) all four calls below share: a 64-byte header, two
+ *       [V] i32 arrays (the row of every root; the new index of every vertex) and one i32 per 256 vertices and per 256 faces.
+ *       0 with scanerf_last_error set for sizes that are refused: V < 1, F < 0, V or 3 F within 256 of 2^31.
+ *     scanerf_mesh_components_label: labels [V] i32 (every element written), and in the scratch the roots counted and numbered in
+ *       ascending order; the header's first int64 is then C, the number of components: the caller reads it and allocates the table.
+ *     scanerf_mesh_components_table: the C rows (label, n_vertices, n_faces [C] i32; cell_min, cell_max [C,3] i32, with cells: all
+ *       three or none), exactly C rows written, with `labels` and the scratch as scanerf_mesh_components_label left them.  The sums
+ *       are integer atomics aggregated per wave and per workgroup first: order-independent.
+ *     scanerf_mesh_filter_count: keep [C] u8 -> the header's second and third int64 are V' and F', the kept vertices and faces; the
+ *       caller reads them and allocates.
+ *     scanerf_mesh_filter_emit: gathers vertices / cells / lattice / normals [V,3] (each may be NULL with its output: skipped) into
+ *       out_* [V',3] and writes out_faces [F',3]; exactly V' and F' rows.  The call reads (V', F') back from the header (one 16-byte
+ *       read that waits for the stream) and REFUSES, writing nothing, when Vout != V' or Fout != F'.
+ *   Refused before any launch: null pointers, sizes scanerf_mesh_components_scratch_bytes refuses, a scratch that is missing, too
+ *     small or not 16-byte aligned, C outside [1, V], negative Vout / Fout.  V == 0 has no call (meshing returns empty results). */
+size_t scanerf_mesh_components_scratch_bytes(int V, int F);
+int scanerf_mesh_components_label(const int32_t *faces, int V, int F, int32_t *labels, void *scratch, size_t scratch_bytes,
+                                  scanerf_stream_t stream);
+int scanerf_mesh_components_table(const int32_t *faces, const int32_t *cells, const int32_t *labels, int V, int F, const void *scratch,
+                                  size_t scratch_bytes, int C, int32_t *label, int32_t *n_vertices, int32_t *n_faces, int32_t *cell_min,
+                                  int32_t *cell_max, scanerf_stream_t stream);
+int scanerf_mesh_filter_count(const int32_t *faces, const int32_t *labels, const uint8_t *keep, int V, int F, int C, void *scratch,
+                              size_t scratch_bytes, scanerf_stream_t stream);
+int scanerf_mesh_filter_emit(const int32_t *faces, const int32_t *labels, const uint8_t *keep, int V, int F, int C, void *scratch,
+                             size_t scratch_bytes, const float *vertices, const int32_t *cells, const float *lattice,
+                             const float *normals, float *out_vertices, int32_t *out_faces, int32_t *out_cells, float *out_lattice,
+                             float *out_normals, int Vout, int Fout, scanerf_stream_t stream);
+
 #define SCANERF_RAY_OUT 16
 
 #ifdef __cplusplus

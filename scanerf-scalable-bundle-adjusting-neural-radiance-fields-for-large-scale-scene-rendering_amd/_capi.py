@@ -117,6 +117,11 @@ PROTOTYPES = {
     "scanerf_isosurface_count_tiles": ("I", "PPPPPPPPIIPPIIIFPZP", REQ),
     "scanerf_isosurface_emit_tiles": ("I", "PPPPPPPPIIPPIIIFPZPPPPIIP", REQ),
     "scanerf_scene_sigma_normals_points": ("I", "PPPPPPPPPIIPPPIP", REQ),
+    "scanerf_mesh_components_scratch_bytes": ("Z", "II", REQ),
+    "scanerf_mesh_components_label": ("I", "PIIPPZP", REQ),
+    "scanerf_mesh_components_table": ("I", "PPPIIPZIPPPPPP", REQ),
+    "scanerf_mesh_filter_count": ("I", "PPPIIIPZP", REQ),
+    "scanerf_mesh_filter_emit": ("I", "PPPIIIPZPPPPPPPPPIIP", REQ),
 }
 SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if required]
 OPTIONAL_SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if not required]

@@ -9,6 +9,10 @@ lattice.  The reference has no mesh extraction; the definition is the comment of
                                                         the multi-tile renderer's weights on a lattice over a world box
     scene_sigma_normals_points(points, tables, ...)     that blended density, its gradient (weight terms included) and the normal at
                                                         world points: the scene mesh's vertex normals
+    mesh_components(faces, n_vertices, cells)           connected components: labels and the per-component table (csrc/mesh_components.hip;
+                                                        DESIGN.md 4.17)
+    filter_mesh(mesh, min_faces, min_extent, keep_largest)   drop floaters and unused vertices by component; the extractors take the
+                                                        same three rules and filter before they evaluate normals
 
 All return a Mesh: vertices [V,3] f32 (world), faces [F,3] i32 (counter-clockwise seen from the outside), cells [V,3] i32 (the owning
 cell of each vertex), lattice [V,3] f32 (the vertices in lattice coordinates) and, on request, normals [V,3] f32.  Two launches with
@@ -115,13 +119,16 @@ def _contracted(lattice, n):
 
 
 def extract_mesh(features, resolutions, blob, weight_feature, occupied_grid, log2dim, occ_corner, occ_size, n, level, normals=False,
-                 route="fused"):
+                 route="fused", min_faces=0, min_extent=0, keep_largest=None, report=None):
     """The level set sigma == level of a tile's density as a triangle mesh.  features [16,T,2] f32 / f16, resolutions [16,3], blob (the
     flat decoder blob), weight_feature [32], occupied_grid bool [2^log2dim], occ_corner / occ_size: the tile box (3 floats each),
     n: cells per axis of the lattice over it.  normals=True adds render.sigma_normals_points' normals at the vertices
-    (axis_scale = 4 / (2 occ_size))."""
+    (axis_scale = 4 / (2 occ_size)).  min_faces / min_extent / keep_largest: filter_mesh's keep rule, applied BEFORE the normals are
+    evaluated (they are computed at the kept vertices only); the defaults keep everything.  report: a dict that receives the
+    component count and the rows before and after the filter."""
     if route not in ROUTES:
         raise RuntimeError(f"scanerf: route must be one of {ROUTES}, got {route!r}")
+    _rules(min_faces, min_extent, keep_largest, True)
     n = _lattice_size(n)
     T, mid = render._normals_common(features, resolutions, blob, weight_feature)
     occ = dev_ptr(occupied_grid, (torch.bool, torch.uint8), "occupied_grid")
@@ -143,6 +150,7 @@ def extract_mesh(features, resolutions, blob, weight_feature, occupied_grid, log
         l2d = (ctypes.c_int32 * 3)(*log2dim)
         head = (*mid, T, occ, l2d, int(occupied_grid.numel()), *n, float(level))
         mesh = _fused(device, n, "isosurface_count", "isosurface_emit", head, (corner, size))
+    mesh = _filter(mesh, min_faces, min_extent, keep_largest, _COMPONENT_ROUTE[route], False, report)
     if normals:
         if mesh.vertices.shape[0]:
             _, _, nrm = render.sigma_normals_points(_contracted(mesh.lattice, n), features, resolutions, blob, weight_feature,
@@ -222,16 +230,19 @@ def _scene_tile_args(feature_tables, resolutions, blobs, corners, sizes, occupie
 
 
 def extract_scene_mesh(feature_tables, resolutions, blobs, corners, sizes, occupied_grid, grid_starts, log2dim, box_corner, box_size, n,
-                       level, route="fused", normals=False):
+                       level, route="fused", normals=False, min_faces=0, min_extent=0, keep_largest=None, report=None):
     """One mesh of a tiled scene: the level set of the field the multi-tile renderer draws -- the tiles' densities blended per lattice
     point with the renderer's xz-distance weights -- on a lattice of n cells over the world box box_corner / box_size (the definition:
     include/scanerf_hip.h, scanerf_isosurface_count_tiles).  The tile arrays are TileSetRenderer's: feature_tables [nb,16,T,2] f16,
     resolutions [nb,16,3] i32, blobs [nb,13994], corners / sizes [nb,3] (render boxes), occupied_grid (the tiles' own grids,
     concatenated), grid_starts [nb] i64, log2dim [nb,3] i32.  -> Mesh; normals=True adds scene_sigma_normals_points' normals at the
     vertices (the gradient of the blended field itself), otherwise normals is None.  route="fused" never stores the
-    lattice; route="dense" composes host geometry -> render.sigma_normals_points per tile -> blend -> surface_nets (the witness)."""
+    lattice; route="dense" composes host geometry -> render.sigma_normals_points per tile -> blend -> surface_nets (the witness).
+    min_faces / min_extent / keep_largest: filter_mesh's keep rule, applied BEFORE the normals are evaluated; the
+    defaults keep everything.  report: a dict that receives the component count and the rows before and after the filter."""
     if route not in ROUTES:
         raise RuntimeError(f"scanerf: route must be one of {ROUTES}, got {route!r}")
+    _rules(min_faces, min_extent, keep_largest, True)
     n = _lattice_size(n)
     tiles = (feature_tables, resolutions, blobs, corners, sizes, occupied_grid, grid_starts, log2dim)
     head, T, nb = _scene_tile_args(*tiles)
@@ -247,6 +258,7 @@ def extract_scene_mesh(feature_tables, resolutions, blobs, corners, sizes, occup
         mesh = surface_nets(torch.from_numpy(values).to(device).contiguous(), level, list(corner), step)
     else:
         mesh = _fused(device, n, "isosurface_count_tiles", "isosurface_emit_tiles", (*head, T, nb, corner, size, *n, float(level)))
+    mesh = _filter(mesh, min_faces, min_extent, keep_largest, _COMPONENT_ROUTE[route], False, report)
     if normals:
         mesh = mesh._replace(normals=scene_sigma_normals_points(mesh.vertices, *tiles, route=route)[2])
     return mesh
@@ -339,6 +351,216 @@ def scene_sigma_normals_points(points, feature_tables, resolutions, blobs, corne
     check(lib().scanerf_scene_sigma_normals_points(p, *head, T, nb, sigma.data_ptr(), grad.data_ptr() if want_grad else None,
                                                    normal.data_ptr(), N, stream()), "scene_sigma_normals_points")
     return sigma, grad, normal
+
+
+# ---- connected components and the filter by component (csrc/mesh_components.hip) -----------------------------------
+Components = collections.namedtuple("Components", "labels label n_vertices n_faces cell_min cell_max")
+COMPONENT_ROUTES = ("fused", "composed")
+_COMPONENT_ROUTE = {"fused": "fused", "dense": "composed"}      # the extractors' witness route composes the filter too
+_i32 = torch.int32
+
+
+def _rules(min_faces, min_extent, keep_largest, have_cells):
+    """The keep rule's values, checked -> (min_faces, min_extent, keep_largest or None, any rule active?)."""
+    for name, v in (("min_faces", min_faces), ("min_extent", min_extent), ("keep_largest", keep_largest)):
+        if v is None and name == "keep_largest":
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise RuntimeError(f"scanerf: {name} must be a non-negative integer, got {v!r}")
+    if min_extent > 0 and not have_cells:
+        raise RuntimeError("scanerf: min_extent needs the vertices' cells (Mesh.cells); there are none")
+    active = min_faces > 0 or min_extent > 0 or keep_largest is not None
+    return int(min_faces), int(min_extent), None if keep_largest is None else int(keep_largest), active
+
+
+def _component_args(faces, n_vertices, cells, route, check_range):
+    """The checks every component op makes before any launch -> (V, F).  check_range: the public functions' one device reduction
+    with one host read for the face indices; the extractors' own outputs skip it."""
+    if route not in COMPONENT_ROUTES:
+        raise RuntimeError(f"scanerf: route must be one of {COMPONENT_ROUTES}, got {route!r}")
+    if isinstance(n_vertices, bool) or not isinstance(n_vertices, (int, np.integer)) or not 0 <= n_vertices < 2 ** 31 // 3:
+        raise RuntimeError(f"scanerf: n_vertices must be an integer in [0, 2^31 / 3), got {n_vertices!r}")
+    V = int(n_vertices)
+    dev_ptr(faces, _i32, "faces")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError(f"scanerf: faces must be [F,3], got {tuple(faces.shape)}")
+    F = int(faces.shape[0])
+    if F >= 2 ** 31 // 3:
+        raise RuntimeError(f"scanerf: F={F} faces are too many for int32 indices")
+    if cells is not None:
+        dev_ptr(cells, _i32, "cells")
+        if tuple(cells.shape) != (V, 3) or cells.device != faces.device:
+            raise RuntimeError(f"scanerf: cells must be [{V},3] on {faces.device}, got {tuple(cells.shape)} on {cells.device}")
+    if F and V == 0:
+        raise RuntimeError(f"scanerf: {F} faces with no vertices")
+    if check_range and F:
+        lo, hi = torch.stack(torch.aminmax(faces)).tolist()
+        if lo < 0 or hi >= V:
+            raise RuntimeError(f"scanerf: face indices run from {lo} to {hi}, outside [0, {V})")
+    return V, F
+
+
+def _labels_composed(faces, V):
+    """The witness: rounds of scatter_reduce(amin) over the edges (both directions) plus labels = labels[labels], to a fixed point
+    (one host read per round).  An edge (s, d) lowers the label of d's LABEL to s's label (hooking the tree, not the vertex: a chain
+    takes a few dozen rounds, not its length); the jump carries it to the vertices.  A label only decreases, names a vertex of its
+    own component and is <= every vertex that carries it.  At the fixed point lab[lab] == lab and lab[lab[d]] <= lab[s] for both
+    directions of every edge, so a label is constant over every edge: it is the component's smallest index.  -> labels [V] int64."""
+    lab = torch.arange(V, dtype=torch.int64, device=faces.device)
+    if faces.shape[0] == 0:
+        return lab
+    f = faces.to(torch.int64)
+    src, dst = f[:, [0, 1, 0, 2, 1, 2]].reshape(-1), f[:, [1, 0, 2, 0, 2, 1]].reshape(-1)
+    while True:
+        new = lab.scatter_reduce(0, lab[dst], lab[src], "amin", include_self=True)
+        new = new[new]
+        if torch.equal(new, lab):
+            return lab
+        lab = new
+
+
+def _table_composed(faces, cells, lab):
+    """The table by bincount / scatter_reduce, rows in ascending label order -> (label, n_vertices, n_faces, cell_min, cell_max)."""
+    V = lab.shape[0]
+    roots = torch.nonzero(lab == torch.arange(V, dtype=torch.int64, device=lab.device)).reshape(-1)
+    nv = torch.bincount(lab, minlength=V)[roots]
+    nf = torch.bincount(lab[faces[:, 0].to(torch.int64)], minlength=V)[roots] if faces.shape[0] else torch.zeros_like(nv)
+    cmin = cmax = None
+    if cells is not None:
+        idx = lab[:, None].expand(V, 3)
+        big = torch.iinfo(torch.int32)
+        cmin = torch.full((V, 3), big.max, dtype=_i32, device=lab.device).scatter_reduce(0, idx, cells, "amin")[roots]
+        cmax = torch.full((V, 3), big.min, dtype=_i32, device=lab.device).scatter_reduce(0, idx, cells, "amax")[roots]
+    return roots.to(_i32), nv.to(_i32), nf.to(_i32), cmin, cmax
+
+
+def _components_scratch(device, V, F):
+    nbytes = int(lib().scanerf_mesh_components_scratch_bytes(V, F))
+    if nbytes == 0:
+        raise RuntimeError(f"scanerf: a mesh of V={V} vertices and F={F} faces is not supported: "
+                           + lib().scanerf_last_error().decode("utf-8", "replace"))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+
+def _components(faces, V, F, cells, route):
+    """-> (Components with the table in rank order, order [C] i64: the library's row (ascending label) of every rank, state: the
+    fused route's (scratch, nbytes) for the filter or None).  V >= 1."""
+    device = faces.device
+    if route == "composed":
+        lab = _labels_composed(faces, V)
+        rows, state = _table_composed(faces, cells, lab), None
+        labels = lab.to(_i32)
+    else:
+        scratch, nbytes = _components_scratch(device, V, F)
+        labels = torch.empty((V,), dtype=_i32, device=device)
+        check(lib().scanerf_mesh_components_label(faces.data_ptr(), V, F, labels.data_ptr(), scratch.data_ptr(), nbytes, stream()),
+              "mesh_components_label")
+        C = int(scratch[:8].view(torch.int64).item())      # the one host read: the number of components
+        new = lambda *shape: torch.empty(shape, dtype=_i32, device=device)
+        rows = (new(C), new(C), new(C), new(C, 3) if cells is not None else None, new(C, 3) if cells is not None else None)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        check(lib().scanerf_mesh_components_table(faces.data_ptr(), ptr(cells), labels.data_ptr(), V, F, scratch.data_ptr(), nbytes, C,
+                                                  *(ptr(t) for t in rows), stream()), "mesh_components_table")
+        state = (scratch, nbytes)
+    label, nf = rows[0], rows[2]
+    # rank: n_faces descending, ties by label ascending -- one int64 key per row (labels are distinct: no two keys are equal)
+    order = torch.argsort(((2 ** 31 - 1 - nf.to(torch.int64)) << 32) | label.to(torch.int64))
+    return Components(labels, *(None if t is None else t[order].contiguous() for t in rows)), order, state
+
+
+def _empty_components(device, with_cells):
+    e = lambda *shape: torch.empty(shape, dtype=_i32, device=device)
+    return Components(e(0), e(0), e(0), e(0), e(0, 3) if with_cells else None, e(0, 3) if with_cells else None)
+
+
+def mesh_components(faces, n_vertices, cells=None, route="fused"):
+    """The connected components of a mesh (the definition: include/scanerf_hip.h, scanerf_mesh_components_label): faces [F,3] i32
+    over n_vertices vertices, optionally their cells [V,3] i32 (Mesh.cells).  -> Components(labels [V] i32: the smallest vertex index
+    of each vertex's component; label, n_vertices, n_faces [C] i32 and, with cells, cell_min, cell_max [C,3] i32: one row per
+    component, ordered by n_faces descending, ties by label ascending -- the row number is the component's rank).  route="fused":
+    a lock-free union-find and aggregated integer sums on the GPU, one host read (C); route="composed": torch label propagation,
+    bincount and scatter_reduce (the witness; a host read per round).  Both give the same bits."""
+    V, F = _component_args(faces, n_vertices, cells, route, True)
+    if V == 0:
+        return _empty_components(faces.device, cells is not None)
+    return _components(faces, V, F, cells, route)[0]
+
+
+def _keep_ranked(comps, min_faces, min_extent, keep_largest):
+    """The keep rule on the table in rank order -> [C] bool."""
+    keep = comps.n_faces >= min_faces
+    if min_extent > 0:
+        keep &= (comps.cell_max - comps.cell_min + 1).max(1).values >= min_extent
+    if keep_largest is not None:
+        keep &= torch.arange(keep.shape[0], device=keep.device) < keep_largest
+    return keep
+
+
+def _filter(mesh, min_faces, min_extent, keep_largest, route, check_range, report=None):
+    """filter_mesh behind its checks of the rule.  report: a dict that receives the component count and the rows before and after."""
+    arrays = {"vertices": (mesh.vertices, _f32), "cells": (mesh.cells, _i32), "lattice": (mesh.lattice, _f32), "normals": (mesh.normals, _f32)}
+    if not isinstance(mesh.vertices, torch.Tensor) or mesh.vertices.dim() != 2 or mesh.vertices.shape[1] != 3:
+        raise RuntimeError("scanerf: mesh.vertices must be a [V,3] tensor")
+    Vn = int(mesh.vertices.shape[0])
+    for name, (t, dt) in arrays.items():
+        if t is None and name != "vertices":
+            continue
+        dev_ptr(t, dt, name)
+        if tuple(t.shape) != (Vn, 3) or t.device != mesh.vertices.device:
+            raise RuntimeError(f"scanerf: mesh.{name} must be [{Vn},3] on {mesh.vertices.device}, got {tuple(t.shape)} on {t.device}")
+    min_faces, min_extent, keep_largest, active = _rules(min_faces, min_extent, keep_largest, mesh.cells is not None)
+    V, F = _component_args(mesh.faces, Vn, mesh.cells, route, check_range and (active or report is not None))
+    if mesh.faces.device != mesh.vertices.device:
+        raise RuntimeError(f"scanerf: mesh.faces lives on {mesh.faces.device}, the vertices on {mesh.vertices.device}")
+    if report is not None:
+        report.update(components=0, kept_components=0, vertices=(V, V), faces=(F, F))
+    if V == 0 or not (active or report is not None):
+        return mesh
+    comps, order, state = _components(mesh.faces, V, F, mesh.cells, route)
+    C = int(comps.label.shape[0])
+    if report is not None:
+        report.update(components=C, kept_components=C)
+    if not active:
+        return mesh            # the default rule keeps everything: the input, bit for bit
+    device = mesh.vertices.device
+    ranked = _keep_ranked(comps, min_faces, min_extent, keep_largest)
+    present = [(k, t) for k, (t, _) in arrays.items() if t is not None]
+    if route == "composed":
+        kept = torch.zeros(V, dtype=torch.bool, device=device)
+        kept[comps.label[ranked].to(torch.int64)] = True
+        kv = kept[comps.labels.to(torch.int64)]
+        kf = kv[mesh.faces[:, 0].to(torch.int64)] if F else torch.zeros(0, dtype=torch.bool, device=device)
+        new_index = torch.cumsum(kv, 0) - 1
+        out = {k: t[kv].contiguous() for k, t in present}
+        out["faces"] = new_index[mesh.faces[kf].to(torch.int64)].to(_i32).reshape(-1, 3).contiguous()
+    else:
+        scratch, nbytes = state
+        keep = torch.empty(C, dtype=torch.uint8, device=device)
+        keep[order] = ranked.to(torch.uint8)       # the library's row order: ascending label
+        head = (mesh.faces.data_ptr(), comps.labels.data_ptr(), keep.data_ptr(), V, F, C, scratch.data_ptr(), nbytes)
+        check(lib().scanerf_mesh_filter_count(*head, stream()), "mesh_filter_count")
+        Vk, Fk = (int(v) for v in scratch[8:24].view(torch.int64).tolist())      # the one host read: (V', F')
+        out = {k: torch.empty((Vk, 3), dtype=t.dtype, device=device) for k, t in present}
+        out["faces"] = torch.empty((Fk, 3), dtype=_i32, device=device)
+        if Vk:
+            src = {k: None for k in arrays}
+            src.update({k: t.data_ptr() for k, t in present})
+            dst = {k: (out[k].data_ptr() if k in out else None) for k in arrays}
+            check(lib().scanerf_mesh_filter_emit(*head, src["vertices"], src["cells"], src["lattice"], src["normals"], dst["vertices"],
+                                                 out["faces"].data_ptr() if Fk else None, dst["cells"], dst["lattice"], dst["normals"],
+                                                 Vk, Fk, stream()), "mesh_filter_emit")
+    if report is not None:
+        report.update(kept_components=int(ranked.sum()), vertices=(V, int(out["vertices"].shape[0])), faces=(F, int(out["faces"].shape[0])))
+    return Mesh(out["vertices"], out["faces"], out.get("cells"), out.get("lattice"), out.get("normals"))
+
+
+def filter_mesh(mesh, min_faces=0, min_extent=0, keep_largest=None, route="fused"):
+    """Drop components of a Mesh (floaters, unused vertices) by the keep rule of include/scanerf_hip.h: a component stays iff
+    n_faces >= min_faces and extent >= min_extent (extent: the largest side of its box of cells, in cells) and (keep_largest is None
+    or rank < keep_largest), the rank by n_faces descending, ties by label ascending.  The defaults keep everything and return the
+    input.  min_faces=1 alone removes exactly the vertices no face uses.  Kept vertices and faces stay in their order, the faces'
+    indices are remapped, cells / lattice / normals (where the mesh has them) are gathered row for row.  -> Mesh."""
+    return _filter(mesh, min_faces, min_extent, keep_largest, route, True)
 
 
 def cells_per_axis(occ_size, longest):

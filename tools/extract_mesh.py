@@ -2,14 +2,15 @@
 """Level-set mesh extraction of exported tiles: one PLY per tile.
 
     python tools/extract_mesh.py TILEDIR [TILEDIR ...] --level SIGMA [--cells-per-axis 256] [--out DIR] [--normals] [--route fused|dense]
-                                 [--gpu 0]
+                                 [--gpu 0] [--min-faces N] [--min-extent CELLS] [--keep-largest K]
 
 TILEDIR holds feature.npz and decoder.pth as renderer.export_tile writes and renderer.load_tile reads them.  The lattice covers the
 tile box (the inner half of the exported 2x box) with --cells-per-axis cells along its longest side and the other sides by the box's
 aspect; the surface is sigma == --level (sigma units, > 0), extracted only where the tile's sampler is occupied, and written with
 formats.write_ply to DIR/<name of TILEDIR>.ply (default: TILEDIR/mesh.ply); --normals stores the tile density's normals at the
-vertices (nx ny nz).  The files read back through formats.read_ply,
-fastmesh.FastMesh and tools/build_tiles.py.
+vertices (nx ny nz).  --min-faces / --min-extent / --keep-largest drop floaters and unused vertices by connected component before
+the normals are evaluated (meshing.filter_mesh); the component count and the rows before and after are printed either
+way.  The files read back through formats.read_ply, fastmesh.FastMesh and tools/build_tiles.py.
 
 Tile meshes abut at the faces of their tile boxes, where each is left open, and overlap in the tiles' margins.  Stitching them into
 one mesh is out of scope here."""
@@ -30,12 +31,16 @@ def parser():
     ap.add_argument("--out", default=None, metavar="DIR", help="write DIR/<tile name>.ply instead of TILEDIR/mesh.ply")
     ap.add_argument("--normals", action="store_true", help="store vertex normals (nx ny nz): the tile density's")
     ap.add_argument("--route", choices=("fused", "dense"), default="fused", help="dense: the composed route (small lattices only)")
+    ap.add_argument("--min-faces", type=int, default=0, help="drop components with fewer faces (1: exactly the unused vertices)")
+    ap.add_argument("--min-extent", type=int, default=0, help="drop components whose box of cells is shorter than this on every axis")
+    ap.add_argument("--keep-largest", type=int, default=None, metavar="K", help="keep only the K components with the most faces")
     ap.add_argument("--gpu", type=int, default=0)
     return ap
 
 
-def extract_tile(tile, cells, level, device, route="fused", normals=False):
-    """tile: renderer.load_tile's dict -> meshing.Mesh (normals=True: with the density's normals at the vertices)."""
+def extract_tile(tile, cells, level, device, route="fused", normals=False, **rules):
+    """tile: renderer.load_tile's dict -> meshing.Mesh (normals=True: with the density's normals at the vertices).  rules:
+    meshing.extract_mesh's min_faces / min_extent / keep_largest / report."""
     import numpy as np
     import torch
 
@@ -46,7 +51,7 @@ def extract_tile(tile, cells, level, device, route="fused", normals=False):
     occ = t(np.asarray(tile["occupied_grid"]).reshape([2 ** k for k in log2dim]), torch.bool)
     return meshing.extract_mesh(t(tile["features"], torch.float16), t(tile["resolution"], torch.int32), t(tile["blob"], torch.float32),
                                 torch.ones(32, dtype=torch.float32, device=device), occ, log2dim, corner.tolist(), size.tolist(),
-                                meshing.cells_per_axis(size.tolist(), cells), level, normals=normals, route=route)
+                                meshing.cells_per_axis(size.tolist(), cells), level, normals=normals, route=route, **rules)
 
 
 def main(argv=None):
@@ -57,12 +62,16 @@ def main(argv=None):
     if args.out:
         os.makedirs(args.out, exist_ok=True)
     for path in args.tiles:
-        mesh = extract_tile(renderer.load_tile(path), args.cells_per_axis, args.level, device, args.route, args.normals)
+        report = {}
+        mesh = extract_tile(renderer.load_tile(path), args.cells_per_axis, args.level, device, args.route, args.normals,
+                            min_faces=args.min_faces, min_extent=args.min_extent, keep_largest=args.keep_largest, report=report)
         name = os.path.basename(os.path.normpath(path))
         out = os.path.join(args.out, name + ".ply") if args.out else os.path.join(path, "mesh.ply")
         formats.write_ply(out, mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy(),
                           normals=mesh.normals.cpu().numpy() if args.normals else None)
         print(f"{out}: {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} faces")
+        print(f"{out}: {report['components']} components, {report['kept_components']} kept; vertices {report['vertices'][0]} -> "
+              f"{report['vertices'][1]}, faces {report['faces'][0]} -> {report['faces'][1]}")
     return 0
 
 
