@@ -835,6 +835,44 @@ int scanerf_mesh_filter_emit(const int32_t *faces, const int32_t *labels, const 
                              const float *normals, float *out_vertices, int32_t *out_faces, int32_t *out_cells, float *out_lattice,
                              float *out_normals, int Vout, int Fout, scanerf_stream_t stream);
 
+/* ---- closest point of a triangle mesh (csrc/mesh_distance.hip): the query behind the geometric evaluation of an
+ *   extracted mesh against a scan.  The reference has no counterpart; the definition is this comment.
+ *   Inputs: points [N,3] f32; the tracer's arrays exactly as scanerf_mesh_first_hit takes them (tris != NULL: pre-gathered triangles,
+ *     else vertices / faces; cell_faces always: it names the faces) plus cell_box; log2dim 4..7; max_dist >= 0 (f32, +inf = no cut).
+ *   Outputs: dist2 [N] f32, face [N] i32, closest [N,3] f32 (may be NULL: not written).
+ *   Per face f = (A, B, C) and point p: q_f(p) = the closest point of the closed triangle, by Voronoi regions in this order -- the vertex
+ *     regions A, B, C, then the edge regions AB, AC, BC, then the interior -- computed in float32 from (A, B - A, C - A), the operands
+ *     `tris` stores, without FMA contraction; d2_f(p) = |p - q_f(p)|^2.  ONE device function computes both for every route below, so
+ *     a (p, f) pair gives the same bits pre-gathered or indexed, through the grid or by brute force.
+ *   A face is DEAD and never answers when n . n == 0 in float32, n = (B - A) x (C - A).  Faces the build does not register (a vertex
+ *     index outside [0, V); a box wholly outside the grid cube, which rounding can do to a face lying in the cube's far side) do not
+ *     answer either.
+ *   dist2[i] = min over the live faces of d2_f; face[i] = the LOWEST face index attaining that float32 minimum (ties are common: shared
+ *     edges and vertices); closest[i] = q of that face.  Where the minimum is > max_dist^2 (float32 product) or not finite, or no live
+ *     face exists, or a coordinate of p is not finite: dist2 = +inf, face = -1, closest = p (for a non-finite p no search runs).
+ *     Coordinates whose squares overflow float32 are outside the definition (the call still ends and writes every element).
+ *   The search is exact: Chebyshev shells of cells around the cell of p (clamped into the grid: points outside the cube are valid),
+ *     candidates compared as (d2, face), stopped by a bound on every face not yet seen, taken with a margin of 2^-18 (grid side + max
+ *     |corner| + max |p|) for the float32 truncation of the build and of d2 itself (the argument: csrc/mesh_distance.hip).  The result does
+ *     not depend on log2dim, the visiting order or the launch geometry.
+ *   N == 0 launches nothing.  Every output element is written exactly once, nothing else is written.  Refused before any launch
+ *     (nothing written): N < 0, log2dim outside 4..7, max_dist negative or NaN, null pointers.  No environment variable is read.
+ *   scanerf_mesh_closest_point_brute: the same outputs from the same device function over every face 0..F-1, no grid (scene_info and
+ *     log2dim only decide which faces the build registers); F == 0 is legal (nothing found).  The witness of the grid route.
+ *   scanerf_mesh_closest_point_counted (measurement; optional): also counters [N,2] i32 = (occupied cells looked at, face tests). */
+int scanerf_mesh_closest_point(const float *points, int N, const float *vertices, const int32_t *faces, const float *tris,
+                               const uint64_t *bitmask, const uint32_t *rank, const int32_t *start_num, const int32_t *cell_faces,
+                               const float *cell_box, const float *scene_info, int log2dim, float max_dist, float *dist2, int32_t *face,
+                               float *closest, scanerf_stream_t stream);
+int scanerf_mesh_closest_point_counted(const float *points, int N, const float *vertices, const int32_t *faces, const float *tris,
+                                       const uint64_t *bitmask, const uint32_t *rank, const int32_t *start_num,
+                                       const int32_t *cell_faces, const float *cell_box, const float *scene_info, int log2dim,
+                                       float max_dist, float *dist2, int32_t *face, float *closest, int32_t *counters,
+                                       scanerf_stream_t stream);
+int scanerf_mesh_closest_point_brute(const float *points, int N, const float *vertices, const int32_t *faces, int V, int F,
+                                     const float *scene_info, int log2dim, float max_dist, float *dist2, int32_t *face, float *closest,
+                                     scanerf_stream_t stream);
+
 #define SCANERF_RAY_OUT 16
 
 #ifdef __cplusplus

@@ -122,6 +122,9 @@ PROTOTYPES = {
     "scanerf_mesh_components_table": ("I", "PPPIIPZIPPPPPP", REQ),
     "scanerf_mesh_filter_count": ("I", "PPPIIIPZP", REQ),
     "scanerf_mesh_filter_emit": ("I", "PPPIIIPZPPPPPPPPPIIP", REQ),
+    "scanerf_mesh_closest_point": ("I", "PIPPPPPPPPPIFPPPP", REQ),
+    "scanerf_mesh_closest_point_counted": ("I", "PIPPPPPPPPPIFPPPPP", OPT),
+    "scanerf_mesh_closest_point_brute": ("I", "PIPPIIPIFPPPP", REQ),
 }
 SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if required]
 OPTIONAL_SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if not required]

@@ -1,0 +1,137 @@
+"""Geometric evaluation of a mesh against another: sample both surfaces, ask for every sample the exact distance to
+the other mesh (FastMesh.closest_point, csrc/mesh_distance.hip -- the hot step), and reduce: accuracy (pred -> gt), completeness
+(gt -> pred), chamfer distance, precision / recall / F-score at distance thresholds.  The reference scores images only
+(postprocess/evaluation.py: PSNR / SSIM, here TileTrainer.validate); it has no geometric score.
+
+sample_surface and the reductions are torch ops: they touch each sample once and are not a hot path (the query is)."""
+import math
+
+import torch
+
+from . import formats
+
+_f32, _f64, _i64 = torch.float32, torch.float64, torch.int64
+
+
+def sample_surface(vertices, faces, n, seed):
+    """n points on the surface, area-weighted and stratified -> (points [n,3] f32, face [n] i64), on the device of `vertices`.
+    Sample i takes u_i = (i + xi_i) / n of the total area and the face whose interval of the float64 area prefix sum holds u_i
+    (cum[f-1] <= u_i < cum[f]: a zero-area face has an empty interval and is never chosen), so every face gets its share of n
+    within one sample either way; inside the face the point is uniform by the square-root map: s = sqrt(r1), barycentrics
+    (1 - s, s (1 - r2), s r2).  (xi, r1, r2) are the columns of ONE torch.rand(n, 3, float64) from a CPU generator seeded with `seed`:
+    the same seed gives the same bits on any device.  Built from torch ops; not a hot path."""
+    v = torch.as_tensor(vertices)
+    f = torch.as_tensor(faces).to(device=v.device, dtype=_i64)
+    n = int(n)
+    if v.dim() != 2 or v.shape[1] != 3 or f.dim() != 2 or f.shape[1] != 3:
+        raise ValueError(f"scanerf: sample_surface needs vertices [V,3] and faces [F,3], got {tuple(v.shape)} and {tuple(f.shape)}")
+    if n < 0:
+        raise ValueError(f"scanerf: sample_surface n={n}")
+    tri = v.to(_f64)[f]                                    # [F,3,3]
+    A, ab, ac = tri[:, 0], tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
+    cum = torch.cumsum(0.5 * torch.linalg.cross(ab, ac).norm(dim=1), 0)
+    total = cum[-1] if cum.numel() else torch.zeros((), dtype=_f64)
+    if not bool(total > 0) or not bool(torch.isfinite(total)):
+        raise ValueError("scanerf: sample_surface: the mesh has no area")
+    r = torch.rand(n, 3, dtype=_f64, generator=torch.Generator(device="cpu").manual_seed(int(seed))).to(v.device)
+    u = (torch.arange(n, dtype=_f64, device=v.device) + r[:, 0]) / max(n, 1) * total
+    u = torch.minimum(u, torch.nextafter(total, torch.zeros_like(total)))   # (a product rounded up to the total itself)
+    idx = torch.searchsorted(cum, u, right=True)
+    s = torch.sqrt(r[:, 1:2])
+    pts = A[idx] + (s * (1.0 - r[:, 2:3])) * ab[idx] + (s * r[:, 2:3]) * ac[idx]
+    return pts.to(_f32).contiguous(), idx
+
+
+def _direction(d, thresholds):
+    """d [n] distances, +inf = not found -> the figures of one direction (float64 reductions on d's device)."""
+    d = d.to(_f64)
+    n = d.numel()
+    found = torch.isfinite(d)
+    df = d[found]
+    k = df.numel()
+    nan = float("nan")
+    return {"n": n, "not_found": float(n - k) / n if n else nan,
+            "mean": float(df.mean()) if k else nan, "median": float(df.median()) if k else nan,
+            "rms": float(df.square().mean().sqrt()) if k else nan,
+            "within": {float(t): (float((d <= float(t)).sum()) / n if n else nan) for t in thresholds}}
+
+
+def summarize(d_pred_to_gt, d_gt_to_pred, thresholds):
+    """The scores from the two distance arrays (+inf = nothing within max_dist).  mean / median (the lower of two middle values) /
+    rms run over the points found; not_found and the threshold shares over ALL points of the direction.  precision[t] = share of
+    pred samples within t of gt, recall[t] = share of gt samples within t of pred, fscore = their harmonic mean (0 when both are 0);
+    chamfer = the mean of the two means."""
+    a, b = _direction(d_pred_to_gt, thresholds), _direction(d_gt_to_pred, thresholds)
+    ts = [float(t) for t in thresholds]
+    pr, rc = {t: a["within"][t] for t in ts}, {t: b["within"][t] for t in ts}
+    fs = {t: (2.0 * pr[t] * rc[t] / (pr[t] + rc[t]) if pr[t] + rc[t] > 0 else 0.0) for t in ts}
+    return {"pred_to_gt": a, "gt_to_pred": b, "precision": pr, "recall": rc, "fscore": fs, "chamfer": 0.5 * (a["mean"] + b["mean"])}
+
+
+def _mesh_arrays(mesh, device):
+    if isinstance(mesh, (str, bytes)) or hasattr(mesh, "__fspath__"):
+        v, f = formats.read_ply(mesh)
+        return torch.from_numpy(v).to(device), torch.from_numpy(f).to(device)
+    v, f = mesh
+    return torch.as_tensor(v).to(device=device, dtype=_f32), torch.as_tensor(f).to(device=device, dtype=torch.int32)
+
+
+@torch.no_grad()
+def compare_meshes(pred, gt, n_samples, thresholds, max_dist=float("inf"), seed=0, log2dim=6, return_distances=False, device=None):
+    """pred, gt: (vertices [V,3], faces [F,3]) or PLY paths.  n_samples points are drawn on each surface (sample_surface; seed for
+    pred, seed + 1 for gt) and queried against the OTHER mesh's FastMesh (log2dim; exact nearest triangle, cut at max_dist).
+    -> summarize()'s dict plus n_samples, thresholds and max_dist (None = no cut); with return_distances=True also "distances":
+    per direction the sample points, their faces, the distances and the nearest faces of the other mesh (tensors on the device)."""
+    from .fastmesh import FastMesh
+    if device is None:
+        dv = [m[0].device for m in (pred, gt) if isinstance(m, (tuple, list)) and isinstance(m[0], torch.Tensor) and m[0].is_cuda]
+        device = dv[0] if dv else torch.device("cuda", torch.cuda.current_device())
+    max_dist = float(max_dist)
+    if not max_dist >= 0.0:
+        raise ValueError(f"scanerf: compare_meshes max_dist must be >= 0 (inf for no cut), got {max_dist}")
+    if int(n_samples) < 1:
+        raise ValueError(f"scanerf: compare_meshes n_samples={n_samples}")
+    thresholds = [float(t) for t in thresholds]
+    (pv, pf), (gv, gf) = _mesh_arrays(pred, device), _mesh_arrays(gt, device)
+    ps, ps_face = sample_surface(pv, pf, n_samples, seed)
+    gs, gs_face = sample_surface(gv, gf, n_samples, seed + 1)
+    d_pg, f_pg, _ = FastMesh.from_arrays(gv, gf, device, log2dim).closest_point(ps, max_dist, want_closest=False)
+    d_gp, f_gp, _ = FastMesh.from_arrays(pv, pf, device, log2dim).closest_point(gs, max_dist, want_closest=False)
+    out = summarize(d_pg, d_gp, thresholds)
+    out.update(n_samples=int(n_samples), thresholds=thresholds, max_dist=None if math.isinf(max_dist) else max_dist)
+    if return_distances:
+        out["distances"] = {"pred_to_gt": {"points": ps, "sample_face": ps_face, "dist": d_pg, "face": f_pg},
+                            "gt_to_pred": {"points": gs, "sample_face": gs_face, "dist": d_gp, "face": f_gp}}
+    return out
+
+
+def json_line(result):
+    """compare_meshes' dict (without the distances) as one JSON line (threshold keys become strings)."""
+    import json
+    return json.dumps({k: v for k, v in result.items() if k != "distances"})
+
+
+def save_distances(path, result):
+    """The "distances" of compare_meshes(return_distances=True) as an .npz: <direction>_<points|sample_face|dist|face>."""
+    import numpy as np
+    np.savez(path, **{f"{d}_{k}": t.cpu().numpy() for d, arrs in result["distances"].items() for k, t in arrs.items()})
+
+
+def add_score_arguments(ap, required):
+    """The arguments tools/compare_meshes.py and the extraction commands' --compare share (argparse)."""
+    ap.add_argument("--samples", type=int, default=None if required else 200000, required=required, metavar="N",
+                    help="points drawn on each surface")
+    ap.add_argument("--threshold", type=float, nargs="+", required=required, default=None, metavar="T",
+                    help="distance thresholds of precision / recall / fscore (world units)")
+    ap.add_argument("--max-dist", type=float, default=float("inf"), metavar="D", help="give up on a point beyond this distance")
+    ap.add_argument("--log2dim", type=int, default=6, help="grid cells per axis of the query structure, as a power of two (4..7)")
+    ap.add_argument("--seed", type=int, default=0)
+
+
+def score_line(pred, gt, args, device, distances=None):
+    """-> json_line(compare_meshes(pred, gt)) under `args` (add_score_arguments); distances: an .npz path for save_distances."""
+    res = compare_meshes(pred, gt, args.samples, args.threshold, max_dist=args.max_dist, seed=args.seed, log2dim=args.log2dim,
+                         return_distances=distances is not None, device=device)
+    if distances is not None:
+        save_distances(distances, res)
+    return json_line(res)

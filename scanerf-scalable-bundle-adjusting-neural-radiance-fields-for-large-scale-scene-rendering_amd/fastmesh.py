@@ -10,6 +10,8 @@ Two deliberate differences from the reference's kernels:
   * rays are clipped to the grid cube first, so origins outside the mesh bounds are traced correctly;
   * first_hit carries its nearest candidate across cells; the reference returns at the first cell with any hit, even one that
     lies beyond that cell, which hides nearer surfaces behind large triangles.
+closest_point (csrc/mesh_distance.hip) has no counterpart in the reference: the exact nearest triangle per query
+point on the same structure, for the geometric evaluation of evaluation.py.
 There is no CPU path: CPU tensors raise.
 """
 import torch
@@ -159,6 +161,41 @@ class FastMesh:
             dev_ptr(self.scene_info, _f32, "scene_info"), self.log2dim, int(self.lds), dev_ptr(out, _f32, "out"), stream()),
               "mesh_first_enter")
         return out
+
+    # ---- closest point (csrc/mesh_distance.hip) ------------------------------------------------------------------
+    @torch.no_grad()
+    def closest_point(self, points, max_dist=float("inf"), route="grid", want_closest=True):
+        """points [N,3] float32 on the GPU -> (dist [N] f32, face [N] i32, closest [N,3] f32 or None): the exact distance to the
+        nearest live triangle, the lowest face index that attains it, and the closest point on that face (include/scanerf_hip.h is
+        the definition).  Where nothing lies within max_dist (or the point is not finite): dist = +inf, face = -1, closest = the
+        point.  route: "grid" (shells of the tracer's grid) or "brute" (every face; the witness, same bits)."""
+        if route not in ("grid", "brute"):
+            raise ValueError(f"scanerf: closest_point route must be 'grid' or 'brute', got {route!r}")
+        max_dist = float(max_dist)
+        if not max_dist >= 0.0:
+            raise ValueError(f"scanerf: closest_point max_dist must be >= 0 (inf for no cut), got {max_dist}")
+        if isinstance(points, torch.Tensor) and (points.dtype != _f32 or points.dim() != 2 or points.shape[1] != 3):
+            raise RuntimeError(f"scanerf: points must be [N,3] float32, got {tuple(points.shape)} {points.dtype}")
+        _require_gpu(points, "points")
+        p = points.detach().contiguous()
+        N = p.shape[0]
+        dist2 = torch.empty(N, dtype=_f32, device=p.device)
+        face = torch.empty(N, dtype=_i32, device=p.device)
+        closest = torch.empty(N, 3, dtype=_f32, device=p.device) if want_closest else None
+        out = (dev_ptr(dist2, _f32, "dist2"), dev_ptr(face, _i32, "face"), dev_ptr(closest, _f32, "closest", allow_none=True))
+        if route == "grid":
+            check(lib().scanerf_mesh_closest_point(
+                dev_ptr(p, _f32, "points"), N, dev_ptr(self.vertices, _f32, "vertices"), dev_ptr(self.faces, _i32, "faces"),
+                dev_ptr(self.tris, _f32, "tris", allow_none=True), dev_ptr(self.bitmask, _i64, "bitmask"),
+                dev_ptr(self.rank, _i32, "rank"), dev_ptr(self.start_num, _i32, "start_num"),
+                dev_ptr(self.cell_faces, _i32, "cell_faces"), dev_ptr(self.cell_box, _f32, "cell_box"),
+                dev_ptr(self.scene_info, _f32, "scene_info"), self.log2dim, max_dist, *out, stream()), "mesh_closest_point")
+        else:
+            check(lib().scanerf_mesh_closest_point_brute(
+                dev_ptr(p, _f32, "points"), N, dev_ptr(self.vertices, _f32, "vertices"), dev_ptr(self.faces, _i32, "faces"),
+                self.vertices.shape[0], self.faces.shape[0], dev_ptr(self.scene_info, _f32, "scene_info"), self.log2dim, max_dist,
+                *out, stream()), "mesh_closest_point_brute")
+        return torch.sqrt(dist2), face, closest
 
     # ---- the reference's methods --------------------------------------------------------------------------------------------
     def _box(self):

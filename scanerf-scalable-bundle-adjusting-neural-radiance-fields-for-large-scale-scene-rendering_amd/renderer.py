@@ -271,3 +271,14 @@ class TileSetRenderer:
                                           self.occupied_grid, self.grid_starts, self.grid_log2dim, corner, size,
                                           meshing.cells_per_axis(size, cells_per_axis), level, route=route, normals=normals,
                                           min_faces=min_faces, min_extent=min_extent, keep_largest=keep_largest, report=report)
+
+    @torch.no_grad()
+    def evaluate_mesh(self, gt, level, cells_per_axis=256, n_samples=200000, thresholds=(0.05,), max_dist=float("inf"), seed=0,
+                      log2dim=6, return_distances=False, **extract):
+        """The geometric score of this scene's mesh against `gt` ((vertices, faces) or a PLY path, e.g. the dataset's scan):
+        extract_mesh(level, cells_per_axis, **extract) -- box, route and the filter rules min_faces / min_extent / keep_largest
+        included -- then evaluation.compare_meshes(extracted, gt, ...).  -> its dict (pred = the extracted mesh)."""
+        from . import evaluation
+        mesh = self.extract_mesh(level, cells_per_axis, **extract)
+        return evaluation.compare_meshes((mesh.vertices, mesh.faces), gt, n_samples, thresholds, max_dist=max_dist, seed=seed,
+                                         log2dim=log2dim, return_distances=return_distances, device=mesh.vertices.device)

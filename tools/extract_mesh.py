@@ -3,6 +3,7 @@
 
     python tools/extract_mesh.py TILEDIR [TILEDIR ...] --level SIGMA [--cells-per-axis 256] [--out DIR] [--normals] [--route fused|dense]
                                  [--gpu 0] [--min-faces N] [--min-extent CELLS] [--keep-largest K]
+                                 [--compare GT.ply --threshold T [T ...] [--samples N] [--max-dist D] [--log2dim L] [--seed S]]
 
 TILEDIR holds feature.npz and decoder.pth as renderer.export_tile writes and renderer.load_tile reads them.  The lattice covers the
 tile box (the inner half of the exported 2x box) with --cells-per-axis cells along its longest side and the other sides by the box's
@@ -10,7 +11,8 @@ aspect; the surface is sigma == --level (sigma units, > 0), extracted only where
 formats.write_ply to DIR/<name of TILEDIR>.ply (default: TILEDIR/mesh.ply); --normals stores the tile density's normals at the
 vertices (nx ny nz).  --min-faces / --min-extent / --keep-largest drop floaters and unused vertices by connected component before
 the normals are evaluated (meshing.filter_mesh); the component count and the rows before and after are printed either
-way.  The files read back through formats.read_ply, fastmesh.FastMesh and tools/build_tiles.py.
+way.  --compare GT.ply prints, after each PLY is written, the geometric score of that tile's mesh against GT.ply as the one JSON line
+of tools/compare_meshes.py.  The files read back through formats.read_ply, fastmesh.FastMesh and tools/build_tiles.py.
 
 Tile meshes abut at the faces of their tile boxes, where each is left open, and overlap in the tiles' margins.  Stitching them into
 one mesh is out of scope here."""
@@ -35,6 +37,11 @@ def parser():
     ap.add_argument("--min-extent", type=int, default=0, help="drop components whose box of cells is shorter than this on every axis")
     ap.add_argument("--keep-largest", type=int, default=None, metavar="K", help="keep only the K components with the most faces")
     ap.add_argument("--gpu", type=int, default=0)
+    ap.add_argument("--compare", default=None, metavar="GT.ply",
+                    help="after writing the PLY, print the geometric score of the mesh against GT.ply as one JSON line (needs --threshold)")
+    import scanerf_amd  # noqa: F401
+    from scanerf_amd import evaluation
+    evaluation.add_score_arguments(ap, required=False)
     return ap
 
 
@@ -55,9 +62,11 @@ def extract_tile(tile, cells, level, device, route="fused", normals=False, **rul
 
 
 def main(argv=None):
-    args = parser().parse_args(argv)
-    import scanerf_amd  # noqa: F401
-    from scanerf_amd import formats, renderer
+    ap = parser()
+    args = ap.parse_args(argv)
+    if args.compare and not args.threshold:
+        ap.error("--compare needs --threshold")
+    from scanerf_amd import evaluation, formats, renderer
     device = f"cuda:{args.gpu}"
     if args.out:
         os.makedirs(args.out, exist_ok=True)
@@ -72,6 +81,8 @@ def main(argv=None):
         print(f"{out}: {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} faces")
         print(f"{out}: {report['components']} components, {report['kept_components']} kept; vertices {report['vertices'][0]} -> "
               f"{report['vertices'][1]}, faces {report['faces'][0]} -> {report['faces'][1]}")
+        if args.compare:
+            print(evaluation.score_line((mesh.vertices, mesh.faces), args.compare, args, mesh.vertices.device))
     return 0
 
 

@@ -4,6 +4,7 @@
     python tools/extract_scene_mesh.py TILEDIR [TILEDIR ...] --level SIGMA [--cells-per-axis 256]
                                        [--box X Y Z SX SY SZ] --out FILE.ply [--normals] [--route fused|dense] [--gpu 0]
                                        [--min-faces N] [--min-extent CELLS] [--keep-largest K]
+                                       [--compare GT.ply --threshold T [T ...] [--samples N] [--max-dist D] [--log2dim L] [--seed S]]
 
 Every TILEDIR holds feature.npz and decoder.pth as renderer.export_tile writes and renderer.load_tile reads them; together they are
 the scene renderer.TileSetRenderer draws.  The field is the one it draws: the tiles' densities blended per point with the render-time
@@ -12,7 +13,8 @@ the faces of the world box.  The lattice covers --box (corner and size in world 
 boxes) with --cells-per-axis cells along its longest side.  --normals stores the vertex normals (nx ny nz): the blended density's own
 gradient, weight terms included.  --min-faces / --min-extent / --keep-largest drop floaters and unused vertices by
 connected component before the normals are evaluated (meshing.filter_mesh); the component count and the rows before
-and after are printed either way.  tools/extract_mesh.py writes one open mesh per tile instead."""
+and after are printed either way.  --compare GT.ply prints, after the PLY is written, the geometric score of the mesh against GT.ply
+(e.g. the dataset's scan) as the one JSON line of tools/compare_meshes.py.  tools/extract_mesh.py writes one open mesh per tile instead."""
 import argparse
 import os
 import sys
@@ -35,13 +37,20 @@ def parser():
     ap.add_argument("--min-extent", type=int, default=0, help="drop components whose box of cells is shorter than this on every axis")
     ap.add_argument("--keep-largest", type=int, default=None, metavar="K", help="keep only the K components with the most faces")
     ap.add_argument("--gpu", type=int, default=0)
+    ap.add_argument("--compare", default=None, metavar="GT.ply",
+                    help="after writing the PLY, print the geometric score of the mesh against GT.ply as one JSON line (needs --threshold)")
+    import scanerf_amd  # noqa: F401
+    from scanerf_amd import evaluation
+    evaluation.add_score_arguments(ap, required=False)
     return ap
 
 
 def main(argv=None):
-    args = parser().parse_args(argv)
-    import scanerf_amd  # noqa: F401
-    from scanerf_amd import formats, renderer
+    ap = parser()
+    args = ap.parse_args(argv)
+    if args.compare and not args.threshold:
+        ap.error("--compare needs --threshold")
+    from scanerf_amd import evaluation, formats, renderer
     rnd = renderer.TileSetRenderer(f"cuda:{args.gpu}", [renderer.load_tile(p) for p in args.tiles])
     box = None if args.box is None else (args.box[:3], args.box[3:])
     report = {}
@@ -54,6 +63,8 @@ def main(argv=None):
     print(f"{args.out}: {len(args.tiles)} tiles, {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} faces")
     print(f"{args.out}: {report['components']} components, {report['kept_components']} kept; vertices {report['vertices'][0]} -> "
           f"{report['vertices'][1]}, faces {report['faces'][0]} -> {report['faces'][1]}")
+    if args.compare:
+        print(evaluation.score_line((mesh.vertices, mesh.faces), args.compare, args, mesh.vertices.device))
     return 0
 
 
