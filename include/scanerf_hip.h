@@ -12,7 +12,12 @@
  *
  * Every function returns 0 on success, non-zero on failure; scanerf_last_error()
  * returns a thread-local message for the last failure.  Launches are asynchronous on
- * `stream` (a hipStream_t passed as void*; NULL = the null stream); no call synchronises.
+ * `stream` (a hipStream_t passed as void*; NULL = the null stream): every launch of a call
+ * goes to that stream and to no other, and the call returns without waiting for it.  ONE
+ * entry waits for its own stream before it returns (hipStreamSynchronize(stream); never the
+ * device, never another stream): scanerf_mesh_filter_emit, which reads V' and F' back to
+ * check them against the caller's.  tests/test_gpu_stream_contract.py holds the list
+ * (SYNCHRONISES) and checks every entry against it under a side stream.
  *
  * Citations are file:line under the reference repository.
  */

@@ -271,6 +271,17 @@ def feat_dtype_code(t):
     return {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}[t.dtype]
 
 
+def ordered_after(creator, seen):
+    """For a device tensor the package builds lazily and keeps (one copy, too large to keep per stream): `creator` is the torch stream
+    its first use filled it on.  A later use under ANOTHER stream first waits for that stream (once per stream: `seen` holds the
+    handles already ordered), so the reader cannot run ahead of the fill.  On the creating stream itself -- the single-stream path --
+    this is a comparison of two handles: no event, no launch."""
+    cur = torch.cuda.current_stream(creator.device)
+    if cur.cuda_stream != creator.cuda_stream and cur.cuda_stream not in seen:
+        cur.wait_stream(creator)
+        seen.add(cur.cuda_stream)
+
+
 _workspaces = {}
 
 

@@ -122,12 +122,17 @@ class HashGrid(nn.Module):
     # once per VALUE, not per call -- `.tolist()` of a device tensor and `.to(device)` of a pageable host tensor each stall the host
     # until the device has drained (three of the four synchronisations of a step, tools/sync_probe.py).  Keyed by tensor object and
     # version counter: a reassigned or in-place modified attribute (checkpoint load, pruning) is converted again.
+    # A device-side conversion is queued on the CURRENT stream, so it is kept per stream (a handful of ints each): a call under another
+    # stream converts its own copy instead of reading one that the first stream may not have written yet.
     def _converted(self, name, how):
         t = getattr(self, name)
-        hit = self.__dict__.setdefault("_conv_cache", {}).get(name + how)
+        key = name + how
+        if how != "list" and str(self.device).startswith("cuda"):
+            key = (key, torch.cuda.current_stream(self.device).cuda_stream)
+        hit = self.__dict__.setdefault("_conv_cache", {}).get(key)
         if hit is None or hit[0] is not t or hit[1] != t._version:   # (the entry holds the tensor: its address cannot be reused meanwhile)
             hit = (t, t._version, t.tolist() if how == "list" else t.to(self.device).int().contiguous())
-            self._conv_cache[name + how] = hit
+            self._conv_cache[key] = hit
         return hit[2]
 
     # ---- sampling (:278-337; no gradients) -------------------------------------------------------------------------------------

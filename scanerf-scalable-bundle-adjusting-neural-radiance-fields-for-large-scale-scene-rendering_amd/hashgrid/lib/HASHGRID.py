@@ -144,6 +144,9 @@ class PackedDecoders:
 # reference still points at the very same object and its version counter is unchanged -- an address recycled by the
 # caching allocator for a new tensor can never hit an old entry.  Writes that bypass the version counter
 # (params.data[...] = ...) are not seen: own a PackedDecoders and repack() instead.
+# The pack is a launch on the CURRENT stream, so an entry also belongs to the stream it was packed on: a call under another stream
+# packs images of its own instead of reading ones the first stream may not have written yet (nothing orders the two streams; a
+# PackedDecoders is ordered by whoever owns it, like every other tensor the caller passes).
 _images = {}
 
 
@@ -161,7 +164,7 @@ def _packed_images(params, folded=False):
     if isinstance(params, PackedDecoders):
         return params.images_folded if folded else params.images
     import weakref
-    key = (id(params), folded)
+    key = (id(params), folded, stream())
     hit = _images.get(key)
     if hit is not None and hit[0]() is params and hit[1] == params._version:
         return hit[2]

@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import network, render
+from . import _capi, network, render
 from .cuda import adam_step_cuda, sample_points_grid
 from .hashgrid import HashEmbeddingBG, level_resolutions
 from .network import sh3
@@ -178,6 +178,8 @@ class TileModel(nn.Module):
         self.adam_step = 0
         self._half_table = None       # f16 / bf16 gather copy of the table (configs[2]); kept in step by the Adam epilogue
         self._overflow_grad = None    # zero table for the fused scatter's workspace-overflow path (never filled per step)
+        # (the stream each of the two was filled on, and the streams already ordered behind it: _capi.ordered_after)
+        self._half_table_from = self._overflow_grad_from = None
 
     def gather_table(self):
         """The table the fused kernels gather from: the fp32 master, or its resident half-precision copy (half the gather
@@ -187,6 +189,9 @@ class TileModel(nn.Module):
             return self.features
         if self._half_table is None or self._half_table.dtype != self.table_dtype:
             self._half_table = self.features.detach().to(self.table_dtype).contiguous()
+            self._half_table_from = (torch.cuda.current_stream(self._half_table.device), set()) if self._half_table.is_cuda else None
+        elif self._half_table_from is not None:   # (converted under another stream: this one waits for it, once)
+            _capi.ordered_after(*self._half_table_from)
         return self._half_table
 
     def invalidate_gather_table(self):
@@ -196,6 +201,9 @@ class TileModel(nn.Module):
     def overflow_grad(self):
         if self._overflow_grad is None:
             self._overflow_grad = torch.zeros_like(self.features)
+            self._overflow_grad_from = (torch.cuda.current_stream(self._overflow_grad.device), set()) if self._overflow_grad.is_cuda else None
+        elif self._overflow_grad_from is not None:   # (zero-filled under another stream: this one waits for it, once)
+            _capi.ordered_after(*self._overflow_grad_from)
         return self._overflow_grad
 
     def set_occupancy(self, grid):
@@ -208,9 +216,13 @@ class TileModel(nn.Module):
     def weight_feature(self, global_step):
         """Coarse-to-fine mask on the device, cached: it is constant once global_step >= 10 000."""
         key = min(int(global_step), 10000)
-        if getattr(self, "_wf_key", None) != key:
-            self._wf_key, self._wf = key, network.weight_feature(global_step, self.device)
-        return self._wf
+        # (built by small kernels on the current stream: one 32-float copy per stream that asks, so that no stream reads a mask
+        # another one has not finished writing)
+        st = torch.cuda.current_stream(self.device).cuda_stream if str(self.device).startswith("cuda") else 0
+        hit = self.__dict__.setdefault("_wf_by_stream", {}).get(st)
+        if hit is None or hit[0] != key:
+            hit = self._wf_by_stream[st] = (key, network.weight_feature(global_step, self.device))
+        return hit[1]
 
     # ---- sampling (no grad: hashgrid/__init__.py:278-285) -------------------------------
     @torch.no_grad()
