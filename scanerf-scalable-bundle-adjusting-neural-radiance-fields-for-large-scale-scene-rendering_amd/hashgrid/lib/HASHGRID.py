@@ -261,14 +261,20 @@ def pts_inference_tracing(rays_o, rays_d, z_vals, dists, running_mask, intersect
         int(sample_major) | _infer_flags(folded), stream()), "pts_inference_tracing")
 
 
-def _layout_shape(name, t, sample_major, B, S, tail):
-    """`t` is a per-sample array of B rays x S samples in the layout `sample_major` (scanerf_hip.h), `tail` trailing dimensions."""
+def sample_shape(sample_major, B, S, *tail):
+    """Shape of a per-sample array of B rays x S samples in the layout `sample_major` (scanerf_hip.h; its flag bits are ignored):
+    [B,S] (0, the reference's), [S,B] (1) or [B/32,S,32] (2), then the `tail` dimensions."""
     lay = int(sample_major) & 3
     if lay == 2 and B % 32:
         raise RuntimeError(f"scanerf: sample_major=2 needs B a multiple of 32, got B={B}")
-    want = {0: (B, S), 1: (S, B), 2: (B // 32, S, 32)}[lay] + tuple(tail)
+    return {0: (B, S), 1: (S, B), 2: (B // 32, S, 32)}[lay] + tuple(tail)
+
+
+def _layout_shape(name, t, sample_major, B, S, tail):
+    """`t` is a per-sample array of B rays x S samples in the layout `sample_major` (scanerf_hip.h), `tail` trailing dimensions."""
+    want = sample_shape(sample_major, B, S, *tail)
     if tuple(t.shape) != want and not (tail == (1,) and tuple(t.shape) == want[:-1]):
-        raise RuntimeError(f"scanerf: {name} has shape {tuple(t.shape)}, expected {want} (sample_major={lay})")
+        raise RuntimeError(f"scanerf: {name} has shape {tuple(t.shape)}, expected {want} (sample_major={int(sample_major) & 3})")
 
 
 def pts_normals(rays_o, rays_d, z_vals, dists, block_idxs, features_tables, params, resolution, grid_occupied, grid_starts,

@@ -50,6 +50,35 @@ def render_box(block_corner, block_size):
     return block_corner + block_size / 4.0, block_size / 2.0
 
 
+class _Rays:
+    """The rays of a tracing pass, one row per ray.  Constants of the batch: rays_o, rays_d, inter (ray_block_intersection's [n,nb,2])
+    and tracing_blocks (each ray's tile order).  STATE, which a pass updates in place: tracing_idx, z_start, transp, dif, spec, depth
+    and normal (None unless asked for)."""
+    STATE = ("tracing_idx", "z_start", "transp", "dif", "spec", "depth", "normal")
+    FIELDS = ("rays_o", "rays_d", "inter", "tracing_blocks") + STATE
+
+    def __init__(self, **fields):
+        for k in self.FIELDS:
+            setattr(self, k, fields[k])
+
+    def take(self, idx):
+        """the sub-batch of the rays `idx`: every field gathered and contiguous"""
+        return _Rays(**{k: t if t is None else t[idx].contiguous() for k, t in vars(self).items()})
+
+    def put_back(self, idx, sub):
+        """the state of `sub` = take(idx) written to its rows (an index listed twice receives equal values twice)"""
+        for k in self.STATE:
+            if getattr(self, k) is not None:
+                getattr(self, k)[idx] = getattr(sub, k)
+
+
+def _work_buffers(sm, n, S, normals, dev):
+    """(pd, ps, pa, pn): per-sample diffuse, specular, opacity and -- with normals, else None -- normal of n rays x S samples in the
+    layout sm, uninitialised (the inference ops write them)"""
+    new = lambda c: torch.empty(_HG.sample_shape(sm, n, S, c), device=dev)
+    return new(3), new(3), new(1), new(3) if normals else None
+
+
 class TileSetRenderer:
     def __init__(self, device, tiles):
         """tiles: dicts as returned by load_tile (block_corner / block_size describe the 2x HashGrid box;
@@ -59,7 +88,7 @@ class TileSetRenderer:
         # prepare_points + pts_inference; a tracing pass runs on the running rays alone when fewer than this many tenths run
         self.fuse_slots = True
         self.compact_below_tenths = 9
-        self.skip_zero_transmittance_background = True   # exact: see render_rays
+        self.skip_zero_transmittance_background = True   # exact: see _behind_background
         t = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt).to(device).contiguous()
         self.feature_tables = t(np.stack([x["features"] for x in tiles]), torch.float16)
         self.params = t(np.stack([x["blob"] for x in tiles]), torch.float32)
@@ -108,138 +137,138 @@ class TileSetRenderer:
         index of 32 neighbouring rays -- neighbouring pixels share their cells down to the fine levels, so the table gathers of
         a wave fall on a few lines instead of 32 per level -- and walks along those rays; 1 = [S,B] (measured slower: every
         CU on the same depth slab)."""
-        dev, nb = self.device, self.block_corner.shape[0]
-        lay = int(layout)
         n_rays = rays_o.shape[0]
+        rays, sm, fused, n_hit, max_tracing = self._set_up(rays_o, rays_d, max(num_sample, num_bg_sample), layout, normals)
+        B = rays.transp.shape[0]
+        work = _work_buffers(sm, B, num_sample, normals, self.device)   # full size: every full-size pass reuses them
+        self._trace(rays, n_hit, max_tracing, work, num_sample=num_sample, sm=sm, fused=fused)
+        if num_bg_sample != num_sample:   # (else the background reuses the full-size colour buffers)
+            del work
+            work = _work_buffers(sm, B, num_bg_sample, False, self.device)
+        out = self._behind_background(rays, work, num_bg_sample=num_bg_sample, sample_range=sample_range, sm=sm,
+                                      skip_saturated=skip_saturated_background)
+        return tuple(t[:n_rays] for t in out) if B != n_rays else out
+
+    def _set_up(self, rays_o, rays_d, max_sample, layout, normals):
+        """-> (rays, sm, fused, n_hit, max_tracing): the batch as _Rays in its initial state, padded to a multiple of 32 where the layout
+        sm that will be used needs it; whether the inference kernel derives the slot lists (pts_inference_tracing); the number of tiles
+        each ray's path meets [B,1] and the view's maximum of it."""
+        dev, nb = self.device, self.block_corner.shape[0]
+        sm = int(layout)
         # the single-pass comparison kernel (HASHGRID.INFER_ARITH = "f32"; also what > 64 tiles or >= 2^31 samples fall back to)
         # reads the reference's [B,S] arrays only
-        single_pass = (_HG.INFER_ARITH == "f32" or nb > 64
-                       or (n_rays + 31) * max(num_sample, num_bg_sample) >= 2 ** 31)
+        single_pass = _HG.INFER_ARITH == "f32" or nb > 64 or (rays_o.shape[0] + 31) * max_sample >= 2 ** 31
         if single_pass:
-            lay = 0
-        if lay == 2 and n_rays % 32:  # pad with copies of the last ray
-            pad = 32 - n_rays % 32
+            sm = 0
+        if sm == 2 and rays_o.shape[0] % 32:  # pad with copies of the last ray
+            pad = 32 - rays_o.shape[0] % 32
             rays_o = torch.cat([rays_o, rays_o[-1:].expand(pad, 3)]).contiguous()
             rays_d = torch.cat([rays_d, rays_d[-1:].expand(pad, 3)]).contiguous()
         B = rays_o.shape[0]
-        sm = lay
-        shp = {0: lambda S, *tail: (B, S, *tail), 1: lambda S, *tail: (S, B, *tail), 2: lambda S, *tail: (B // 32, S, 32, *tail)}[lay]
         inter = torch.full((B, nb, 2), 1e7, device=dev)
         ray_block_intersection(rays_o, rays_d, self.block_corner, self.block_size, inter)
         tracing_blocks = sort_tracing_blocks(inter)   # = torch.argsort(inter[..., 0], dim=-1, stable=True)
         max_tracing = int(torch.mean((inter != 1e7).float(), dim=-1).sum(dim=-1).max().cpu())
-        transp = torch.ones(B, 1, device=dev)
-        dif, spec, depth = torch.zeros(B, 3, device=dev), torch.zeros(B, 3, device=dev), torch.zeros(B, 1, device=dev)
-        tracing_idx = torch.zeros(B, 1, dtype=torch.int32, device=dev)
-        z_start = torch.zeros(B, 1, device=dev)
-        pd = torch.empty(shp(num_sample, 3), device=dev)
-        ps = torch.empty(shp(num_sample, 3), device=dev)
-        pa = torch.empty(shp(num_sample, 1), device=dev)
-        normal = torch.zeros(B, 3, device=dev) if normals else None
-        pn = torch.empty(shp(num_sample, 3), device=dev) if normals else None
-
-        fuse_slots = tracing_fusable(nb) and not single_pass and self.fuse_slots
-
-        def fg_pass(ro, rd, it, tb, tidx, zst, tr, df, sp, dp, running, pd, ps, pa, nm=None, pn=None):
-            """One tracing pass (rendering.py:356-420) over the rays given: per-ray state tidx / zst / tr / df / sp / dp (and the
-            normal nm, when asked for) updated in place."""
-            n = ro.shape[0]
-            shp_ = {0: lambda S, *tail: (n, S, *tail), 1: lambda S, *tail: (S, n, *tail), 2: lambda S, *tail: (n // 32, S, 32, *tail)}[lay]
-            z = torch.full(shp_(num_sample), -1.0, device=dev)
-            dd = torch.full(shp_(num_sample), -1.0, device=dev)
-            sample_points(ro, rd, self.block_corner, self.block_size, self.fake_occupied_grid, self.grid_starts,
-                          self.grid_log2dim, tb, it, tidx, zst, z, dd, sample_major=sm)
-            bi = None
-            if nm is not None:   # the normals read slot lists, on either colour route (which stays what it would have been)
-                bi = torch.full(shp_(num_sample, 4), -1, dtype=torch.int16, device=dev)
-                prepare_points(z, running, it, bi, sample_major=sm)
-                pts_normals(ro, rd, z, dd, bi, self.feature_tables, self.params, self.resolution, self.occupied_grid,
-                            self.grid_starts, self.grid_log2dim, self.block_corner, self.block_size, pn, sample_major=sm)
-            if fuse_slots:   # the slot lists never exist: the inference kernel derives them (pts_inference_tracing); rays that
-                # got no sample in this pass (first depth -1) are neither written by it nor read by the accumulation
-                pts_inference_tracing(ro, rd, z, dd, running, it, self.feature_tables, self.packed, self.resolution, self.occupied_grid,
-                                      self.grid_starts, self.grid_log2dim, self.block_corner, self.block_size, pd, ps, pa,
-                                      sample_major=sm | SKIP_UNSAMPLED)
-                if nm is not None:   # (before accumulate_color, which advances the transparency both read)
-                    accumulate_normal(pn, pa, tr, z, nm, sample_major=sm | SKIP_UNSAMPLED)
-                accumulate_color(pd, ps, pa, tr, z, df, sp, dp, sample_major=sm | SKIP_UNSAMPLED)
-                return
-            else:
-                if bi is None:
-                    bi = torch.full(shp_(num_sample, 4), -1, dtype=torch.int16, device=dev)
-                    prepare_points(z, running, it, bi, sample_major=sm)
-                pts_inference(ro, rd, z, dd, bi, self.feature_tables, self.packed, self.resolution, self.occupied_grid,
-                              self.grid_starts, self.grid_log2dim, self.block_corner, self.block_size, pd, ps, pa, sample_major=sm)
-            if nm is not None:
-                accumulate_normal(pn, pa, tr, z, nm, sample_major=sm)
-            accumulate_color(pd, ps, pa, tr, z, df, sp, dp, sample_major=sm)
-
+        zeros = lambda c, dtype=torch.float32: torch.zeros(B, c, dtype=dtype, device=dev)
+        rays = _Rays(rays_o=rays_o, rays_d=rays_d, inter=inter, tracing_blocks=tracing_blocks, tracing_idx=zeros(1, torch.int32),
+                     z_start=zeros(1), transp=torch.ones(B, 1, device=dev), dif=zeros(3), spec=zeros(3), depth=zeros(1),
+                     normal=zeros(3) if normals else None)
         # tiles each ray's path meets (the sorted list ends at the first miss): a ray whose tracing index has reached its own count has
-        # nothing left to sample -- sample_points leaves it at once (`bound.x == kInf`), so dropping it from `running` here (the
+        # nothing left to sample -- sample_points leaves it at once (`bound.x == kInf`), so dropping it from `running` (the
         # reference's mask compares with the view's maximum, rendering.py:356) changes no value and lets the later passes run on
         # the few rays that do cross a second tile
         n_hit = (inter[..., 0] != 1e7).sum(dim=-1, keepdim=True).to(torch.int32).clamp_(max=max_tracing)
+        return rays, sm, tracing_fusable(nb) and not single_pass and self.fuse_slots, n_hit, max_tracing
+
+    def _fg_pass(self, rays, running, work, *, num_sample, sm, fused):
+        """One tracing pass (rendering.py:356-420) over `rays`, whose state it updates in place.  running: [n] bool, the rays that get
+        slot lists; work: _work_buffers of as many rays."""
+        r, dev = rays, self.device
+        pd, ps, pa, pn = work
+        shape = lambda *tail: _HG.sample_shape(sm, r.transp.shape[0], num_sample, *tail)
+        boxes = (self.block_corner, self.block_size)
+        scene = (self.resolution, self.occupied_grid, self.grid_starts, self.grid_log2dim, *boxes)
+        z = torch.full(shape(), -1.0, device=dev)
+        dd = torch.full(shape(), -1.0, device=dev)
+        sample_points(r.rays_o, r.rays_d, *boxes, self.fake_occupied_grid, self.grid_starts, self.grid_log2dim, r.tracing_blocks,
+                      r.inter, r.tracing_idx, r.z_start, z, dd, sample_major=sm)
+        if r.normal is not None or not fused:   # the normals read slot lists, on either colour route (which stays what it would have been)
+            bi = torch.full(shape(4), -1, dtype=torch.int16, device=dev)
+            prepare_points(z, running, r.inter, bi, sample_major=sm)
+        if r.normal is not None:
+            pts_normals(r.rays_o, r.rays_d, z, dd, bi, self.feature_tables, self.params, *scene, pn, sample_major=sm)
+        # fused: no slot lists for the colours, the inference kernel derives them; rays that got no sample in this pass (first depth
+        # -1) are neither written by it nor read by the accumulations
+        flags = sm | SKIP_UNSAMPLED if fused else sm
+        if fused:
+            pts_inference_tracing(r.rays_o, r.rays_d, z, dd, running, r.inter, self.feature_tables, self.packed, *scene, pd, ps, pa,
+                                  sample_major=flags)
+        else:
+            pts_inference(r.rays_o, r.rays_d, z, dd, bi, self.feature_tables, self.packed, *scene, pd, ps, pa, sample_major=sm)
+        if r.normal is not None:   # (before accumulate_color, which advances the transparency both read)
+            accumulate_normal(pn, pa, r.transp, z, r.normal, sample_major=flags)
+        accumulate_color(pd, ps, pa, r.transp, z, r.dif, r.spec, r.depth, sample_major=flags)
+
+    def _trace(self, rays, n_hit, max_tracing, work, *, num_sample, sm, fused):
+        """The tracing loop: passes over the tiles along each ray until no ray runs.  work: the full-size _work_buffers."""
+        B, how = rays.transp.shape[0], dict(num_sample=num_sample, sm=sm, fused=fused)
         for _ in range(max_tracing):
-            running = ((tracing_idx < n_hit) & (transp > 1e-5))[:, 0].contiguous()
+            running = ((rays.tracing_idx < n_hit) & (rays.transp > 1e-5))[:, 0].contiguous()
             n_run = int(running.sum())
             if n_run == 0:
                 break
             if n_run * 10 > B * self.compact_below_tenths:   # (compaction costs ~0.1 ms of gathers)
-                fg_pass(rays_o, rays_d, inter, tracing_blocks, tracing_idx, z_start, transp, dif, spec, depth, running, pd, ps, pa,
-                        normal, pn)
+                self._fg_pass(rays, running, work, **how)
                 continue
             # Not every ray runs (rays that miss every tile; later passes: most have left the tiles or are saturated): the pass runs
-            # on the running rays alone -- every op
-            # is per ray, so each running ray gets the values the full-size pass gives it; the others' colours are untouched either
-            # way, and their tracing state (which the full-size pass advances) is never read again: a ray that stopped stays stopped
-            # (the full-size pass costs its fills, slot lists and accumulation for every ray: ~4 ms at 1920x1080 for nothing)
+            # on the running rays alone -- every op is per ray, so each running ray gets the values the full-size pass gives it; the
+            # others' colours are untouched either way, and their tracing state (which the full-size pass advances) is never read
+            # again: a ray that stopped stays stopped (the full-size pass costs its fills, slot lists and accumulation for every ray:
+            # ~4 ms at 1920x1080 for nothing)
             idx = running.nonzero()[:, 0]
-            if lay == 2 and n_run % 32:
+            if sm == 2 and n_run % 32:   # (the padding repeats the last running ray)
                 idx = torch.cat([idx, idx[-1:].expand(32 - n_run % 32)])
             n = idx.shape[0]
-            state = (tracing_idx, z_start, transp, dif, spec, depth) + ((normal,) if normals else ())
-            sub = [t[idx].contiguous() for t in (rays_o, rays_d, inter, tracing_blocks) + state]
-            shp_n = {0: lambda S, *tail: (n, S, *tail), 1: lambda S, *tail: (S, n, *tail), 2: lambda S, *tail: (n // 32, S, 32, *tail)}[lay]
-            fg_pass(*sub[:10], torch.ones(n, dtype=torch.bool, device=dev), torch.empty(shp_n(num_sample, 3), device=dev),
-                    torch.empty(shp_n(num_sample, 3), device=dev), torch.empty(shp_n(num_sample, 1), device=dev),
-                    sub[10] if normals else None, torch.empty(shp_n(num_sample, 3), device=dev) if normals else None)
-            for full, part in zip(state, sub[4:]):
-                full[idx] = part   # (the padding repeats the last ray: equal values land on it twice)
-        # blended backgrounds of the exit tile(s)
+            sub = rays.take(idx)
+            self._fg_pass(sub, torch.ones(n, dtype=torch.bool, device=self.device),
+                          _work_buffers(sm, n, num_sample, rays.normal is not None, self.device), **how)
+            rays.put_back(idx, sub)
+
+    def _behind_background(self, rays, work, *, num_bg_sample, sample_range, sm, skip_saturated):
+        """The blended backgrounds of each ray's exit tile(s) (rendering.py:421-536), composed behind the traced foreground
+        -> render_rays' outputs for the whole (padded) batch.  work: _work_buffers of B rays x num_bg_sample samples."""
+        r, dev, B = rays, self.device, rays.transp.shape[0]
+        pd, ps, pa, _ = work
+        zeros = lambda c: torch.zeros(B, c, device=dev)
         bg_b = torch.full((B, 4), -1, dtype=torch.int16, device=dev)
-        bg_w = torch.zeros(B, 4, device=dev)
-        update_outgoing_bidx(rays_o, rays_d, self.block_corner, self.block_size, tracing_blocks, inter, bg_b, bg_w, 0.12, False)
+        bg_w = zeros(4)
+        update_outgoing_bidx(r.rays_o, r.rays_d, self.block_corner, self.block_size, r.tracing_blocks, r.inter, bg_b, bg_w, 0.12, False)
         bg_w = bg_w / torch.sum(bg_w, dim=-1, keepdim=True)
         # rays whose foreground transmittance is EXACTLY zero (an opacity rounded to 1.0 on the way: hard surfaces) get no background:
         # it would be multiplied by that zero -- `dif + 0 * bgd` is `dif` bit for bit, colour and depth alike -- so nothing changes
         # but the decoder work of their 128 background samples (exact, unlike skip_saturated_background below)
         if self.skip_zero_transmittance_background:
-            bg_b[(transp == 0)[:, 0]] = -1
-        if skip_saturated_background:
+            bg_b[(r.transp == 0)[:, 0]] = -1
+        if skip_saturated:
             # rays the foreground has saturated get no background: it would enter the pixel with weight <= 1e-5 -- 400x below
             # one 8-bit step -- and on an opaque scene it is most of the frame's decoder work
-            bg_b[(transp <= 1e-5)[:, 0]] = -1
+            bg_b[(r.transp <= 1e-5)[:, 0]] = -1
         n_blend = int((bg_w > 0).sum(dim=-1).max().cpu())
-        bgd, bgs, bgz = torch.zeros(B, 3, device=dev), torch.zeros(B, 3, device=dev), torch.zeros(B, 1, device=dev)
-        if num_bg_sample != num_sample:
-            pd = torch.empty(shp(num_bg_sample, 3), device=dev)
-            ps = torch.empty(shp(num_bg_sample, 3), device=dev)
-            pa = torch.empty(shp(num_bg_sample, 1), device=dev)
+        bgd, bgs, bgz = zeros(3), zeros(3), zeros(1)
         for i in range(n_blend):
-            zb = torch.full(shp(num_bg_sample), -1.0, device=dev)
-            inverse_z_sampling(inter, bg_b[:, i].contiguous(), zb, sample_range, sample_major=sm)
+            zb = torch.full(_HG.sample_shape(sm, B, num_bg_sample), -1.0, device=dev)
+            inverse_z_sampling(r.inter, bg_b[:, i].contiguous(), zb, sample_range, sample_major=sm)
             # (bg_pts_inference_v2 writes every sample: zeros where the ray has no background tile at this blend step)
-            bg_pts_inference_v2(rays_o, rays_d, zb, bg_b, i, self.block_corner, self.block_size, self.resolution,
+            bg_pts_inference_v2(r.rays_o, r.rays_d, zb, bg_b, i, self.block_corner, self.block_size, self.resolution,
                                 self.feature_tables, self.packed, pd, ps, pa, sample_major=sm)
-            t1 = torch.ones(B, 1, device=dev)
-            td, ts, tz = torch.zeros(B, 3, device=dev), torch.zeros(B, 3, device=dev), torch.zeros(B, 1, device=dev)
+            t1, td, ts, tz = torch.ones(B, 1, device=dev), zeros(3), zeros(3), zeros(1)
             accumulate_color(pd, ps, pa, t1, zb, td, ts, tz, sample_major=sm)
             w = torch.nan_to_num(bg_w[:, i:i + 1])  # rays with no exit tile: 0/0 in the reference's normalisation
             bgd += td * w
             bgs += ts * w
             bgz += tz * w
-        out = (dif + transp * bgd, spec + transp * bgs, depth + transp * bgz, transp) + ((normal,) if normals else ())
-        return tuple(t[:n_rays] for t in out) if B != n_rays else out
+        out = (r.dif + r.transp * bgd, r.spec + r.transp * bgs, r.depth + r.transp * bgz, r.transp)
+        return out if r.normal is None else out + (r.normal,)
 
     def render(self, H, W, K, c2w, **kw):
         """One view -> (diffuse [H,W,3], specular [H,W,3], depth [H,W,1], transparency [H,W,1]), and with normals=True the normal map

@@ -452,8 +452,8 @@ def test_above_64_tiles_everything_takes_the_single_pass_route(monkeypatch):
 # ------------------------------------------------------------------ f. renderer end to end
 @pytest.mark.parametrize("name", ["G9", "G36", "G64"])
 def test_renderer_end_to_end_on_grids(name, monkeypatch):
-    """TileSetRenderer.render_rays on 9, 36 and 64 tiles: the oracle's loop, in the layouts 0 and 2, twice the same bits, and the
-    later tracing passes run on the compacted running rays."""
+    """TileSetRenderer.render_rays on 9, 36 and 64 tiles: the oracle's loop, in the layouts 0 and 2 (on G9 also 1), twice the same
+    bits, and the later tracing passes run on the compacted running rays."""
     sampled, fused = count_calls(monkeypatch, "sample_points"), count_calls(monkeypatch, "pts_inference_tracing")
     ref = oracle_image(name)
     assert ref["T"].min() < 1e-5 and ref["T"].max() == 1.0 and (ref["T"] < 0.5).mean() > 0.5
@@ -473,6 +473,11 @@ def test_renderer_end_to_end_on_grids(name, monkeypatch):
         assert np.array_equal(a, b)
     for a, b in zip(lay0, render(name, layout=0)):
         assert np.array_equal(a, b)
+    if name == "G9":   # the [S,B] layout, end to end here alone: unpadded like layout 0
+        n01 = len(sampled)
+        image_close(render(name, layout=1), ref, f"{name} layout 1")
+        assert len(sampled) > n01 and all(sm == 1 for _, sm in sampled[n01:])
+        assert sampled[n01][0] == B and all(b <= B for b, _ in sampled[n01:])
 
 
 def test_renderer_fused_and_two_op_routes_give_the_same_bits_at_eight_tiles(monkeypatch):
