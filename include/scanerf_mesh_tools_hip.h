@@ -1,0 +1,62 @@
+/*
+ * scanerf_mesh_tools_hip.h -- the second public header of libscanerf_hip.so: post-processing ops on extracted meshes that came after
+ * ABI version 10 was pinned.  The same library and the same conventions as scanerf_hip.h (int status, scanerf_last_error(), device
+ * pointers, contiguous row-major arrays, the stream last, no allocation, no state, no environment variable); scanerf_stream_t is
+ * the first header's.  The entries live here, and not in scanerf_hip.h, because that header's set of declarations is pinned by the
+ * ABI version and by the stream-contract registry (tests/test_capi_cpu.py, tests/stream_cases.py); an op added here leaves both as
+ * they are and brings its own checks (tests/test_mesh_visibility_cpu.py, tests/test_gpu_mesh_visibility.py).  The Python side
+ * types these entries from _capi.TOOL_PROTOTYPES and calls them through _capi.tool(name).
+ */
+#ifndef SCANERF_MESH_TOOLS_HIP_H_
+#define SCANERF_MESH_TOOLS_HIP_H_
+
+#include "scanerf_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* ---- point visibility from a set of cameras (csrc/mesh_visibility.hip): for every point and every camera, is the
+ *   point inside the camera's image and is the segment between them free of the mesh?  What "cull the parts of an extracted mesh
+ *   that no training camera saw" needs.  The reference has no counterpart; the definition is this comment.
+ *   Inputs: points [N,3] f32 (any points, typically a mesh's vertices); Ks [C,9], C2Ws [C,12] f32 row-major, as scanerf_view_coverage
+ *     takes them; the image size H, W; bias > 0 and finite; near >= 0; far > 0 (+inf allowed); the tracer's arrays exactly as
+ *     scanerf_mesh_first_hit takes them (tris != NULL: pre-gathered triangles, else vertices / faces / cell_faces); log2dim 4..7.
+ *   Everything below is float32, operation by operation, without FMA contraction.  For point p and camera c:
+ *     fx = K[0], cx = K[2], fy = K[4], cy = K[5] (skew is ignored, as scanerf_compute_ray_forward ignores it); column k of R is
+ *     (C2W[k], C2W[4 + k], C2W[8 + k]); the eye is E = (C2W[3], C2W[7], C2W[11]).
+ *     w = p - E;  xc = (w0 R00 + w1 R10) + w2 R20, yc and zc likewise with columns 1 and 2;  len = sqrtf((w0 w0 + w1 w1) + w2 w2).
+ *   IN VIEW iff p is finite and zc > near and len <= far and len > bias and 0 <= fx (xc / zc) + cx < (float)W and
+ *     0 <= fy (yc / zc) + cy < (float)H.  Pixel px covers [px, px + 1): the +0.5 convention of scanerf_compute_ray_forward.
+ *   SEGMENT: s = bias / len, P = p - s w, d = E - P: it starts `bias` towards the eye, so that the point's own faces do not hide it.
+ *   HIDDEN iff the first-hit walk of scanerf_mesh_first_hit on the ray (P, d) would return h with 0 < h < 1.  The kernel does not
+ *     finish that walk: it stops at the first triangle with 0 < t < 1, and after the first cell whose exit t1 >= 1; it uses the same
+ *     grid walk, the same ray / triangle test (two-sided, edges inclusive, |det| <= 1e-12 is a dead face that hides nothing) and the
+ *     same operands (A, B - A, C - A).  An occluder behind the eye does not count.
+ *   SEEN = in view and not hidden.
+ *   Outputs: views [N] i32 = the number of cameras that see the point (every element written; 0 for a non-finite point);
+ *     mask [N, ceil(C / 32)] u32 (may be NULL: not written): bit c & 31 of word c >> 5 is seen(p, c), the unused high bits are 0.
+ *   Integer outputs only, every element written exactly once by a plain store, nothing else written: two launches give equal bits,
+ *     both triangle forms give equal bits, every log2dim gives equal bits.
+ *   N == 0 launches nothing.  C == 0 writes zeros to views (mask has no columns; the camera and tracer arrays are not read).
+ *   Refused before any launch (nothing written): N < 0 or C < 0, null pointers (but tris, mask), H or W < 1, log2dim outside 4..7,
+ *     bias not in (0, inf), near negative or NaN, far not > 0.  No allocation, no host synchronisation; every launch on `stream`.
+ *   scanerf_mesh_point_views_cameras_per_pass: the cameras a wavefront takes per pass over its 64 points (its on-chip mask words); a
+ *     larger C takes several passes.
+ *   scanerf_mesh_point_views_counted (measurement): also adds to counters [3] u64, which the caller zeroes: the pairs in view (the
+ *     segments walked), the occupied cells looked at, the ray / triangle tests. */
+int scanerf_mesh_point_views_cameras_per_pass(void);
+int scanerf_mesh_point_views(const float *points, int N, const float *Ks, const float *C2Ws, int C, int H, int W, float bias,
+                             float near, float far, const float *vertices, const int32_t *faces, const float *tris,
+                             const uint64_t *bitmask, const uint32_t *rank, const int32_t *start_num, const int32_t *cell_faces,
+                             const float *scene_info, int log2dim, int32_t *views, uint32_t *mask, scanerf_stream_t stream);
+int scanerf_mesh_point_views_counted(const float *points, int N, const float *Ks, const float *C2Ws, int C, int H, int W, float bias,
+                                     float near, float far, const float *vertices, const int32_t *faces, const float *tris,
+                                     const uint64_t *bitmask, const uint32_t *rank, const int32_t *start_num,
+                                     const int32_t *cell_faces, const float *scene_info, int log2dim, int32_t *views, uint32_t *mask,
+                                     uint64_t *counters, scanerf_stream_t stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* SCANERF_MESH_TOOLS_HIP_H_ */

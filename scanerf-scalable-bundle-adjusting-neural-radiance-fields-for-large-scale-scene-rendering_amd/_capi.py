@@ -128,6 +128,14 @@ PROTOTYPES = {
 }
 SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if required]
 OPTIONAL_SYMBOLS = [n for n, (_, _, required) in PROTOTYPES.items() if not required]
+# The exports of the second public header, include/scanerf_mesh_tools_hip.h (ops that came after ABI version 10 pinned the first
+# header's set): the same letters, typed the same way, reached through tool(name) and not through lib().  All of them are required.
+# tests/test_mesh_visibility_cpu.py checks this table against that header.
+TOOL_PROTOTYPES = {
+    "scanerf_mesh_point_views_cameras_per_pass": ("I", ""),
+    "scanerf_mesh_point_views": ("I", "PIPPIIIFFFPPPPPPPPIPPP"),
+    "scanerf_mesh_point_views_counted": ("I", "PIPPIIIFFFPPPPPPPPIPPPP"),
+}
 CTYPES = {"P": ctypes.c_void_p, "I": ctypes.c_int, "U": ctypes.c_uint, "F": ctypes.c_float, "Z": ctypes.c_size_t,
           "L": ctypes.c_int64, "S": ctypes.c_char_p}
 
@@ -159,6 +167,22 @@ def _typed(fn, name, ret, args):
         return fn(*a)
     call.__name__ = name
     return call
+
+
+_tools = {}
+
+
+def tool(name):
+    """The typed function of an export of include/scanerf_mesh_tools_hip.h (TOOL_PROTOTYPES); a library without it is an error."""
+    fn = _tools.get(name)
+    if fn is None:
+        ret, args = TOOL_PROTOTYPES[name]
+        lib()   # the checks and the warnings of the first load
+        so = ctypes.CDLL(LIB_PATH)
+        if not hasattr(so, name):
+            raise RuntimeError(f"scanerf: {LIB_PATH} does not export {name}")
+        fn = _tools[name] = _typed(getattr(so, name), name, ret, args)
+    return fn
 
 
 def lib():

@@ -11,7 +11,8 @@ Two deliberate differences from the reference's kernels:
   * first_hit carries its nearest candidate across cells; the reference returns at the first cell with any hit, even one that
     lies beyond that cell, which hides nearer surfaces behind large triangles.
 closest_point (csrc/mesh_distance.hip) has no counterpart in the reference: the exact nearest triangle per query
-point on the same structure, for the geometric evaluation of evaluation.py.
+point on the same structure, for the geometric evaluation of evaluation.py.  Neither has point_views (csrc/mesh_visibility.hip;
+DESIGN.md 4.19): which cameras see which points, the mesh occluding -- what meshing.cull_unseen drops unseen surface by.
 There is no CPU path: CPU tensors raise.
 """
 import torch
@@ -196,6 +197,86 @@ class FastMesh:
                 self.vertices.shape[0], self.faces.shape[0], dev_ptr(self.scene_info, _f32, "scene_info"), self.log2dim, max_dist,
                 *out, stream()), "mesh_closest_point_brute")
         return torch.sqrt(dist2), face, closest
+
+    # ---- which cameras see which points (csrc/mesh_visibility.hip) ----------------------------------------------
+    @torch.no_grad()
+    def point_views(self, points, ks, c2ws, H, W, bias, near=0.0, far=float("inf"), want_mask=False, route="fused"):
+        """points [N,3] float32 on the GPU, cameras ks [C,3,3] / c2ws [C,3,4] (arrays or tensors, moved to the points' device), the
+        image size -> (views [N] i32: the number of cameras that see each point, mask [N, ceil(C/32)] i32 or None: bit c & 31 of word
+        c >> 5 is "camera c sees the point").  Seen = inside the image, nearer than `far`, beyond `near` along the optical axis, and
+        the segment from the point (moved `bias` towards the eye) to the eye meets no face; include/scanerf_mesh_tools_hip.h is the
+        definition.  route="fused": one launch for all pairs; route="composed": the witness, per camera the same operands as separate
+        torch elementwise ops, first_hit on the pairs in view, 0 < h < 1 (same bits where torch's division and square root are
+        correctly rounded)."""
+        if route not in ("fused", "composed"):
+            raise ValueError(f"scanerf: point_views route must be 'fused' or 'composed', got {route!r}")
+        bias, near, far = float(bias), float(near), float(far)
+        if not (0.0 < bias < float("inf")):
+            raise ValueError(f"scanerf: point_views bias must be > 0 and finite, got {bias}")
+        if not near >= 0.0:
+            raise ValueError(f"scanerf: point_views near must be >= 0, got {near}")
+        if not far > 0.0:
+            raise ValueError(f"scanerf: point_views far must be > 0 (inf for no limit), got {far}")
+        for name, v in (("H", H), ("W", W)):
+            if isinstance(v, bool) or int(v) != v or v < 1:
+                raise ValueError(f"scanerf: point_views {name} must be a positive integer, got {v!r}")
+        H, W = int(H), int(W)
+        if isinstance(points, torch.Tensor) and (points.dtype != _f32 or points.dim() != 2 or points.shape[1] != 3):
+            raise RuntimeError(f"scanerf: points must be [N,3] float32, got {tuple(points.shape)} {points.dtype}")
+        _require_gpu(points, "points")
+        from .allocation import _cameras
+        p = points.detach().contiguous()
+        k9, c12 = _cameras(ks, c2ws, p.device)
+        N, C = p.shape[0], k9.shape[0]
+        nw = (C + 31) // 32
+        if route == "composed":
+            return self._point_views_composed(p, k9, c12, H, W, bias, near, far, want_mask)
+        views = torch.empty(N, dtype=_i32, device=p.device)
+        mask = torch.empty((N, nw), dtype=_i32, device=p.device) if want_mask else None
+        if N == 0:
+            return views, mask
+        from ._capi import tool
+        check(tool("scanerf_mesh_point_views")(
+            dev_ptr(p, _f32, "points"), N, dev_ptr(k9, _f32, "ks"), dev_ptr(c12, _f32, "c2ws"), C, H, W, bias, near, far,
+            dev_ptr(self.vertices, _f32, "vertices"), dev_ptr(self.faces, _i32, "faces"),
+            dev_ptr(self.tris, _f32, "tris", allow_none=True), dev_ptr(self.bitmask, _i64, "bitmask"),
+            dev_ptr(self.rank, _i32, "rank"), dev_ptr(self.start_num, _i32, "start_num"),
+            dev_ptr(self.cell_faces, _i32, "cell_faces"), dev_ptr(self.scene_info, _f32, "scene_info"), self.log2dim,
+            dev_ptr(views, _i32, "views"), dev_ptr(mask, _i32, "mask", allow_none=True), stream()), "mesh_point_views")
+        return views, mask
+
+    def _point_views_composed(self, p, k9, c12, H, W, bias, near, far, want_mask):
+        dev = p.device
+        N, C = p.shape[0], k9.shape[0]
+        scalar = lambda v: torch.tensor(v, dtype=_f32, device=dev)
+        bias, near, far, Hf, Wf = scalar(bias), scalar(near), scalar(far), scalar(float(H)), scalar(float(W))
+        finite = torch.isfinite(p).all(1)
+        views = torch.zeros(N, dtype=_i32, device=dev)
+        words = torch.zeros((N, (C + 31) // 32), dtype=_i64, device=dev)
+        for c in range(C):
+            K, T = k9[c], c12[c]
+            E = torch.stack([T[3], T[7], T[11]])
+            w = p - E
+            w0, w1, w2 = w[:, 0], w[:, 1], w[:, 2]
+            xc = (w0 * T[0] + w1 * T[4]) + w2 * T[8]
+            yc = (w0 * T[1] + w1 * T[5]) + w2 * T[9]
+            zc = (w0 * T[2] + w1 * T[6]) + w2 * T[10]
+            length = torch.sqrt((w0 * w0 + w1 * w1) + w2 * w2)
+            px = K[0] * (xc / zc) + K[2]
+            py = K[4] * (yc / zc) + K[5]
+            inview = finite & (zc > near) & (length <= far) & (length > bias) & (px >= 0) & (px < Wf) & (py >= 0) & (py < Hf)
+            idx = torch.nonzero(inview).reshape(-1)
+            if idx.shape[0] == 0:
+                continue
+            pi, wi = p[idx], w[idx]
+            s = bias / length[idx]
+            P = pi - s[:, None] * wi
+            d = E - P
+            h = self.first_hit(P.contiguous(), d.contiguous())
+            seen = idx[~((h > 0) & (h < 1))]
+            views[seen] += 1
+            words[seen, c >> 5] |= 1 << (c & 31)
+        return views, (words.to(_i32) if want_mask else None)
 
     # ---- the reference's methods --------------------------------------------------------------------------------------------
     def _box(self):

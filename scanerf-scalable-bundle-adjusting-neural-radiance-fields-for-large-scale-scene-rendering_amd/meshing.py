@@ -13,6 +13,10 @@ lattice.  The reference has no mesh extraction; the definition is the comment of
                                                         DESIGN.md 4.17)
     filter_mesh(mesh, min_faces, min_extent, keep_largest)   drop floaters and unused vertices by component; the extractors take the
                                                         same three rules and filter before they evaluate normals
+    vertex_views(mesh, ks, c2ws, H, W, bias)            how many cameras see each vertex, the mesh itself occluding (csrc/mesh_visibility.hip;
+                                                        DESIGN.md 4.19)
+    cull_unseen(mesh, ks, c2ws, H, W, min_views, bias)  drop the faces none of whose vertices min_views cameras saw; the extractors take
+                                                        cameras / min_views / view_bias and cull before the component rule
 
 All return a Mesh: vertices [V,3] f32 (world), faces [F,3] i32 (counter-clockwise seen from the outside), cells [V,3] i32 (the owning
 cell of each vertex), lattice [V,3] f32 (the vertices in lattice coordinates) and, on request, normals [V,3] f32.  Two launches with
@@ -119,16 +123,20 @@ def _contracted(lattice, n):
 
 
 def extract_mesh(features, resolutions, blob, weight_feature, occupied_grid, log2dim, occ_corner, occ_size, n, level, normals=False,
-                 route="fused", min_faces=0, min_extent=0, keep_largest=None, report=None):
+                 route="fused", min_faces=0, min_extent=0, keep_largest=None, report=None, cameras=None, min_views=0, view_bias=None,
+                 view_far=None):
     """The level set sigma == level of a tile's density as a triangle mesh.  features [16,T,2] f32 / f16, resolutions [16,3], blob (the
     flat decoder blob), weight_feature [32], occupied_grid bool [2^log2dim], occ_corner / occ_size: the tile box (3 floats each),
     n: cells per axis of the lattice over it.  normals=True adds render.sigma_normals_points' normals at the vertices
     (axis_scale = 4 / (2 occ_size)).  min_faces / min_extent / keep_largest: filter_mesh's keep rule, applied BEFORE the normals are
     evaluated (they are computed at the kept vertices only); the defaults keep everything.  report: a dict that receives the
-    component count and the rows before and after the filter."""
+    component count and the rows before and after the filter.  cameras = (ks, c2ws, H, W) with min_views >= 1: cull_unseen on the raw
+    mesh, BEFORE the component rule (so min_faces removes what the cull fragments); view_bias: half a lattice spacing by default;
+    view_far: the cameras' range (None: no limit); report["cull"] receives cull_unseen's report."""
     if route not in ROUTES:
         raise RuntimeError(f"scanerf: route must be one of {ROUTES}, got {route!r}")
     _rules(min_faces, min_extent, keep_largest, True)
+    _view_rule(cameras, min_views, view_bias, view_far)
     n = _lattice_size(n)
     T, mid = render._normals_common(features, resolutions, blob, weight_feature)
     occ = dev_ptr(occupied_grid, (torch.bool, torch.uint8), "occupied_grid")
@@ -150,6 +158,7 @@ def extract_mesh(features, resolutions, blob, weight_feature, occupied_grid, log
         l2d = (ctypes.c_int32 * 3)(*log2dim)
         head = (*mid, T, occ, l2d, int(occupied_grid.numel()), *n, float(level))
         mesh = _fused(device, n, "isosurface_count", "isosurface_emit", head, (corner, size))
+    mesh = _cull_extracted(mesh, cameras, min_views, view_bias, view_far, size, n, route, report)
     mesh = _filter(mesh, min_faces, min_extent, keep_largest, _COMPONENT_ROUTE[route], False, report)
     if normals:
         if mesh.vertices.shape[0]:
@@ -230,7 +239,8 @@ def _scene_tile_args(feature_tables, resolutions, blobs, corners, sizes, occupie
 
 
 def extract_scene_mesh(feature_tables, resolutions, blobs, corners, sizes, occupied_grid, grid_starts, log2dim, box_corner, box_size, n,
-                       level, route="fused", normals=False, min_faces=0, min_extent=0, keep_largest=None, report=None):
+                       level, route="fused", normals=False, min_faces=0, min_extent=0, keep_largest=None, report=None, cameras=None,
+                       min_views=0, view_bias=None, view_far=None):
     """One mesh of a tiled scene: the level set of the field the multi-tile renderer draws -- the tiles' densities blended per lattice
     point with the renderer's xz-distance weights -- on a lattice of n cells over the world box box_corner / box_size (the definition:
     include/scanerf_hip.h, scanerf_isosurface_count_tiles).  The tile arrays are TileSetRenderer's: feature_tables [nb,16,T,2] f16,
@@ -239,10 +249,13 @@ def extract_scene_mesh(feature_tables, resolutions, blobs, corners, sizes, occup
     vertices (the gradient of the blended field itself), otherwise normals is None.  route="fused" never stores the
     lattice; route="dense" composes host geometry -> render.sigma_normals_points per tile -> blend -> surface_nets (the witness).
     min_faces / min_extent / keep_largest: filter_mesh's keep rule, applied BEFORE the normals are evaluated; the
-    defaults keep everything.  report: a dict that receives the component count and the rows before and after the filter."""
+    defaults keep everything.  report: a dict that receives the component count and the rows before and after the filter.
+    cameras = (ks, c2ws, H, W) with min_views >= 1: cull_unseen on the raw mesh (DESIGN.md 4.19), BEFORE the component rule;
+    view_bias: half a lattice spacing by default; view_far: the cameras' range (None: no limit)."""
     if route not in ROUTES:
         raise RuntimeError(f"scanerf: route must be one of {ROUTES}, got {route!r}")
     _rules(min_faces, min_extent, keep_largest, True)
+    _view_rule(cameras, min_views, view_bias, view_far)
     n = _lattice_size(n)
     tiles = (feature_tables, resolutions, blobs, corners, sizes, occupied_grid, grid_starts, log2dim)
     head, T, nb = _scene_tile_args(*tiles)
@@ -258,6 +271,7 @@ def extract_scene_mesh(feature_tables, resolutions, blobs, corners, sizes, occup
         mesh = surface_nets(torch.from_numpy(values).to(device).contiguous(), level, list(corner), step)
     else:
         mesh = _fused(device, n, "isosurface_count_tiles", "isosurface_emit_tiles", (*head, T, nb, corner, size, *n, float(level)))
+    mesh = _cull_extracted(mesh, cameras, min_views, view_bias, view_far, size, n, route, report)
     mesh = _filter(mesh, min_faces, min_extent, keep_largest, _COMPONENT_ROUTE[route], False, report)
     if normals:
         mesh = mesh._replace(normals=scene_sigma_normals_points(mesh.vertices, *tiles, route=route)[2])
@@ -561,6 +575,106 @@ def filter_mesh(mesh, min_faces=0, min_extent=0, keep_largest=None, route="fused
     input.  min_faces=1 alone removes exactly the vertices no face uses.  Kept vertices and faces stay in their order, the faces'
     indices are remapped, cells / lattice / normals (where the mesh has them) are gathered row for row.  -> Mesh."""
     return _filter(mesh, min_faces, min_extent, keep_largest, route, True)
+
+
+# ---- which cameras see the mesh, and the cull by it (csrc/mesh_visibility.hip; DESIGN.md 4.19) ---------------------------------------
+VIEW_ROUTES = ("fused", "composed")
+_VIEW_ROUTE = {"fused": "fused", "dense": "composed"}      # the extractors' witness route composes the visibility too
+
+
+def _min_views(min_views):
+    if isinstance(min_views, bool) or not isinstance(min_views, (int, np.integer)) or min_views < 0:
+        raise RuntimeError(f"scanerf: min_views must be a non-negative integer, got {min_views!r}")
+    return int(min_views)
+
+
+def _view_rule(cameras, min_views, view_bias, view_far):
+    """The extractors' view arguments, checked before any launch."""
+    if _min_views(min_views) > 0 and (cameras is None or len(cameras) != 4):
+        raise RuntimeError("scanerf: min_views >= 1 needs cameras=(ks, c2ws, H, W)")
+    if view_bias is not None and not 0.0 < float(view_bias) < float("inf"):
+        raise RuntimeError(f"scanerf: view_bias must be > 0 and finite, got {view_bias!r}")
+    if view_far is not None and not float(view_far) > 0.0:
+        raise RuntimeError(f"scanerf: view_far must be > 0, got {view_far!r}")
+
+
+def default_view_bias(size, n):
+    """Half a lattice spacing (the smallest axis): a surface-nets vertex lies within its cell, its faces within one spacing of it."""
+    return 0.5 * min(_f32_div(size[k], n[k]) for k in range(3))
+
+
+def _cull_extracted(mesh, cameras, min_views, view_bias, view_far, size, n, route, report):
+    if cameras is None or min_views == 0:
+        return mesh
+    ks, c2ws, H, W = cameras
+    sub = {} if report is not None else None
+    mesh = cull_unseen(mesh, ks, c2ws, H, W, min_views=min_views, bias=default_view_bias(size, n) if view_bias is None else float(view_bias),
+                       far=float("inf") if view_far is None else float(view_far), route=_VIEW_ROUTE[route], report=sub)
+    if report is not None:
+        report["cull"] = sub
+    return mesh
+
+
+def vertex_views(mesh, ks, c2ws, H, W, bias, near=0.0, far=float("inf"), want_mask=False, route="fused", log2dim=6):
+    """For every vertex of `mesh` the number of cameras that see it, the mesh itself being the occluder: the tracer is built on the
+    mesh (FastMesh.from_arrays, log2dim) and FastMesh.point_views queries its vertices.  -> (views [V] i32, mask [V, ceil(C/32)] i32 or
+    None).  bias: how far towards the eye a segment starts, so that the vertex's own faces do not hide it (about half an edge)."""
+    if route not in VIEW_ROUTES:
+        raise RuntimeError(f"scanerf: route must be one of {VIEW_ROUTES}, got {route!r}")
+    from .allocation import _cameras
+    from .fastmesh import FastMesh
+    dev_ptr(mesh.vertices, _f32, "vertices")
+    dev_ptr(mesh.faces, _i32, "faces")
+    device = mesh.vertices.device
+    V = int(mesh.vertices.shape[0])
+    if V == 0 or mesh.faces.shape[0] == 0:      # nothing to build a tracer on (and nothing the cull would keep)
+        C = _cameras(ks, c2ws)[0].shape[0]
+        return (torch.zeros(V, dtype=_i32, device=device),
+                torch.zeros((V, (C + 31) // 32), dtype=_i32, device=device) if want_mask else None)
+    fm = FastMesh.from_arrays(mesh.vertices, mesh.faces, device, log2dim=log2dim)
+    return fm.point_views(mesh.vertices, ks, c2ws, H, W, bias, near=near, far=far, want_mask=want_mask, route=route)
+
+
+def cull_by_views(mesh, views, min_views=1, report=None):
+    """The cull rule on given per-vertex view counts [V] (any integer dtype, the mesh's device): a face stays iff at least one of its
+    three vertices has views >= min_views, a vertex stays iff a kept face uses it.  Kept rows stay in their order, the faces' indices
+    are remapped, cells / lattice / normals (where the mesh has them) are gathered row for row: filter_mesh's contract with a per-face
+    rule.  min_views=0 returns the input object.  report: receives vertices / faces (before, after) and views_histogram (entry k: the
+    vertices seen by exactly k cameras).  torch ops (mask, cumsum, gather): it is not the hot path."""
+    min_views = _min_views(min_views)
+    V, F = int(mesh.vertices.shape[0]), int(mesh.faces.shape[0])
+    if not isinstance(views, torch.Tensor) or views.dtype.is_floating_point or tuple(views.shape) != (V,) or views.device != mesh.vertices.device:
+        raise RuntimeError(f"scanerf: views must be an integer tensor [{V}] on {mesh.vertices.device}")
+    if report is not None:
+        report.update(vertices=(V, V), faces=(F, F), views_histogram=torch.bincount(views.to(torch.int64)).tolist() if V else [])
+    if min_views == 0:
+        return mesh
+    f = mesh.faces.to(torch.int64)
+    kf = (views >= min_views)[f].any(1) if F else torch.zeros(0, dtype=torch.bool, device=f.device)
+    kv = torch.zeros(V, dtype=torch.bool, device=f.device)
+    kv[f[kf].reshape(-1)] = True
+    new_index = torch.cumsum(kv, 0) - 1
+    gather = lambda t: None if t is None else t[kv].contiguous()
+    out = Mesh(gather(mesh.vertices), new_index[f[kf]].to(_i32).reshape(-1, 3).contiguous(), gather(mesh.cells), gather(mesh.lattice),
+               gather(mesh.normals))
+    if report is not None:
+        report.update(vertices=(V, int(out.vertices.shape[0])), faces=(F, int(out.faces.shape[0])))
+    return out
+
+
+def cull_unseen(mesh, ks, c2ws, H, W, min_views=1, bias=None, near=0.0, far=float("inf"), log2dim=6, route="fused", report=None):
+    """Drop the parts of a Mesh that fewer than min_views cameras saw (inner shells, undersides, the far side of the capture's border):
+    vertex_views on the mesh itself, then cull_by_views.  bias is required (the extractors pass half a lattice spacing).
+    min_views=0 returns the input object (the views are computed only for a report)."""
+    min_views = _min_views(min_views)
+    if route not in VIEW_ROUTES:
+        raise RuntimeError(f"scanerf: route must be one of {VIEW_ROUTES}, got {route!r}")
+    if bias is None:
+        raise RuntimeError("scanerf: cull_unseen needs bias (about half an edge of the mesh)")
+    if min_views == 0 and report is None:
+        return mesh
+    views, _ = vertex_views(mesh, ks, c2ws, H, W, bias, near=near, far=far, route=route, log2dim=log2dim)
+    return cull_by_views(mesh, views, min_views, report)
 
 
 def cells_per_axis(occ_size, longest):

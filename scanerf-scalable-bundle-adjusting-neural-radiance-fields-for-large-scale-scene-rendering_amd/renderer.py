@@ -286,20 +286,23 @@ class TileSetRenderer:
 
     @torch.no_grad()
     def extract_mesh(self, level, cells_per_axis=256, box=None, route="fused", normals=False, min_faces=0, min_extent=0,
-                     keep_largest=None, report=None):
+                     keep_largest=None, report=None, cameras=None, min_views=0, view_bias=None, view_far=None):
         """ONE mesh of the whole scene: the level set sigma == level of the density this renderer draws, the tiles' densities blended
         per point with the render-time weights (meshing.extract_scene_mesh).  box = (corner, size) of the world box
         the lattice covers (default: scene_box()), with cells_per_axis cells along its longest side.  normals=True: the vertex normals,
         the blended density's own gradient (meshing.scene_sigma_normals_points).  min_faces / min_extent /
         keep_largest: meshing.filter_mesh's keep rule (floaters and unused vertices go), applied before the normals
-        are evaluated; report: a dict that receives the component count and the rows before and after.  -> meshing.Mesh."""
+        are evaluated; report: a dict that receives the component count and the rows before and after.  cameras = (ks, c2ws, H, W)
+        with min_views >= 1: the parts no camera saw go first (meshing.cull_unseen; view_bias: half a lattice spacing
+        by default).  -> meshing.Mesh."""
         from . import meshing
         corner, size = self.scene_box() if box is None else box
         size = [float(v) for v in size]
         return meshing.extract_scene_mesh(self.feature_tables, self.resolution, self.params, self.block_corner, self.block_size,
                                           self.occupied_grid, self.grid_starts, self.grid_log2dim, corner, size,
                                           meshing.cells_per_axis(size, cells_per_axis), level, route=route, normals=normals,
-                                          min_faces=min_faces, min_extent=min_extent, keep_largest=keep_largest, report=report)
+                                          min_faces=min_faces, min_extent=min_extent, keep_largest=keep_largest, report=report,
+                                          cameras=cameras, min_views=min_views, view_bias=view_bias, view_far=view_far)
 
     @torch.no_grad()
     def evaluate_mesh(self, gt, level, cells_per_axis=256, n_samples=200000, thresholds=(0.05,), max_dist=float("inf"), seed=0,

@@ -372,11 +372,13 @@ class TileModel(nn.Module):
 
     # ---- geometry out: the density's level set as a triangle mesh (the reference has none) ------------------------
     @torch.no_grad()
-    def extract_mesh(self, n, level, global_step=None, normals=True, route="fused", min_faces=0, min_extent=0, keep_largest=None):
+    def extract_mesh(self, n, level, global_step=None, normals=True, route="fused", min_faces=0, min_extent=0, keep_largest=None,
+                     cameras=None, min_views=0, view_bias=None, view_far=None):
         """Surface nets over the tile box on a lattice of n = (nx, ny, nz) cells (an int: that many along the longest side, the others
         by the box's aspect), inside = sigma > level -> meshing.Mesh (world-space vertices, faces, cells, lattice, normals).
         global_step: the coarse-to-fine mask of that step; None = no mask, as the normals and the renderer read the table.
-        min_faces / min_extent / keep_largest: meshing.filter_mesh's keep rule, applied before the normals are evaluated."""
+        min_faces / min_extent / keep_largest: meshing.filter_mesh's keep rule, applied before the normals are evaluated.
+        cameras = (ks, c2ws, H, W) with min_views >= 1: the parts no camera saw go before that (meshing.cull_unseen)."""
         from . import meshing
         if self.n_levels != 16:
             raise RuntimeError("scanerf: the mesh extraction needs 16 levels (the reference hard-codes them)")
@@ -385,7 +387,8 @@ class TileModel(nn.Module):
         wf = torch.ones(32, dtype=torch.float32, device=self.device) if global_step is None else self.weight_feature(global_step)
         return meshing.extract_mesh(self.gather_table().detach(), self.resolution, self.decoder.blob().detach().contiguous(), wf,
                                     self.occupied_grid, self.log2dim, self.occ_corner, self.occ_size, n, level, normals=normals, route=route,
-                                    min_faces=min_faces, min_extent=min_extent, keep_largest=keep_largest)
+                                    min_faces=min_faces, min_extent=min_extent, keep_largest=keep_largest,
+                                    cameras=cameras, min_views=min_views, view_bias=view_bias, view_far=view_far)
 
     # ---- optimiser on the table: fused sparse Adam (only touched entries move) --------------
     @torch.no_grad()

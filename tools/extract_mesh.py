@@ -3,6 +3,7 @@
 
     python tools/extract_mesh.py TILEDIR [TILEDIR ...] --level SIGMA [--cells-per-axis 256] [--out DIR] [--normals] [--route fused|dense]
                                  [--gpu 0] [--min-faces N] [--min-extent CELLS] [--keep-largest K]
+                                 [--cameras camera.log --min-views N [--view-bias B] [--view-far D]]
                                  [--compare GT.ply --threshold T [T ...] [--samples N] [--max-dist D] [--log2dim L] [--seed S]]
 
 TILEDIR holds feature.npz and decoder.pth as renderer.export_tile writes and renderer.load_tile reads them.  The lattice covers the
@@ -11,7 +12,9 @@ aspect; the surface is sigma == --level (sigma units, > 0), extracted only where
 formats.write_ply to DIR/<name of TILEDIR>.ply (default: TILEDIR/mesh.ply); --normals stores the tile density's normals at the
 vertices (nx ny nz).  --min-faces / --min-extent / --keep-largest drop floaters and unused vertices by connected component before
 the normals are evaluated (meshing.filter_mesh); the component count and the rows before and after are printed either
-way.  --compare GT.ply prints, after each PLY is written, the geometric score of that tile's mesh against GT.ply as the one JSON line
+way.  --cameras camera.log --min-views N first drops the faces none of whose vertices N of the log's cameras see (the mesh itself
+occluding; meshing.cull_unseen; --view-bias: half a lattice spacing by default, --view-far: the cameras' range).
+--compare GT.ply prints, after each PLY is written, the geometric score of that tile's mesh against GT.ply as the one JSON line
 of tools/compare_meshes.py.  The files read back through formats.read_ply, fastmesh.FastMesh and tools/build_tiles.py.
 
 Tile meshes abut at the faces of their tile boxes, where each is left open, and overlap in the tiles' margins.  Stitching them into
@@ -36,6 +39,10 @@ def parser():
     ap.add_argument("--min-faces", type=int, default=0, help="drop components with fewer faces (1: exactly the unused vertices)")
     ap.add_argument("--min-extent", type=int, default=0, help="drop components whose box of cells is shorter than this on every axis")
     ap.add_argument("--keep-largest", type=int, default=None, metavar="K", help="keep only the K components with the most faces")
+    ap.add_argument("--cameras", default=None, metavar="camera.log", help="the capture's cameras (formats.read_campara): cull what they do not see")
+    ap.add_argument("--min-views", type=int, default=0, metavar="N", help="keep a face iff N cameras see one of its vertices (needs --cameras)")
+    ap.add_argument("--view-bias", type=float, default=None, metavar="B", help="start of a sight line, off the vertex (default: half a lattice spacing)")
+    ap.add_argument("--view-far", type=float, default=None, metavar="D", help="the cameras' range (default: no limit)")
     ap.add_argument("--gpu", type=int, default=0)
     ap.add_argument("--compare", default=None, metavar="GT.ply",
                     help="after writing the PLY, print the geometric score of the mesh against GT.ply as one JSON line (needs --threshold)")
@@ -47,7 +54,7 @@ def parser():
 
 def extract_tile(tile, cells, level, device, route="fused", normals=False, **rules):
     """tile: renderer.load_tile's dict -> meshing.Mesh (normals=True: with the density's normals at the vertices).  rules:
-    meshing.extract_mesh's min_faces / min_extent / keep_largest / report."""
+    meshing.extract_mesh's min_faces / min_extent / keep_largest / report and cameras / min_views / view_bias / view_far."""
     import numpy as np
     import torch
 
@@ -61,19 +68,30 @@ def extract_tile(tile, cells, level, device, route="fused", normals=False, **rul
                                 meshing.cells_per_axis(size.tolist(), cells), level, normals=normals, route=route, **rules)
 
 
+def cull_line(out, cull):
+    """What cull_unseen reported, as one printed line."""
+    hist = cull["views_histogram"]
+    return (f"{out}: unseen parts culled first: vertices {cull['vertices'][0]} -> {cull['vertices'][1]}, faces {cull['faces'][0]} -> "
+            f"{cull['faces'][1]}; {hist[0] if hist else 0} vertices seen by no camera, at most {max(len(hist) - 1, 0)} views")
+
+
 def main(argv=None):
     ap = parser()
     args = ap.parse_args(argv)
     if args.compare and not args.threshold:
         ap.error("--compare needs --threshold")
+    if args.min_views > 0 and not args.cameras:
+        ap.error("--min-views needs --cameras")
     from scanerf_amd import evaluation, formats, renderer
     device = f"cuda:{args.gpu}"
+    view = dict(cameras=formats.read_campara(args.cameras, return_shape=True) if args.cameras else None, min_views=args.min_views,
+                view_bias=args.view_bias, view_far=args.view_far)
     if args.out:
         os.makedirs(args.out, exist_ok=True)
     for path in args.tiles:
         report = {}
         mesh = extract_tile(renderer.load_tile(path), args.cells_per_axis, args.level, device, args.route, args.normals,
-                            min_faces=args.min_faces, min_extent=args.min_extent, keep_largest=args.keep_largest, report=report)
+                            min_faces=args.min_faces, min_extent=args.min_extent, keep_largest=args.keep_largest, report=report, **view)
         name = os.path.basename(os.path.normpath(path))
         out = os.path.join(args.out, name + ".ply") if args.out else os.path.join(path, "mesh.ply")
         formats.write_ply(out, mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy(),
@@ -81,6 +99,8 @@ def main(argv=None):
         print(f"{out}: {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} faces")
         print(f"{out}: {report['components']} components, {report['kept_components']} kept; vertices {report['vertices'][0]} -> "
               f"{report['vertices'][1]}, faces {report['faces'][0]} -> {report['faces'][1]}")
+        if "cull" in report:
+            print(cull_line(out, report["cull"]))
         if args.compare:
             print(evaluation.score_line((mesh.vertices, mesh.faces), args.compare, args, mesh.vertices.device))
     return 0

@@ -4,6 +4,7 @@
     python tools/extract_scene_mesh.py TILEDIR [TILEDIR ...] --level SIGMA [--cells-per-axis 256]
                                        [--box X Y Z SX SY SZ] --out FILE.ply [--normals] [--route fused|dense] [--gpu 0]
                                        [--min-faces N] [--min-extent CELLS] [--keep-largest K]
+                                       [--cameras camera.log --min-views N [--view-bias B] [--view-far D]]
                                        [--compare GT.ply --threshold T [T ...] [--samples N] [--max-dist D] [--log2dim L] [--seed S]]
 
 Every TILEDIR holds feature.npz and decoder.pth as renderer.export_tile writes and renderer.load_tile reads them; together they are
@@ -13,7 +14,9 @@ the faces of the world box.  The lattice covers --box (corner and size in world 
 boxes) with --cells-per-axis cells along its longest side.  --normals stores the vertex normals (nx ny nz): the blended density's own
 gradient, weight terms included.  --min-faces / --min-extent / --keep-largest drop floaters and unused vertices by
 connected component before the normals are evaluated (meshing.filter_mesh); the component count and the rows before
-and after are printed either way.  --compare GT.ply prints, after the PLY is written, the geometric score of the mesh against GT.ply
+and after are printed either way.  --cameras camera.log --min-views N first drops the faces none of whose vertices N of the log's
+cameras see (the mesh itself occluding; meshing.cull_unseen; --view-bias: half a lattice spacing by default,
+--view-far: the cameras' range).  --compare GT.ply prints, after the PLY is written, the geometric score of the mesh against GT.ply
 (e.g. the dataset's scan) as the one JSON line of tools/compare_meshes.py.  tools/extract_mesh.py writes one open mesh per tile instead."""
 import argparse
 import os
@@ -36,6 +39,10 @@ def parser():
     ap.add_argument("--min-faces", type=int, default=0, help="drop components with fewer faces (1: exactly the unused vertices)")
     ap.add_argument("--min-extent", type=int, default=0, help="drop components whose box of cells is shorter than this on every axis")
     ap.add_argument("--keep-largest", type=int, default=None, metavar="K", help="keep only the K components with the most faces")
+    ap.add_argument("--cameras", default=None, metavar="camera.log", help="the capture's cameras (formats.read_campara): cull what they do not see")
+    ap.add_argument("--min-views", type=int, default=0, metavar="N", help="keep a face iff N cameras see one of its vertices (needs --cameras)")
+    ap.add_argument("--view-bias", type=float, default=None, metavar="B", help="start of a sight line, off the vertex (default: half a lattice spacing)")
+    ap.add_argument("--view-far", type=float, default=None, metavar="D", help="the cameras' range (default: no limit)")
     ap.add_argument("--gpu", type=int, default=0)
     ap.add_argument("--compare", default=None, metavar="GT.ply",
                     help="after writing the PLY, print the geometric score of the mesh against GT.ply as one JSON line (needs --threshold)")
@@ -50,12 +57,16 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.compare and not args.threshold:
         ap.error("--compare needs --threshold")
+    if args.min_views > 0 and not args.cameras:
+        ap.error("--min-views needs --cameras")
     from scanerf_amd import evaluation, formats, renderer
     rnd = renderer.TileSetRenderer(f"cuda:{args.gpu}", [renderer.load_tile(p) for p in args.tiles])
     box = None if args.box is None else (args.box[:3], args.box[3:])
     report = {}
+    cameras = formats.read_campara(args.cameras, return_shape=True) if args.cameras else None
     mesh = rnd.extract_mesh(args.level, args.cells_per_axis, box=box, route=args.route, normals=args.normals, min_faces=args.min_faces,
-                            min_extent=args.min_extent, keep_largest=args.keep_largest, report=report)
+                            min_extent=args.min_extent, keep_largest=args.keep_largest, report=report, cameras=cameras,
+                            min_views=args.min_views, view_bias=args.view_bias, view_far=args.view_far)
     out_dir = os.path.dirname(os.path.abspath(args.out))
     os.makedirs(out_dir, exist_ok=True)
     formats.write_ply(args.out, mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy(),
@@ -63,6 +74,10 @@ def main(argv=None):
     print(f"{args.out}: {len(args.tiles)} tiles, {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} faces")
     print(f"{args.out}: {report['components']} components, {report['kept_components']} kept; vertices {report['vertices'][0]} -> "
           f"{report['vertices'][1]}, faces {report['faces'][0]} -> {report['faces'][1]}")
+    if "cull" in report:
+        cull, hist = report["cull"], report["cull"]["views_histogram"]
+        print(f"{args.out}: unseen parts culled first: vertices {cull['vertices'][0]} -> {cull['vertices'][1]}, faces {cull['faces'][0]} -> "
+              f"{cull['faces'][1]}; {hist[0] if hist else 0} vertices seen by no camera, at most {max(len(hist) - 1, 0)} views")
     if args.compare:
         print(evaluation.score_line((mesh.vertices, mesh.faces), args.compare, args, mesh.vertices.device))
     return 0
