@@ -56,6 +56,51 @@ int scanerf_mesh_point_views_counted(const float *points, int N, const float *Ks
                                      const int32_t *cell_faces, const float *scene_info, int log2dim, int32_t *views, uint32_t *mask,
                                      uint64_t *counters, scanerf_stream_t stream);
 
+/* ---- depth-map fusion into a truncated signed distance volume (csrc/tsdf.hip): every lattice point against every
+ *   camera's depth map.  What "mesh what the cameras saw, not the density" needs; the zero set is then cut by
+ *   scanerf_isosurface_*_dense.  The reference has no counterpart; the definition is this comment.
+ *   Inputs: depths [C,H,W] f32, z-depth (what scanerf_compute_ray_forward's rays measure: their camera-z component is 1); Ks [C,9],
+ *     C2Ws [C,12] f32 row-major, read as scanerf_mesh_point_views reads them (fx = K[0], cx = K[2], fy = K[4], cy = K[5]; column k of R
+ *     is (C2W[k], C2W[4 + k], C2W[8 + k]); E = (C2W[3], C2W[7], C2W[11])); origin[3], spacing[3]: HOST arrays; the lattice has
+ *     (nx+1)(ny+1)(nz+1) points, point (i, j, k) at row p = (i (ny+1) + j)(nz+1) + k; trunc in (0, inf); near >= 0; far > near
+ *     (+inf allowed); acc [P,2] f32, interleaved (S, Wt), read AND written.
+ *   Everything below is float32, operation by operation, without FMA contraction.  Lattice point (i0, i1, i2) has the world position
+ *     P_a = origin_a + (float)i_a * spacing_a (two roundings: the dense surface-nets op's vertex placement).
+ *   For camera c = 0 .. C-1, IN THIS ORDER:
+ *     w = P - E;  xc = (w0 R00 + w1 R10) + w2 R20, yc and zc likewise with columns 1 and 2;
+ *     u = fx (xc / zc) + cx,  v = fy (yc / zc) + cy;
+ *     IN VIEW iff zc > near and 0 <= u < (float)W and 0 <= v < (float)H;  px = (int)u, py = (int)v (pixel px covers [px, px + 1));
+ *     D = depths[c][py][px];  VALID iff D is finite and near < D <= far;  sdf = D - zc;
+ *     OBSERVED iff in view and valid and sdf >= -trunc;  term = fminf(1, sdf / trunc);
+ *     for an observed pair: S <- S + term, Wt <- Wt + 1.
+ *   The sums START FROM THE VALUES IN acc: cameras may be fed in batches, and a split into batches gives the bits of one call.
+ *   Each point is owned by one thread; no atomics; acc[p] is read once and written once per call, only for a point some camera
+ *     observed (an unobserved point's row is not written: it would receive the bits it holds); nothing else is written.  Whole
+ *     (block of points, camera) pairs are skipped when the block's bounding sphere lies behind `near` or outside the frustum by a
+ *     margin that covers the float32 rounding of the test above: the skip never changes a bit.
+ *   C == 0 launches nothing.  Refused before any launch (nothing written): null pointers, C < 0, H or W < 1, an n_k < 1, 2^31 or more
+ *     lattice points, trunc not in (0, inf), near negative or NaN, far not > near, a spacing not positive and finite, an origin not
+ *     finite.  No allocation, no host synchronisation; every launch on `stream`.
+ *   scanerf_tsdf_cameras_per_pass: the cameras a workgroup stages on chip per pass; a larger C takes several passes.
+ *   scanerf_tsdf_integrate_counted (measurement): also adds to counters [3] u64, which the caller zeroes: the (point, camera) pairs
+ *     evaluated, the (block, camera) pairs skipped, the updates (observed pairs: the sum of the Wt increments).
+ *   scanerf_tsdf_values: for p < P (P >= 0; 0 launches nothing; min_weight >= 1): observed[p] (u8) = Wt >= min_weight;
+ *     values[p] = observed ? 0.5f - 0.5f * (S / Wt) : 0.  In [0, 1] for sums this op formed; inside iff > 0.5: the level of the
+ *     surface-nets op is 0.5 and its strict `values > level` makes an unobserved point outside.  Every element of both written once.
+ *   scanerf_tsdf_cell_support: cells [V,3] i32 (Mesh.cells: cell (a, b, c) has the corners (a + da, b + db, c + dc), d in {0, 1});
+ *     support[v] (i32) = the number of its 8 corners with observed != 0; a cell outside [0, n_k) on an axis gets 0 and reads nothing.
+ *     V == 0 launches nothing; V < 0, an n_k < 1, 2^31 or more points and null pointers are refused. */
+int scanerf_tsdf_cameras_per_pass(void);
+int scanerf_tsdf_integrate(const float *depths, const float *Ks, const float *C2Ws, int C, int H, int W, const float *origin,
+                           const float *spacing, int nx, int ny, int nz, float trunc, float near, float far, float *acc,
+                           scanerf_stream_t stream);
+int scanerf_tsdf_integrate_counted(const float *depths, const float *Ks, const float *C2Ws, int C, int H, int W, const float *origin,
+                                   const float *spacing, int nx, int ny, int nz, float trunc, float near, float far, float *acc,
+                                   uint64_t *counters, scanerf_stream_t stream);
+int scanerf_tsdf_values(const float *acc, int P, float min_weight, float *values, uint8_t *observed, scanerf_stream_t stream);
+int scanerf_tsdf_cell_support(const uint8_t *observed, int nx, int ny, int nz, const int32_t *cells, int V, int32_t *support,
+                              scanerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,11 @@ TOOL_PROTOTYPES = {
     "scanerf_mesh_point_views_cameras_per_pass": ("I", ""),
     "scanerf_mesh_point_views": ("I", "PIPPIIIFFFPPPPPPPPIPPP"),
     "scanerf_mesh_point_views_counted": ("I", "PIPPIIIFFFPPPPPPPPIPPPP"),
+    "scanerf_tsdf_cameras_per_pass": ("I", ""),
+    "scanerf_tsdf_integrate": ("I", "PPPIIIPPIIIFFFPP"),
+    "scanerf_tsdf_integrate_counted": ("I", "PPPIIIPPIIIFFFPPP"),
+    "scanerf_tsdf_values": ("I", "PIFPPP"),
+    "scanerf_tsdf_cell_support": ("I", "PIIIPIPP"),
 }
 CTYPES = {"P": ctypes.c_void_p, "I": ctypes.c_int, "U": ctypes.c_uint, "F": ctypes.c_float, "Z": ctypes.c_size_t,
           "L": ctypes.c_int64, "S": ctypes.c_char_p}

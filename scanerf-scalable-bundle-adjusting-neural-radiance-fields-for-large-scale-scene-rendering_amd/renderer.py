@@ -314,3 +314,44 @@ class TileSetRenderer:
         mesh = self.extract_mesh(level, cells_per_axis, **extract)
         return evaluation.compare_meshes((mesh.vertices, mesh.faces), gt, n_samples, thresholds, max_dist=max_dist, seed=seed,
                                          log2dim=log2dim, return_distances=return_distances, device=mesh.vertices.device)
+
+    @torch.no_grad()
+    def fuse_mesh(self, cameras, cells_per_axis=256, box=None, trunc=None, max_transparency=0.5, scale=1, views_per_batch=8,
+                  min_weight=1, min_faces=0, min_extent=0, keep_largest=None, report=None, **render_kw):
+        """ONE mesh of what the cameras saw (fusion.py): cameras = (ks [C,3,3], c2ws [C,3,4], H, W), typically the
+        capture's.  Each camera is rendered at H // scale x W // scale (K scaled as fusion.scale_cameras does; render_kw goes to
+        render), its depth set to 0 where the transparency exceeds max_transparency or the depth is not finite (fusion.mask_depth),
+        and the maps are fused views_per_batch at a time (never more of them are held) into a TSDF volume over box = (corner, size)
+        (default: scene_box()) with cells_per_axis cells along its longest side; trunc: 4 x the largest spacing by default.  Then
+        TSDFVolume.extract: the zero set, the support cull, filter_mesh's rules.  -> meshing.Mesh (no normals)."""
+        from . import fusion, meshing
+        if cameras is None or len(cameras) != 4:
+            raise RuntimeError("scanerf: fuse_mesh needs cameras=(ks, c2ws, H, W)")
+        ks, c2ws, H, W = cameras
+        scale = fusion._positive_int(scale, "scale")
+        vpb = fusion._views_per_batch(views_per_batch)
+        H, W = fusion._positive_int(H, "H"), fusion._positive_int(W, "W")
+        h, w = H // scale, W // scale
+        if h < 1 or w < 1:
+            raise RuntimeError(f"scanerf: H={H} W={W} leave no pixel at scale={scale}")
+        if not 0.0 <= float(max_transparency) <= 1.0:
+            raise RuntimeError(f"scanerf: max_transparency must lie in [0, 1], got {max_transparency!r}")
+        fusion._min_weight(min_weight)
+        meshing._rules(min_faces, min_extent, keep_largest, True)
+        ks = fusion.scale_cameras(ks, scale)
+        c2ws = torch.as_tensor(c2ws).to(torch.float32)
+        if c2ws.dim() != 3 or c2ws.shape[0] != ks.shape[0] or c2ws.shape[1] < 3 or c2ws.shape[2] != 4:
+            raise RuntimeError(f"scanerf: c2ws must be [C,3,4] (or [C,4,4]) with C={ks.shape[0]}, got {tuple(c2ws.shape)}")
+        corner, size = self.scene_box() if box is None else box
+        size = [float(v) for v in size]
+        n = meshing.cells_per_axis(size, cells_per_axis)
+        spacing = fusion.lattice_spacing(size, n)
+        vol = fusion.TSDFVolume([float(v) for v in corner], spacing, n, fusion.default_trunc(spacing) if trunc is None else trunc,
+                                self.device)
+        for i in range(0, int(ks.shape[0]), vpb):
+            maps = []
+            for c in range(i, min(i + vpb, int(ks.shape[0]))):
+                _, _, depth, transp = self.render(h, w, ks[c], c2ws[c], **render_kw)[:4]
+                maps.append(fusion.mask_depth(depth[..., 0], transp[..., 0], float(max_transparency)))
+            vol.integrate(torch.stack(maps).contiguous(), ks[i:i + vpb], c2ws[i:i + vpb])
+        return vol.extract(min_weight, min_faces, min_extent, keep_largest, report)

@@ -1,0 +1,78 @@
+#!/usr/bin/env python3
+"""ONE mesh of a tiled scene from what its cameras saw: depth maps rendered at the capture's cameras, fused into a truncated signed
+distance volume, the zero set written as a PLY.
+
+    python tools/fuse_mesh.py TILEDIR [TILEDIR ...] --cameras camera.log --out FILE.ply [--cells-per-axis 256]
+                              [--box X Y Z SX SY SZ] [--trunc T] [--min-weight N] [--scale S] [--max-transparency A]
+                              [--views-per-batch B] [--min-faces N] [--min-extent CELLS] [--keep-largest K] [--gpu 0]
+                              [--compare GT.ply --threshold T [T ...] [--samples N] [--max-dist D] [--log2dim L] [--seed S]]
+
+Every TILEDIR holds feature.npz and decoder.pth as renderer.export_tile writes and renderer.load_tile reads them.  Each camera of
+camera.log (formats.read_campara) is rendered at 1 / --scale of its size; a pixel whose ray kept more than --max-transparency of its
+transmittance has no depth.  The maps are fused --views-per-batch at a time over --box (default: the bounding box of the tiles' render
+boxes) with --cells-per-axis cells along its longest side; --trunc: the truncation distance in world units (default: 4 x the largest
+lattice spacing); a lattice point counts as observed after --min-weight observations.  No level to pick: the surface is the volume's
+zero set, in world units; what no ray stopped at never enters it.  Faces that touch a cell with an unobserved corner are dropped
+(fusion.support_cull), then --min-faces / --min-extent / --keep-largest drop components (meshing.filter_mesh).
+--compare GT.ply prints the geometric score against GT.ply as the one JSON line of tools/compare_meshes.py.
+tools/extract_scene_mesh.py cuts the density's level set instead."""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def parser():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("tiles", metavar="TILEDIR", nargs="+", help="directories with feature.npz and decoder.pth: the tiles of one scene")
+    ap.add_argument("--cameras", required=True, metavar="camera.log", help="the capture's cameras (formats.read_campara)")
+    ap.add_argument("--out", required=True, metavar="FILE.ply")
+    ap.add_argument("--cells-per-axis", type=int, default=256, help="lattice cells along the world box's longest side")
+    ap.add_argument("--box", type=float, nargs=6, default=None, metavar=("X", "Y", "Z", "SX", "SY", "SZ"),
+                    help="world box of the lattice: corner and size (default: the bounding box of the tiles' render boxes)")
+    ap.add_argument("--trunc", type=float, default=None, help="truncation distance, world units (default: 4 x the largest lattice spacing)")
+    ap.add_argument("--min-weight", type=int, default=1, help="observations a lattice point needs to count as observed")
+    ap.add_argument("--scale", type=int, default=1, help="render the cameras at 1 / scale of their size")
+    ap.add_argument("--max-transparency", type=float, default=0.5, help="a ray that kept more of its transmittance has no depth")
+    ap.add_argument("--views-per-batch", type=int, default=8, help="depth maps held at a time")
+    ap.add_argument("--min-faces", type=int, default=0, help="drop components with fewer faces (1: exactly the unused vertices)")
+    ap.add_argument("--min-extent", type=int, default=0, help="drop components whose box of cells is shorter than this on every axis")
+    ap.add_argument("--keep-largest", type=int, default=None, metavar="K", help="keep only the K components with the most faces")
+    ap.add_argument("--gpu", type=int, default=0)
+    ap.add_argument("--compare", default=None, metavar="GT.ply",
+                    help="after writing the PLY, print the geometric score of the mesh against GT.ply as one JSON line (needs --threshold)")
+    import scanerf_amd  # noqa: F401
+    from scanerf_amd import evaluation
+    evaluation.add_score_arguments(ap, required=False)
+    return ap
+
+
+def main(argv=None):
+    ap = parser()
+    args = ap.parse_args(argv)
+    if args.compare and not args.threshold:
+        ap.error("--compare needs --threshold")
+    from scanerf_amd import evaluation, formats, renderer
+    rnd = renderer.TileSetRenderer(f"cuda:{args.gpu}", [renderer.load_tile(p) for p in args.tiles])
+    box = None if args.box is None else (args.box[:3], args.box[3:])
+    report = {}
+    cameras = formats.read_campara(args.cameras, return_shape=True)
+    mesh = rnd.fuse_mesh(cameras, args.cells_per_axis, box=box, trunc=args.trunc, max_transparency=args.max_transparency, scale=args.scale,
+                         views_per_batch=args.views_per_batch, min_weight=args.min_weight, min_faces=args.min_faces,
+                         min_extent=args.min_extent, keep_largest=args.keep_largest, report=report)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    formats.write_ply(args.out, mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy())
+    sup = report["support"]
+    print(f"{args.out}: {len(args.tiles)} tiles, {len(cameras[0])} cameras, {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} faces")
+    print(f"{args.out}: support cull: vertices {sup['vertices'][0]} -> {sup['vertices'][1]}, faces {sup['faces'][0]} -> {sup['faces'][1]}")
+    print(f"{args.out}: {report['components']} components, {report['kept_components']} kept; vertices {report['vertices'][0]} -> "
+          f"{report['vertices'][1]}, faces {report['faces'][0]} -> {report['faces'][1]}")
+    if args.compare:
+        print(evaluation.score_line((mesh.vertices, mesh.faces), args.compare, args, mesh.vertices.device))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
