@@ -89,7 +89,29 @@ int scanerf_mesh_point_views_counted(const float *points, int N, const float *Ks
  *     surface-nets op is 0.5 and its strict `values > level` makes an unobserved point outside.  Every element of both written once.
  *   scanerf_tsdf_cell_support: cells [V,3] i32 (Mesh.cells: cell (a, b, c) has the corners (a + da, b + db, c + dc), d in {0, 1});
  *     support[v] (i32) = the number of its 8 corners with observed != 0; a cell outside [0, n_k) on an axis gets 0 and reads nothing.
- *     V == 0 launches nothing; V < 0, an n_k < 1, 2^31 or more points and null pointers are refused. */
+ *     V == 0 launches nothing; V < 0, an n_k < 1, 2^31 or more points and null pointers are refused.
+ *   COLOUR.  scanerf_tsdf_integrate_color: the above, every word of it, and beside it colors [C,H,W,3] f32 (the
+ *     cameras' images, pixel for pixel with depths) and cacc [P,4] f32, interleaved (R, G, B, Wc), read AND written, 16-byte aligned;
+ *     row p of cacc is row p of acc.  For camera c, in order, for a pair that is OBSERVED by the rule above:
+ *       COLOURED iff sdf <= trunc and the three channels of colors[c][py][px] are finite;
+ *       for a coloured pair: R <- R + r, G <- G + g, B <- B + b, Wc <- Wc + 1.
+ *     The channels are summed as they are (no clamp).  An observed pair with sdf > trunc is free space in front of whatever the
+ *     pixel shows: its colour belongs to a surface further away and is left out.  The sums start from the values in cacc (a batch
+ *     split gives the bits of one call); one thread owns the point, no atomics; cacc[p] is loaded once as one 16-byte word and
+ *     stored once, only for a point some camera coloured; acc receives exactly the bits scanerf_tsdf_integrate gives it.  A skipped
+ *     (block, camera) pair is not in view, so the skip never changes a bit of cacc either.  Refused before any launch as above,
+ *     and: a null colors or cacc, a cacc that is not 16-byte aligned.  C == 0 launches nothing.
+ *   scanerf_tsdf_integrate_color_counted (measurement): counters [4] u64; the first three as scanerf_tsdf_integrate_counted's, the
+ *     fourth the coloured pairs (the sum of the Wc increments).
+ *   scanerf_tsdf_vertex_colors: the colour of mesh vertices from cacc.  cells [V,3] i32 (Mesh.cells), lattice [V,3] f32 (Mesh.lattice:
+ *     the vertex in lattice units), rgb [V,3] f32 and weight [V] f32 written, every element once.  float32, operation by operation:
+ *       t_a = fminf(fmaxf(lattice_a - (float)cell_a, 0), 1);  per axis the corner weights (1 - t_a, t_a);
+ *       corner d = 0 .. 7 has the offsets (d >> 2, (d >> 1) & 1, d & 1) (scanerf_tsdf_cell_support's order), the row q_d and the
+ *       weight w_d = (wx * wy) * wz;  num_k and den = the sums of w_d * cacc[q_d][k] for k = R, G, B and Wc, accumulated in ascending
+ *       d starting from the d = 0 product;  weight[v] = den;  rgb[v][k] = den > 0 ? num_k / den : 0.
+ *     Sums and weight are interpolated, then divided: a corner nobody coloured drops out by itself.  A cell outside [0, n_k) on an
+ *     axis gets rgb = 0, weight = 0 and reads nothing.  V == 0 launches nothing; V < 0, an n_k < 1, 2^31 or more points, null
+ *     pointers and a cacc that is not 16-byte aligned are refused. */
 int scanerf_tsdf_cameras_per_pass(void);
 int scanerf_tsdf_integrate(const float *depths, const float *Ks, const float *C2Ws, int C, int H, int W, const float *origin,
                            const float *spacing, int nx, int ny, int nz, float trunc, float near, float far, float *acc,
@@ -100,6 +122,15 @@ int scanerf_tsdf_integrate_counted(const float *depths, const float *Ks, const f
 int scanerf_tsdf_values(const float *acc, int P, float min_weight, float *values, uint8_t *observed, scanerf_stream_t stream);
 int scanerf_tsdf_cell_support(const uint8_t *observed, int nx, int ny, int nz, const int32_t *cells, int V, int32_t *support,
                               scanerf_stream_t stream);
+int scanerf_tsdf_integrate_color(const float *depths, const float *colors, const float *Ks, const float *C2Ws, int C, int H, int W,
+                                 const float *origin, const float *spacing, int nx, int ny, int nz, float trunc, float near, float far,
+                                 float *acc, float *cacc, scanerf_stream_t stream);
+int scanerf_tsdf_integrate_color_counted(const float *depths, const float *colors, const float *Ks, const float *C2Ws, int C, int H,
+                                         int W, const float *origin, const float *spacing, int nx, int ny, int nz, float trunc,
+                                         float near, float far, float *acc, float *cacc, uint64_t *counters,
+                                         scanerf_stream_t stream);
+int scanerf_tsdf_vertex_colors(const float *cacc, int nx, int ny, int nz, const int32_t *cells, const float *lattice, int V,
+                               float *rgb, float *weight, scanerf_stream_t stream);
 
 #ifdef __cplusplus
 }

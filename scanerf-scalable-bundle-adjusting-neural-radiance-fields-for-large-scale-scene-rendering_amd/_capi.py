@@ -140,6 +140,9 @@ TOOL_PROTOTYPES = {
     "scanerf_tsdf_integrate_counted": ("I", "PPPIIIPPIIIFFFPPP"),
     "scanerf_tsdf_values": ("I", "PIFPPP"),
     "scanerf_tsdf_cell_support": ("I", "PIIIPIPP"),
+    "scanerf_tsdf_integrate_color": ("I", "PPPPIIIPPIIIFFFPPP"),
+    "scanerf_tsdf_integrate_color_counted": ("I", "PPPPIIIPPIIIFFFPPPP"),
+    "scanerf_tsdf_vertex_colors": ("I", "PIIIPPIPPP"),
 }
 CTYPES = {"P": ctypes.c_void_p, "I": ctypes.c_int, "U": ctypes.c_uint, "F": ctypes.c_float, "Z": ctypes.c_size_t,
           "L": ctypes.c_int64, "S": ctypes.c_char_p}

@@ -7,6 +7,12 @@
 // neighbouring pixels; the four wavefronts are the block's (x, y) columns.  Each thread owns ONE point for all cameras: (S, Wt) live
 // in two registers from one load to at most one store, no atomics.
 //
+// COLOUR: k_tsdf_integrate<COUNT, true> also owns the point's (R, G, B, Wc) of cacc [P,4], one 16-byte load, four
+// registers, at most one 16-byte store.  An observed pair with sdf <= trunc whose pixel of colors [C,H,W,3] is finite in all three
+// channels adds the pixel to them: the three gathers happen only for such a pair (a free-space pair, sdf > trunc, shows a surface
+// further away).  <COUNT, false> is the kernel of 4.20, instruction for instruction.  k_tsdf_vertex_colors reads the sums back at a
+// mesh vertex: the eight corners of its cell weighted trilinearly, sums and weight interpolated separately, then one division.
+//
 // The camera loop runs inside the kernel, in passes of kCamsPerPass.  Per pass the workgroup copies the cameras' 21 floats into the
 // LDS (coalesced), then thread t decides whether camera t can be skipped for the whole block, then every thread walks the cameras in
 // ascending order; the 21 floats are wave-uniform LDS reads (one address per instruction: a broadcast).
@@ -73,15 +79,17 @@ __device__ __forceinline__ bool skip_camera(const float *cam, const float c[3], 
     return false;
 }
 
-template <bool COUNT>
+template <bool COUNT, bool COLOR>
 __global__ void __launch_bounds__(kThreads) k_tsdf_integrate(const float *__restrict__ depths, const float *__restrict__ Ks,
                                                              const float *__restrict__ C2Ws, int C, int H, int W, Lattice L, int tiles_y,
                                                              int tiles_z, float trunc, float near, float far, float2 *__restrict__ acc,
-                                                             unsigned long long *__restrict__ counters)
+                                                             unsigned long long *__restrict__ counters,
+                                                             const float *__restrict__ colors, float4 *__restrict__ cacc)
 {
+    constexpr int kTally = COLOR ? 4 : 3;
     __shared__ float cams[kCamsPerPass * kCamFloats];
     __shared__ int skip[kCamsPerPass];
-    __shared__ unsigned long long tally[3];
+    __shared__ unsigned long long tally[kTally];
 
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kWave);
@@ -113,9 +121,14 @@ __global__ void __launch_bounds__(kThreads) k_tsdf_integrate(const float *__rest
     float2 sw = make_float2(0.0f, 0.0f);
     if (live) sw = acc[p];
     bool touched = false;
-    unsigned long long n_pairs = 0, n_updates = 0, n_skipped = 0;
+    float4 cw = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    bool coloured = false;
+    if (COLOR) {
+        if (live) cw = cacc[p];
+    }
+    unsigned long long n_pairs = 0, n_updates = 0, n_skipped = 0, n_coloured = 0;
     if (COUNT) {
-        if (threadIdx.x < 3) tally[threadIdx.x] = 0ull;
+        if (threadIdx.x < kTally) tally[threadIdx.x] = 0ull;
     }
 
     for (int cbase = 0; cbase < C; cbase += kCamsPerPass) {
@@ -142,7 +155,8 @@ __global__ void __launch_bounds__(kThreads) k_tsdf_integrate(const float *__rest
             if (COUNT) n_pairs += live ? 1ull : 0ull;
             if (inview) {
                 const int px = (int)u, py = (int)v;   // 0 <= px < W, 0 <= py < H by the test above
-                const float D = depths[((size_t)(cbase + cc) * (size_t)H + (size_t)py) * (size_t)W + (size_t)px];
+                const size_t pixel = ((size_t)(cbase + cc) * (size_t)H + (size_t)py) * (size_t)W + (size_t)px;
+                const float D = depths[pixel];
                 const bool valid = D > ninf && D < pinf && D > near && D <= far;
                 const float sdf = D - zc;
                 if (valid && sdf >= -trunc) {
@@ -150,18 +164,36 @@ __global__ void __launch_bounds__(kThreads) k_tsdf_integrate(const float *__rest
                     sw.y = sw.y + 1.0f;
                     touched = true;
                     if (COUNT) ++n_updates;
+                    if (COLOR) {
+                        if (sdf <= trunc) {   // in the band: the pixel shows THIS surface (pixel < C H W: in bounds of colors)
+                            const float *rgb = colors + 3 * pixel;
+                            const float r = rgb[0], g = rgb[1], b = rgb[2];
+                            if (r > ninf && r < pinf && g > ninf && g < pinf && b > ninf && b < pinf) {
+                                cw.x = cw.x + r;
+                                cw.y = cw.y + g;
+                                cw.z = cw.z + b;
+                                cw.w = cw.w + 1.0f;
+                                coloured = true;
+                                if (COUNT) ++n_coloured;
+                            }
+                        }
+                    }
                 }
             }
         }
     }
     if (touched) acc[p] = sw;
+    if (COLOR) {
+        if (coloured) cacc[p] = cw;
+    }
     if (COUNT) {
         __syncthreads();
         atomicAdd(&tally[0], n_pairs);
         atomicAdd(&tally[2], n_updates);
+        if (COLOR) atomicAdd(&tally[3], n_coloured);
         if (threadIdx.x == 0) atomicAdd(&tally[1], n_skipped);
         __syncthreads();
-        if (threadIdx.x < 3) atomicAdd(&counters[threadIdx.x], tally[threadIdx.x]);
+        if (threadIdx.x < kTally) atomicAdd(&counters[threadIdx.x], tally[threadIdx.x]);
     }
 }
 
@@ -194,6 +226,47 @@ __global__ void __launch_bounds__(kThreads) k_tsdf_cell_support(const uint8_t *_
     }
 }
 
+// one thread per vertex: the (R, G, B, Wc) of the eight corners of its cell, weighted trilinearly; see the header for the order
+__global__ void __launch_bounds__(kThreads) k_tsdf_vertex_colors(const float4 *__restrict__ cacc, int nx, int ny, int nz,
+                                                                 const int32_t *__restrict__ cells, const float *__restrict__ lattice, int V,
+                                                                 float *__restrict__ rgb, float *__restrict__ weight)
+{
+    for (int64_t v = (int64_t)blockIdx.x * kThreads + threadIdx.x; v < V; v += (int64_t)gridDim.x * kThreads) {
+        const int a = cells[3 * v], b = cells[3 * v + 1], c = cells[3 * v + 2];
+        float4 sum = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (a >= 0 && a < nx && b >= 0 && b < ny && c >= 0 && c < nz) {
+            const int cell[3] = { a, b, c };
+            float w[3][2];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float t = fminf(fmaxf(lattice[3 * v + k] - (float)cell[k], 0.0f), 1.0f);
+                w[k][0] = 1.0f - t;
+                w[k][1] = t;
+            }
+#pragma unroll
+            for (int d = 0; d < 8; ++d) {
+                const size_t q = ((size_t)(a + (d >> 2)) * (size_t)(ny + 1) + (size_t)(b + ((d >> 1) & 1))) * (size_t)(nz + 1) +
+                                 (size_t)(c + (d & 1));
+                const float wd = (w[0][d >> 2] * w[1][(d >> 1) & 1]) * w[2][d & 1];
+                const float4 s = cacc[q];
+                if (d == 0) {
+                    sum = make_float4(wd * s.x, wd * s.y, wd * s.z, wd * s.w);
+                } else {
+                    sum.x = sum.x + wd * s.x;
+                    sum.y = sum.y + wd * s.y;
+                    sum.z = sum.z + wd * s.z;
+                    sum.w = sum.w + wd * s.w;
+                }
+            }
+        }
+        const bool any = sum.w > 0.0f;
+        rgb[3 * v] = any ? sum.x / sum.w : 0.0f;
+        rgb[3 * v + 1] = any ? sum.y / sum.w : 0.0f;
+        rgb[3 * v + 2] = any ? sum.z / sum.w : 0.0f;
+        weight[v] = sum.w;
+    }
+}
+
 bool lattice_ok(int nx, int ny, int nz)      // fewer than 2^31 lattice points (every n_k >= 1)
 {
     const int64_t xy = ((int64_t)nx + 1) * ((int64_t)ny + 1);
@@ -202,7 +275,7 @@ bool lattice_ok(int nx, int ny, int nz)      // fewer than 2^31 lattice points (
 
 int integrate(const char *what, const float *depths, const float *Ks, const float *C2Ws, int C, int H, int W, const float *origin,
               const float *spacing, int nx, int ny, int nz, float trunc, float near, float far, float *acc, uint64_t *counters,
-              bool count, scanerf_stream_t stream)
+              bool count, scanerf_stream_t stream, const float *colors = nullptr, float *cacc = nullptr, bool color = false)
 {
     const float inf = __builtin_huge_valf();
     SCANERF_REQUIRE(C >= 0, "%s: C=%d (negative size)", what, C);
@@ -213,6 +286,8 @@ int integrate(const char *what, const float *depths, const float *Ks, const floa
     SCANERF_REQUIRE(near >= 0.0f, "%s: near=%g (must be >= 0)", what, (double)near);
     SCANERF_REQUIRE(far > near, "%s: far=%g (must be > near=%g; +inf for no limit)", what, (double)far, (double)near);
     SCANERF_REQUIRE(depths && Ks && C2Ws && origin && spacing && acc && (!count || counters), "%s: null pointer", what);
+    SCANERF_REQUIRE(!color || (colors && cacc), "%s: null pointer", what);
+    SCANERF_REQUIRE(!color || ((uintptr_t)cacc & 15) == 0, "%s: cacc must be 16-byte aligned (it is loaded and stored as float4)", what);
     Lattice L;
     for (int a = 0; a < 3; ++a) {
         SCANERF_REQUIRE(spacing[a] > 0.0f && spacing[a] < inf, "%s: spacing[%d]=%g (must be > 0 and finite)", what, a, (double)spacing[a]);
@@ -228,10 +303,18 @@ int integrate(const char *what, const float *depths, const float *Ks, const floa
     hipStream_t st = (hipStream_t)stream;
     unsigned long long *ctr = reinterpret_cast<unsigned long long *>(counters);
     float2 *a2 = reinterpret_cast<float2 *>(acc);
-    if (count)
-        hipLaunchKernelGGL((k_tsdf_integrate<true>), grid, block, 0, st, depths, Ks, C2Ws, C, H, W, L, tiles_y, tiles_z, trunc, near, far, a2, ctr);
-    else
-        hipLaunchKernelGGL((k_tsdf_integrate<false>), grid, block, 0, st, depths, Ks, C2Ws, C, H, W, L, tiles_y, tiles_z, trunc, near, far, a2, ctr);
+    float4 *c4 = reinterpret_cast<float4 *>(cacc);
+#define SCANERF_TSDF_LAUNCH(COUNT, COLOR)                                                                                                  \
+    hipLaunchKernelGGL((k_tsdf_integrate<COUNT, COLOR>), grid, block, 0, st, depths, Ks, C2Ws, C, H, W, L, tiles_y, tiles_z, trunc, near, \
+                       far, a2, ctr, colors, c4)
+    if (color) {
+        if (count) SCANERF_TSDF_LAUNCH(true, true);
+        else SCANERF_TSDF_LAUNCH(false, true);
+    } else {
+        if (count) SCANERF_TSDF_LAUNCH(true, false);
+        else SCANERF_TSDF_LAUNCH(false, false);
+    }
+#undef SCANERF_TSDF_LAUNCH
     return check_launch(what);
 }
 
@@ -252,6 +335,23 @@ SCANERF_API int scanerf_tsdf_integrate_counted(const float *depths, const float 
 {
     return integrate("tsdf_integrate_counted", depths, Ks, C2Ws, C, H, W, origin, spacing, nx, ny, nz, trunc, near, far, acc, counters, true,
                      stream);
+}
+
+SCANERF_API int scanerf_tsdf_integrate_color(const float *depths, const float *colors, const float *Ks, const float *C2Ws, int C, int H, int W,
+                                             const float *origin, const float *spacing, int nx, int ny, int nz, float trunc, float near,
+                                             float far, float *acc, float *cacc, scanerf_stream_t stream)
+{
+    return integrate("tsdf_integrate_color", depths, Ks, C2Ws, C, H, W, origin, spacing, nx, ny, nz, trunc, near, far, acc, nullptr, false,
+                     stream, colors, cacc, true);
+}
+
+SCANERF_API int scanerf_tsdf_integrate_color_counted(const float *depths, const float *colors, const float *Ks, const float *C2Ws, int C, int H,
+                                                     int W, const float *origin, const float *spacing, int nx, int ny, int nz, float trunc,
+                                                     float near, float far, float *acc, float *cacc, uint64_t *counters,
+                                                     scanerf_stream_t stream)
+{
+    return integrate("tsdf_integrate_color_counted", depths, Ks, C2Ws, C, H, W, origin, spacing, nx, ny, nz, trunc, near, far, acc, counters,
+                     true, stream, colors, cacc, true);
 }
 
 SCANERF_API int scanerf_tsdf_values(const float *acc, int P, float min_weight, float *values, uint8_t *observed, scanerf_stream_t stream)
@@ -276,4 +376,18 @@ SCANERF_API int scanerf_tsdf_cell_support(const uint8_t *observed, int nx, int n
     hipLaunchKernelGGL(k_tsdf_cell_support, dim3(stream_grid(V, kThreads)), dim3(kThreads), 0, (hipStream_t)stream, observed, nx, ny, nz,
                        cells, V, support);
     return check_launch("tsdf_cell_support");
+}
+
+SCANERF_API int scanerf_tsdf_vertex_colors(const float *cacc, int nx, int ny, int nz, const int32_t *cells, const float *lattice, int V,
+                                           float *rgb, float *weight, scanerf_stream_t stream)
+{
+    SCANERF_REQUIRE(V >= 0, "tsdf_vertex_colors: V=%d (negative size)", V);
+    SCANERF_REQUIRE(nx >= 1 && ny >= 1 && nz >= 1, "tsdf_vertex_colors: n=(%d, %d, %d) (every n_k must be >= 1)", nx, ny, nz);
+    SCANERF_REQUIRE(lattice_ok(nx, ny, nz), "tsdf_vertex_colors: n=(%d, %d, %d) has 2^31 or more lattice points", nx, ny, nz);
+    if (V == 0) return 0;
+    SCANERF_REQUIRE(cacc && cells && lattice && rgb && weight, "tsdf_vertex_colors: null pointer");
+    SCANERF_REQUIRE(((uintptr_t)cacc & 15) == 0, "tsdf_vertex_colors: cacc must be 16-byte aligned (it is loaded as float4)");
+    hipLaunchKernelGGL(k_tsdf_vertex_colors, dim3(stream_grid(V, kThreads)), dim3(kThreads), 0, (hipStream_t)stream,
+                       reinterpret_cast<const float4 *>(cacc), nx, ny, nz, cells, lattice, V, rgb, weight);
+    return check_launch("tsdf_vertex_colors");
 }

@@ -168,11 +168,12 @@ _PLY_TYPES = {"char": "i1", "uchar": "u1", "short": "i2", "ushort": "u2", "int":
               "float32": "f4", "float64": "f8"}
 
 
-def read_ply(path, normals=False):
+def read_ply(path, normals=False, colors=False):
     """Triangle mesh from an ascii or binary_little_endian PLY -> (vertices [V,3] f32, faces [F,3] i32).
     Reads what plyIO.h's read_plyFile reads: vertex x/y/z and the face list property (vertex_indices /
     vertex_index); other vertex properties are skipped, faces must be triangles.  normals=True: the vertex properties nx/ny/nz as a
-    third array [V,3] f32 (the file must hold them)."""
+    third array [V,3] f32 (the file must hold them).  colors=True: the vertex properties red/green/blue as a last array [V,3] u8
+    (the file must hold them, as uchar)."""
     with open(path, "rb") as f:
         if f.readline().strip() != b"ply":
             raise ValueError(f"{path}: not a PLY file")
@@ -194,8 +195,8 @@ def read_ply(path, normals=False):
                 break
         if fmt not in ("ascii", "binary_little_endian"):
             raise ValueError(f"{path}: unsupported PLY format {fmt}")
-        verts = faces = nrm = None
-        want = "xyz" if not normals else ("x", "y", "z", "nx", "ny", "nz")
+        verts = faces = nrm = rgb = None
+        want = ("x", "y", "z") + (("nx", "ny", "nz") if normals else ()) + (("red", "green", "blue") if colors else ())
         if fmt == "ascii":
             rows = f.read().decode("ascii", "replace").split("\n")
             pos = 0
@@ -211,6 +212,10 @@ def read_ply(path, normals=False):
                         verts = np.stack([data["x"], data["y"], data["z"]], 1).astype(np.float32).reshape(-1, 3)
                         if normals:
                             nrm = np.stack([data["nx"], data["ny"], data["nz"]], 1).astype(np.float32).reshape(-1, 3)
+                        if colors:
+                            if any(data.dtype[c] != np.uint8 for c in ("red", "green", "blue")):
+                                raise ValueError(f"{path}: red / green / blue must be uchar")
+                            rgb = np.stack([data["red"], data["green"], data["blue"]], 1).astype(np.uint8).reshape(-1, 3)
                 else:
                     out = []
                     for _ in range(e["count"]):
@@ -239,6 +244,11 @@ def read_ply(path, normals=False):
                     if normals:
                         ix = [names.index(c) for c in ("nx", "ny", "nz")]
                         nrm = np.array([[float(r[i]) for i in ix] for r in chunk], np.float32).reshape(-1, 3)
+                    if colors:
+                        if any(_PLY_TYPES[p[1]] != "u1" for p in e["props"] if p[2] in ("red", "green", "blue")):
+                            raise ValueError(f"{path}: red / green / blue must be uchar")
+                        ix = [names.index(c) for c in ("red", "green", "blue")]
+                        rgb = np.array([[int(r[i]) for i in ix] for r in chunk], np.uint8).reshape(-1, 3)
                 elif e["name"] == "face":
                     faces = []
                     for r in chunk:
@@ -257,31 +267,57 @@ def read_ply(path, normals=False):
     if any(fc is None or len(fc) != 3 for fc in faces):
         raise ValueError(f"{path}: only triangle faces are supported")
     faces = np.asarray(faces, np.int32).reshape(-1, 3)
-    return (verts, faces, nrm) if normals else (verts, faces)
+    return (verts, faces) + ((nrm,) if normals else ()) + ((rgb,) if colors else ())
 
 
-def write_ply(path, vertices, faces, binary=True, normals=None):
-    """vertices [V,3] f32, faces [F,3] i32 -> a PLY read_ply reads; normals [V,3]: stored as nx / ny / nz behind x / y / z."""
+def quantize_colors(colors):
+    """[V,3] floats in [0, 1] -> [V,3] u8: floor(clamp(c, 0, 1) * 255 + 0.5), in float64; a non-finite value is refused."""
+    c = np.asarray(colors, np.float64)
+    if not np.isfinite(c).all():
+        raise ValueError("colors hold a value that is not finite")
+    return np.floor(np.clip(c, 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+
+
+def write_ply(path, vertices, faces, binary=True, normals=None, colors=None):
+    """vertices [V,3] f32, faces [F,3] i32 -> a PLY read_ply reads; normals [V,3]: stored as nx / ny / nz behind x / y / z;
+    colors [V,3] floats in [0, 1]: stored as uchar red / green / blue behind those, floor(clamp(c, 0, 1) * 255 + 0.5)
+    (quantize_colors; a non-finite colour is refused, before the file is opened)."""
     vertices, faces = np.asarray(vertices, np.float32), np.asarray(faces, np.int32)
+    rgb = None
+    if colors is not None:
+        if np.shape(colors) != vertices.shape:
+            raise ValueError(f"{path}: colors {np.shape(colors)} do not match vertices {vertices.shape}")
+        try:
+            rgb = quantize_colors(colors).reshape(-1, 3)
+        except ValueError as e:
+            raise ValueError(f"{path}: {e}") from None
     if normals is not None:
         normals = np.asarray(normals, np.float32)
         if normals.shape != vertices.shape:
             raise ValueError(f"{path}: normals {normals.shape} do not match vertices {vertices.shape}")
         vertices = np.concatenate([vertices.reshape(-1, 3), normals.reshape(-1, 3)], 1)
-    hdr = ("ply\nformat %s 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n%s"
+    hdr = ("ply\nformat %s 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n%s%s"
            "element face %d\nproperty list uchar int vertex_indices\nend_header\n") % (
                "binary_little_endian" if binary else "ascii", len(vertices),
-               "" if normals is None else "property float nx\nproperty float ny\nproperty float nz\n", len(faces))
+               "" if normals is None else "property float nx\nproperty float ny\nproperty float nz\n",
+               "" if rgb is None else "property uchar red\nproperty uchar green\nproperty uchar blue\n", len(faces))
     with open(path, "wb") as f:
         f.write(hdr.encode("ascii"))
         if binary:
-            f.write(np.ascontiguousarray(vertices).astype("<f4").tobytes())
+            if rgb is None:
+                f.write(np.ascontiguousarray(vertices).astype("<f4").tobytes())
+            else:
+                rows = vertices.reshape(len(rgb), -1)
+                rec = np.zeros(len(rgb), dtype=[("v", "<f4", (rows.shape[1],)), ("c", "u1", (3,))])
+                rec["v"], rec["c"] = rows, rgb
+                f.write(rec.tobytes())
             rec = np.zeros(len(faces), dtype=[("n", "u1"), ("i", "<i4", (3,))])
             rec["n"], rec["i"] = 3, faces
             f.write(rec.tobytes())
         else:
-            for v in vertices:
-                f.write((" ".join("%r" % float(x) for x in v) + "\n").encode("ascii"))
+            for i, v in enumerate(vertices):
+                tail = "" if rgb is None else " %d %d %d" % tuple(int(x) for x in rgb[i])
+                f.write((" ".join("%r" % float(x) for x in v) + tail + "\n").encode("ascii"))
             for t in faces:
                 f.write(("3 %d %d %d\n" % (t[0], t[1], t[2])).encode("ascii"))
 

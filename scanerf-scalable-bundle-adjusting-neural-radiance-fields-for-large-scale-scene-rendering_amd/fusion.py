@@ -7,9 +7,12 @@ the dense surface-nets op.  The reference has no counterpart; the definition is 
                                                       witness: one eager float32 torch op per operation of the definition, no skip
         .values(min_weight)                           the value lattice in [0, 1] (inside > 0.5) and which points were observed
         .extract(min_weight, ...)                     surface_nets at 0.5 -> cell_support -> support_cull -> filter_mesh's rules
+    TSDFVolume(..., color=True)                       also owns cacc [P,4] = (R, G, B, Wc): integrate(..., colors=)
+                                                      sums the images' pixels in the same launch, vertex_colors(mesh) reads them
+                                                      back at a mesh's vertices, extract(colors=True) -> (mesh, rgb)
     support_cull(mesh, support)                       a face stays iff all three vertices have support 8
-    fuse_depth_maps(depths, ks, c2ws, box, n, ...)    the above in one call, the cameras fed in batches
-    mask_depth / scale_cameras                        what TileSetRenderer.fuse_mesh does to its renders and cameras
+    fuse_depth_maps(depths, ks, c2ws, box, n, ...)    the above in one call, the cameras fed in batches; colors= [C,H,W,3] -> (mesh, rgb)
+    mask_depth / scale_cameras / clamped_image        what TileSetRenderer.fuse_mesh does to its renders and cameras
 
 Depth is z-depth (compute_ray_forward's rays have camera-z component 1, so TileSetRenderer.render's and FastMesh.render_depth's
 depth is); 0 marks a pixel without depth.  No CPU path."""
@@ -61,10 +64,29 @@ def _depth_maps(depths, ks, c2ws, device):
     return depths.detach().contiguous(), k9, c12, C, H, W
 
 
+def _color_maps(colors, depths):
+    """The checks of a batch of images against its depth maps -> colors [C,H,W,3] f32, contiguous."""
+    want = (*depths.shape, 3)
+    if not isinstance(colors, torch.Tensor) or colors.dtype != _f32 or tuple(colors.shape) != want:
+        raise RuntimeError(f"scanerf: colors must be a {list(want)} float32 tensor (the depth maps' cameras and pixels)"
+                           + (f", got {tuple(colors.shape)} {colors.dtype}" if isinstance(colors, torch.Tensor) else ""))
+    if colors.device != depths.device:
+        raise RuntimeError(f"scanerf: colors live on {colors.device}, depths on {depths.device}")
+    return colors.detach().contiguous()
+
+
+def _fill(fill):
+    if isinstance(fill, bool) or not isinstance(fill, (int, float, np.integer, np.floating)) or not math.isfinite(fill):
+        raise RuntimeError(f"scanerf: fill must be a finite number, got {fill!r}")
+    return float(fill)
+
+
 class TSDFVolume:
-    def __init__(self, origin, spacing, n, trunc, device):
+    def __init__(self, origin, spacing, n, trunc, device, color=False):
         """A lattice of n = (nx, ny, nz) cells, point (i, j, k) at origin + float(index) * spacing (the dense surface-nets op's vertex
-        placement, so its vertices and these points share a frame); trunc: the truncation distance in world units."""
+        placement, so its vertices and these points share a frame); trunc: the truncation distance in world units.  color=True: the
+        volume also sums colours, in cacc [P,4] = (R, G, B, Wc) zeros: 16 bytes per lattice point beside acc's 8 (0.87 GB at a
+        512 x 205 x 512 lattice); integrate then needs colors=."""
         self.n = [int(v) for v in meshing._lattice_size(n)]
         self.origin, self.spacing = meshing._host3(origin, "origin"), meshing._host3(spacing, "spacing")
         if not all(v >= 1 for v in self.n):
@@ -80,7 +102,10 @@ class TSDFVolume:
         if not 0.0 < self.trunc < math.inf:
             raise RuntimeError(f"scanerf: trunc must be > 0 and finite, got {trunc!r}")
         self.device = torch.device(device)
+        if not isinstance(color, (bool, np.bool_)):
+            raise RuntimeError(f"scanerf: color must be True or False, got {color!r}")
         self.acc = torch.zeros((self.points, 2), dtype=_f32, device=self.device)
+        self.cacc = torch.zeros((self.points, 4), dtype=_f32, device=self.device) if color else None
 
     @property
     def shape(self):
@@ -88,15 +113,21 @@ class TSDFVolume:
 
     # ---- integration ------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def integrate(self, depths, ks, c2ws, near=0.0, far=math.inf, route="fused", counters=None):
+    def integrate(self, depths, ks, c2ws, near=0.0, far=math.inf, route="fused", counters=None, colors=None):
         """Add the cameras' observations to acc, camera by camera in their order: depths [C,H,W] f32 z-depth on the GPU, ks [C,3,3],
         c2ws [C,3,4] (arrays or tensors).  A pixel counts iff its depth is finite and near < depth <= far (0 marks "no depth").
         The sums start from what acc holds: feeding the cameras in batches gives the bits of one call.  counters: a zeroed
-        [3] int64 GPU tensor that receives (pairs evaluated, (block, camera) pairs skipped, updates): the measurement entry."""
+        [3] int64 GPU tensor that receives (pairs evaluated, (block, camera) pairs skipped, updates): the measurement entry.
+        A volume with colour needs colors [C,H,W,3] f32 (any other volume refuses them): an observed pair with sdf <= trunc and a
+        finite pixel adds the pixel, unclamped, to cacc (R, G, B) and 1 to Wc, in the same launch; acc gets the same bits either way;
+        counters is then [4], the fourth the coloured pairs."""
         if route not in ROUTES:
             raise RuntimeError(f"scanerf: route must be one of {ROUTES}, got {route!r}")
         near, far = _range(near, far)
         d, k9, c12, C, H, W = _depth_maps(depths, ks, c2ws, self.device)
+        if (colors is None) != (self.cacc is None):
+            raise RuntimeError("scanerf: a volume with colour (color=True) needs colors=, a volume without takes none")
+        col = None if colors is None else _color_maps(colors, d)
         acc = dev_ptr(self.acc, _f32, "acc")
         dp = dev_ptr(d, _f32, "depths")
         if d.device != self.acc.device:
@@ -106,7 +137,18 @@ class TSDFVolume:
         if route == "composed":
             if counters is not None:
                 raise RuntimeError("scanerf: counters belong to the fused route")
-            self._integrate_composed(d, k9, c12, H, W, near, far)
+            self._integrate_composed(d, k9, c12, H, W, near, far, col)
+            return self
+        if col is not None:
+            head = (dp, dev_ptr(col, _f32, "colors"), k9.data_ptr(), c12.data_ptr(), C, H, W, self.origin, self.spacing, *self.n,
+                    self.trunc, near, far, acc, dev_ptr(self.cacc, _f32, "cacc"))
+            if counters is None:
+                check(tool("scanerf_tsdf_integrate_color")(*head, stream()), "tsdf_integrate_color")
+            else:
+                if tuple(counters.shape) != (4,):
+                    raise RuntimeError("scanerf: counters must be a [4] int64 tensor (a volume with colour)")
+                check(tool("scanerf_tsdf_integrate_color_counted")(*head, dev_ptr(counters, torch.int64, "counters"), stream()),
+                      "tsdf_integrate_color_counted")
             return self
         head = (dp, k9.data_ptr(), c12.data_ptr(), C, H, W, self.origin, self.spacing, *self.n, self.trunc, near, far, acc)
         if counters is None:
@@ -125,14 +167,15 @@ class TSDFVolume:
         axes = [scalar(self.origin[k]) + torch.arange(self.n[k] + 1, device=dev, dtype=_f32) * scalar(self.spacing[k]) for k in range(3)]
         return torch.stack(torch.meshgrid(*axes, indexing="ij"), -1).reshape(-1, 3).contiguous()
 
-    def _integrate_composed(self, depths, k9, c12, H, W, near, far):
+    def _integrate_composed(self, depths, k9, c12, H, W, near, far, colors=None):
         """The witness: the definition of include/scanerf_mesh_tools_hip.h, every operation one eager float32 torch op, one camera at a
-        time, every point against every camera (no skip)."""
+        time, every point against every camera (no skip); with colors, the colour rule beside it."""
         dev = self.acc.device
         scalar = lambda v: torch.tensor(v, dtype=_f32, device=dev)
         near, far, trunc, Hf, Wf, one = scalar(near), scalar(far), scalar(self.trunc), scalar(float(H)), scalar(float(W)), scalar(1.0)
         P = self.lattice_points()
         S, Wt = self.acc[:, 0].clone(), self.acc[:, 1].clone()
+        RGB, Wc = (self.cacc[:, :3].clone(), self.cacc[:, 3].clone()) if colors is not None else (None, None)
         for c in range(k9.shape[0]):
             K, T = k9[c], c12[c]
             w0, w1, w2 = P[:, 0] - T[3], P[:, 1] - T[7], P[:, 2] - T[11]
@@ -153,8 +196,17 @@ class TSDFVolume:
             term = torch.minimum(one, sdf[observed] / trunc)
             S[at] = S[at] + term
             Wt[at] = Wt[at] + one
+            if colors is not None:
+                pix = colors[c][py[observed], px[observed]]
+                coloured = (sdf[observed] <= trunc) & torch.isfinite(pix).all(1)
+                ct = at[coloured]
+                RGB[ct] = RGB[ct] + pix[coloured]
+                Wc[ct] = Wc[ct] + one
         self.acc[:, 0] = S
         self.acc[:, 1] = Wt
+        if colors is not None:
+            self.cacc[:, :3] = RGB
+            self.cacc[:, 3] = Wc
 
     # ---- the value lattice and the mesh ---------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -184,9 +236,41 @@ class TSDFVolume:
         return support
 
     @torch.no_grad()
-    def extract(self, min_weight=1, min_faces=0, min_extent=0, keep_largest=None, report=None):
+    def vertex_colors(self, mesh, fill=0.5):
+        """The colours of a mesh's vertices (a volume with colour; the mesh from this volume's lattice, with cells and lattice) ->
+        (rgb [V,3] f32, weight [V] f32): the sums and Wc of the eight corners of each vertex's cell interpolated trilinearly at
+        mesh.lattice, then rgb = sums / weight.  A vertex with weight 0 (no corner of its cell was coloured) gets `fill` in all
+        three channels.  The values are the means of what was integrated: unclamped images give unclamped colours."""
+        fill = _fill(fill)
+        if self.cacc is None:
+            raise RuntimeError("scanerf: vertex_colors needs a volume with colour (color=True)")
+        if getattr(mesh, "cells", None) is None or getattr(mesh, "lattice", None) is None:
+            raise RuntimeError("scanerf: vertex_colors needs mesh.cells and mesh.lattice (a mesh of this volume's lattice)")
+        cacc = dev_ptr(self.cacc, _f32, "cacc")
+        cp, lp = dev_ptr(mesh.cells, _i32, "cells"), dev_ptr(mesh.lattice, _f32, "lattice")
+        V = int(mesh.cells.shape[0])
+        if mesh.cells.dim() != 2 or mesh.cells.shape[1] != 3 or tuple(mesh.lattice.shape) != (V, 3):
+            raise RuntimeError(f"scanerf: cells and lattice must be [V,3], got {tuple(mesh.cells.shape)} and {tuple(mesh.lattice.shape)}")
+        if mesh.cells.device != self.cacc.device or mesh.lattice.device != self.cacc.device:
+            raise RuntimeError(f"scanerf: the mesh lives on {mesh.cells.device}, the volume on {self.cacc.device}")
+        rgb = torch.empty((V, 3), dtype=_f32, device=self.cacc.device)
+        weight = torch.empty((V,), dtype=_f32, device=self.cacc.device)
+        if V:
+            check(tool("scanerf_tsdf_vertex_colors")(cacc, *self.n, cp, lp, V, rgb.data_ptr(), weight.data_ptr(), stream()),
+                  "tsdf_vertex_colors")
+            rgb[weight == 0] = fill
+        return rgb, weight
+
+    @torch.no_grad()
+    def extract(self, min_weight=1, min_faces=0, min_extent=0, keep_largest=None, report=None, colors=False):
         """The fused surface: surface_nets(values, 0.5) -> cell_support -> support_cull -> filter_mesh's three rules.  -> meshing.Mesh
-        (no normals).  report: a dict that receives support_cull's rows under "support" and the component filter's."""
+        (no normals).  report: a dict that receives support_cull's rows under "support" and the component filter's.
+        colors=True (a volume with colour): -> (mesh, rgb [V,3] f32), vertex_colors on the FINAL mesh, after the support cull and the
+        component filter; report["color"] receives the number of vertices no camera coloured (they hold vertex_colors' fill)."""
+        if not isinstance(colors, (bool, np.bool_)):
+            raise RuntimeError(f"scanerf: colors must be True or False, got {colors!r}")
+        if colors and self.cacc is None:
+            raise RuntimeError("scanerf: extract(colors=True) needs a volume with colour (color=True)")
         min_weight = _min_weight(min_weight)
         meshing._rules(min_faces, min_extent, keep_largest, True)
         values, observed = self.values(min_weight)
@@ -195,7 +279,13 @@ class TSDFVolume:
         mesh = support_cull(mesh, self.cell_support(observed, mesh.cells), sub)
         if report is not None:
             report["support"] = sub
-        return meshing._filter(mesh, min_faces, min_extent, keep_largest, "fused", False, report)
+        mesh = meshing._filter(mesh, min_faces, min_extent, keep_largest, "fused", False, report)
+        if not colors:
+            return mesh
+        rgb, weight = self.vertex_colors(mesh)
+        if report is not None:
+            report["color"] = int((weight == 0).sum())
+        return mesh, rgb
 
 
 def support_cull(mesh, support, report=None):
@@ -236,10 +326,11 @@ def _views_per_batch(v):
 
 
 def fuse_depth_maps(depths, ks, c2ws, box_corner, box_size, n, trunc=None, views_per_batch=8, near=0.0, far=math.inf, min_weight=1,
-                    min_faces=0, min_extent=0, keep_largest=None, report=None):
+                    min_faces=0, min_extent=0, keep_largest=None, report=None, colors=None):
     """Depth maps [C,H,W] f32 (z-depth, 0 = no depth) of the cameras ks / c2ws -> the Mesh of what they saw, on a lattice of n cells
     over the world box box_corner / box_size.  trunc: default_trunc of the spacing.  The cameras are integrated views_per_batch at a
-    time (the same bits for every batch size).  The rest: TSDFVolume.extract."""
+    time (the same bits for every batch size).  The rest: TSDFVolume.extract.  colors [C,H,W,3] f32 (the cameras' images, values in
+    [0, 1] for a PLY): -> (mesh, rgb [V,3] f32), the mesh the one of the call without colours."""
     vpb = _views_per_batch(views_per_batch)
     n = meshing._lattice_size(n)
     corner, size = meshing._host3(box_corner, "box_corner"), meshing._host3(box_size, "box_size")
@@ -253,11 +344,14 @@ def fuse_depth_maps(depths, ks, c2ws, box_corner, box_size, n, trunc=None, views
     near, far = _range(near, far)
     if not isinstance(depths, torch.Tensor) or depths.dim() != 3:
         raise RuntimeError("scanerf: depths must be a [C,H,W] float32 tensor")
-    vol = TSDFVolume(list(corner), spacing, n, default_trunc(spacing) if trunc is None else trunc, depths.device)
+    if colors is not None and (not isinstance(colors, torch.Tensor) or colors.dim() != 4 or colors.shape[0] != depths.shape[0]):
+        raise RuntimeError("scanerf: colors must be a [C,H,W,3] float32 tensor, one image per depth map")
+    vol = TSDFVolume(list(corner), spacing, n, default_trunc(spacing) if trunc is None else trunc, depths.device, color=colors is not None)
     ks, c2ws = torch.as_tensor(ks), torch.as_tensor(c2ws)
     for i in range(0, int(depths.shape[0]), vpb):
-        vol.integrate(depths[i:i + vpb], ks[i:i + vpb], c2ws[i:i + vpb], near=near, far=far)
-    return vol.extract(min_weight, min_faces, min_extent, keep_largest, report)
+        vol.integrate(depths[i:i + vpb], ks[i:i + vpb], c2ws[i:i + vpb], near=near, far=far,
+                      colors=None if colors is None else colors[i:i + vpb])
+    return vol.extract(min_weight, min_faces, min_extent, keep_largest, report, colors=colors is not None)
 
 
 # ---- what TileSetRenderer.fuse_mesh does to its cameras and renders ---------------------------------------------------------------
@@ -279,3 +373,10 @@ def mask_depth(depth, transparency, max_transparency):
     bad = (transparency > max_transparency) | ~torch.isfinite(depth)
     return torch.where(bad, torch.zeros_like(depth), depth)
 
+
+
+def clamped_image(diffuse, specular=None):
+    """The image fuse_mesh integrates: clamp(diffuse, 0, 1) (colors="diffuse") or clamp(diffuse + specular, 0, 1) (colors="rgb"), one
+    float32 addition and one clamp per channel.  A NaN stays a NaN: the integration leaves such a pixel out."""
+    image = diffuse if specular is None else diffuse + specular
+    return torch.clamp(image.to(_f32), 0.0, 1.0)

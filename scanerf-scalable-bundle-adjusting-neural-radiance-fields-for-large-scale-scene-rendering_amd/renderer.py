@@ -317,14 +317,19 @@ class TileSetRenderer:
 
     @torch.no_grad()
     def fuse_mesh(self, cameras, cells_per_axis=256, box=None, trunc=None, max_transparency=0.5, scale=1, views_per_batch=8,
-                  min_weight=1, min_faces=0, min_extent=0, keep_largest=None, report=None, **render_kw):
+                  min_weight=1, min_faces=0, min_extent=0, keep_largest=None, report=None, colors=None, **render_kw):
         """ONE mesh of what the cameras saw (fusion.py): cameras = (ks [C,3,3], c2ws [C,3,4], H, W), typically the
         capture's.  Each camera is rendered at H // scale x W // scale (K scaled as fusion.scale_cameras does; render_kw goes to
         render), its depth set to 0 where the transparency exceeds max_transparency or the depth is not finite (fusion.mask_depth),
         and the maps are fused views_per_batch at a time (never more of them are held) into a TSDF volume over box = (corner, size)
         (default: scene_box()) with cells_per_axis cells along its longest side; trunc: 4 x the largest spacing by default.  Then
-        TSDFVolume.extract: the zero set, the support cull, filter_mesh's rules.  -> meshing.Mesh (no normals)."""
+        TSDFVolume.extract: the zero set, the support cull, filter_mesh's rules.  -> meshing.Mesh (no normals).
+        colors: "diffuse" also fuses clamp(diffuse, 0, 1) of the same renders (the view-independent part: the
+        sensible colour of a mesh), "rgb" clamp(diffuse + specular, 0, 1) (the image shown everywhere else), batched with the depth
+        maps; -> (mesh, rgb [V,3] f32), the mesh the one of the call without colours.  None: no colour, the Mesh alone."""
         from . import fusion, meshing
+        if colors not in (None, "diffuse", "rgb"):
+            raise RuntimeError(f"scanerf: colors must be None, 'diffuse' or 'rgb', got {colors!r}")
         if cameras is None or len(cameras) != 4:
             raise RuntimeError("scanerf: fuse_mesh needs cameras=(ks, c2ws, H, W)")
         ks, c2ws, H, W = cameras
@@ -347,11 +352,14 @@ class TileSetRenderer:
         n = meshing.cells_per_axis(size, cells_per_axis)
         spacing = fusion.lattice_spacing(size, n)
         vol = fusion.TSDFVolume([float(v) for v in corner], spacing, n, fusion.default_trunc(spacing) if trunc is None else trunc,
-                                self.device)
+                                self.device, color=colors is not None)
         for i in range(0, int(ks.shape[0]), vpb):
-            maps = []
+            maps, images = [], []
             for c in range(i, min(i + vpb, int(ks.shape[0]))):
-                _, _, depth, transp = self.render(h, w, ks[c], c2ws[c], **render_kw)[:4]
+                diffuse, specular, depth, transp = self.render(h, w, ks[c], c2ws[c], **render_kw)[:4]
                 maps.append(fusion.mask_depth(depth[..., 0], transp[..., 0], float(max_transparency)))
-            vol.integrate(torch.stack(maps).contiguous(), ks[i:i + vpb], c2ws[i:i + vpb])
-        return vol.extract(min_weight, min_faces, min_extent, keep_largest, report)
+                if colors is not None:
+                    images.append(fusion.clamped_image(diffuse, specular if colors == "rgb" else None))
+            vol.integrate(torch.stack(maps).contiguous(), ks[i:i + vpb], c2ws[i:i + vpb],
+                          colors=torch.stack(images).contiguous() if colors is not None else None)
+        return vol.extract(min_weight, min_faces, min_extent, keep_largest, report, colors=colors is not None)
