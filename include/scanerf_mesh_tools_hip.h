@@ -111,7 +111,29 @@ int scanerf_mesh_point_views_counted(const float *points, int N, const float *Ks
  *       d starting from the d = 0 product;  weight[v] = den;  rgb[v][k] = den > 0 ? num_k / den : 0.
  *     Sums and weight are interpolated, then divided: a corner nobody coloured drops out by itself.  A cell outside [0, n_k) on an
  *     axis gets rgb = 0, weight = 0 and reads nothing.  V == 0 launches nothing; V < 0, an n_k < 1, 2^31 or more points, null
- *     pointers and a cacc that is not 16-byte aligned are refused. */
+ *     pointers and a cacc that is not 16-byte aligned are refused.
+ *   NORMALS.  scanerf_tsdf_vertex_normals: the volume's own gradient at mesh vertices.  values [P] f32 and
+ *     observed [P] u8: what scanerf_tsdf_values wrote (min_weight is already in observed); spacing[3]: a HOST array; cells [V,3] i32,
+ *     lattice [V,3] f32 as scanerf_tsdf_vertex_colors takes them; normal [V,3] f32 and grad [V,3] f32 written, every element once.
+ *     float32, operation by operation, without FMA contraction; division and sqrtf correctly rounded.
+ *     THE GRADIENT AT A LATTICE POINT q, per axis a with h_a = spacing[a] and e_a the unit step of the axis:
+ *       has+ iff q + e_a is inside the lattice and observed;  has- iff q - e_a is inside the lattice and observed;
+ *       g_a(q) = (val[q + e_a] - val[q - e_a]) / (h_a + h_a)   with both,
+ *                (val[q + e_a] - val[q]) / h_a                 with has+ alone,
+ *                (val[q] - val[q - e_a]) / h_a                 with has- alone,
+ *                0                                             with neither.
+ *     AT A VERTEX: t_a, the corner order and the corner weights w_d = (wx * wy) * wz exactly as scanerf_tsdf_vertex_colors forms them;
+ *       G_a = the sum of w_d * g_a(q_d), accumulated in ascending d starting from the d = 0 product, each component by itself;
+ *       len = sqrtf((Gx * Gx + Gy * Gy) + Gz * Gz);  normal_a = (-G_a) / (len + 1e-8f);  grad_a = G_a.
+ *     Values are higher inside, so -G points out, as the faces of the surface-nets op are wound (the convention of
+ *     scanerf_scene_sigma_normals_points).  A zero G gives the normal (-0) / 1e-8f = -0 in every component.
+ *     A vertex whose cell lies outside [0, n_k) on an axis, or whose cell has a corner with observed == 0, gets normal = grad = +0:
+ *     an out-of-range cell reads nothing, an unobserved corner's value is a placeholder, not a distance.  (Where all 8 corners are
+ *     observed every corner has a neighbour inside the cell on every axis, so no evaluated stencil takes the "neither" branch.)
+ *     One thread owns one vertex; the 32 distinct lattice points of a cell's stencil (8 corners, 8 more beyond them per axis) are
+ *     loaded once each; neither values nor observed is written.  Refused before any launch (nothing written): null pointers, V < 0,
+ *     an n_k < 1, 2^31 or more lattice points, a spacing not positive and finite.  V == 0 (with valid pointers) launches nothing.
+ *     No allocation, no host synchronisation; the launch goes on `stream`. */
 int scanerf_tsdf_cameras_per_pass(void);
 int scanerf_tsdf_integrate(const float *depths, const float *Ks, const float *C2Ws, int C, int H, int W, const float *origin,
                            const float *spacing, int nx, int ny, int nz, float trunc, float near, float far, float *acc,
@@ -131,6 +153,9 @@ int scanerf_tsdf_integrate_color_counted(const float *depths, const float *color
                                          scanerf_stream_t stream);
 int scanerf_tsdf_vertex_colors(const float *cacc, int nx, int ny, int nz, const int32_t *cells, const float *lattice, int V,
                                float *rgb, float *weight, scanerf_stream_t stream);
+int scanerf_tsdf_vertex_normals(const float *values, const uint8_t *observed, int nx, int ny, int nz, const float *spacing,
+                                const int32_t *cells, const float *lattice, int V, float *normal, float *grad,
+                                scanerf_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,8 @@ Layout (mirrors the reference's operator surface for this path, nothing else):
   meshing.py       level-set mesh extraction (surface nets over a tile's density, or over a tile set's blended density; no reference counterpart) on csrc/isosurface.hip
   evaluation.py    geometric evaluation of a mesh against another (surface samples, exact point-to-mesh distances, chamfer / F-score; no reference counterpart) on csrc/mesh_distance.hip
   fusion.py        a mesh fused from rendered depth (TSDF volume over depth maps, zero set by surface nets; no reference counterpart) on csrc/tsdf.hip,
-                   with vertex colours on request (the renders' images summed by the same kernel, read out at the vertices)
+                   with vertex colours on request (the renders' images summed by the same kernel, read out at the vertices) and vertex
+                   normals on request (the volume's own gradient at the vertices)
   csrc/            HIP kernels + the C ABI (include/scanerf_hip.h) -> lib/libscanerf_hip.so
 
 The directory name is not a Python identifier; import it through the `scanerf_amd`

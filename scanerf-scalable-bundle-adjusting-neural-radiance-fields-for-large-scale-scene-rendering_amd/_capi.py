@@ -143,6 +143,7 @@ TOOL_PROTOTYPES = {
     "scanerf_tsdf_integrate_color": ("I", "PPPPIIIPPIIIFFFPPP"),
     "scanerf_tsdf_integrate_color_counted": ("I", "PPPPIIIPPIIIFFFPPPP"),
     "scanerf_tsdf_vertex_colors": ("I", "PIIIPPIPPP"),
+    "scanerf_tsdf_vertex_normals": ("I", "PPIIIPPPIPPP"),
 }
 CTYPES = {"P": ctypes.c_void_p, "I": ctypes.c_int, "U": ctypes.c_uint, "F": ctypes.c_float, "Z": ctypes.c_size_t,
           "L": ctypes.c_int64, "S": ctypes.c_char_p}

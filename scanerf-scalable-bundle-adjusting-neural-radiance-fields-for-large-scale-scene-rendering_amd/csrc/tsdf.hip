@@ -13,6 +13,10 @@
 // further away).  <COUNT, false> is the kernel of 4.20, instruction for instruction.  k_tsdf_vertex_colors reads the sums back at a
 // mesh vertex: the eight corners of its cell weighted trilinearly, sums and weight interpolated separately, then one division.
 //
+// NORMALS: k_tsdf_vertex_normals reads the value lattice back at a mesh vertex: per corner of its cell and per axis the
+// difference of the observed neighbours' values (central, or one-sided where a neighbour is missing), weighted trilinearly; -G
+// normalised is the normal.  One thread per vertex, the 32 points of the stencil loaded once each; see the kernel.
+//
 // The camera loop runs inside the kernel, in passes of kCamsPerPass.  Per pass the workgroup copies the cameras' 21 floats into the
 // LDS (coalesced), then thread t decides whether camera t can be skipped for the whole block, then every thread walks the cameras in
 // ascending order; the 21 floats are wave-uniform LDS reads (one address per instruction: a broadcast).
@@ -267,6 +271,83 @@ __global__ void __launch_bounds__(kThreads) k_tsdf_vertex_colors(const float4 *_
     }
 }
 
+// one thread per vertex: the volume's own gradient at the vertex; see the header for the definition.  The stencil of a
+// cell is 32 distinct lattice points: its 8 corners and, per axis, the 8 points one step beyond them.  Each is loaded once.  Along an
+// axis the 8 corners form 4 lines (m, p0, p1, pp): p0 and p1 are corners, m and pp the points beyond.  A vertex is evaluated only when
+// all 8 corners are observed, so p0 always has its + neighbour (p1) and p1 its - neighbour (p0): the definition's "neither" branch
+// cannot arise here, and both one-sided forms are (val[p1] - val[p0]) / h.  What is left to decide per line is whether m and pp exist
+// (inside the lattice and observed).  The loads beyond the cell use a clamped row (the corner's own) where the point is outside, so
+// every load is in bounds and none sits behind a branch; numerator and denominator are selected, then divided once: the operations of
+// the definition, one division per corner and axis.
+__global__ void __launch_bounds__(kThreads) k_tsdf_vertex_normals(const float *__restrict__ values, const uint8_t *__restrict__ observed,
+                                                                  int nx, int ny, int nz, float hx, float hy, float hz,
+                                                                  const int32_t *__restrict__ cells, const float *__restrict__ lattice, int V,
+                                                                  float *__restrict__ normal, float *__restrict__ grad)
+{
+    for (int64_t v = (int64_t)blockIdx.x * kThreads + threadIdx.x; v < V; v += (int64_t)gridDim.x * kThreads) {
+        const int cell[3] = { cells[3 * v], cells[3 * v + 1], cells[3 * v + 2] };
+        const int n[3] = { nx, ny, nz };
+        const size_t stride[3] = { (size_t)(ny + 1) * (size_t)(nz + 1), (size_t)(nz + 1), 1 };
+        float G[3] = { 0.0f, 0.0f, 0.0f }, N[3] = { 0.0f, 0.0f, 0.0f };
+        bool ok = cell[0] >= 0 && cell[0] < nx && cell[1] >= 0 && cell[1] < ny && cell[2] >= 0 && cell[2] < nz;
+        size_t q[8];
+        if (ok) {
+            const size_t q0 = (size_t)cell[0] * stride[0] + (size_t)cell[1] * stride[1] + (size_t)cell[2];
+            int seen = 0;
+#pragma unroll
+            for (int d = 0; d < 8; ++d) {
+                q[d] = q0 + (size_t)(d >> 2) * stride[0] + (size_t)((d >> 1) & 1) * stride[1] + (size_t)(d & 1);
+                seen += observed[q[d]] != 0 ? 1 : 0;
+            }
+            ok = seen == 8;
+        }
+        if (ok) {
+            const float h[3] = { hx, hy, hz };
+            float val[8], w[3][2], wd[8];
+#pragma unroll
+            for (int d = 0; d < 8; ++d) val[d] = values[q[d]];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float t = fminf(fmaxf(lattice[3 * v + k] - (float)cell[k], 0.0f), 1.0f);
+                w[k][0] = 1.0f - t;
+                w[k][1] = t;
+            }
+#pragma unroll
+            for (int d = 0; d < 8; ++d) wd[d] = (w[0][d >> 2] * w[1][(d >> 1) & 1]) * w[2][d & 1];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int bit = 4 >> k;                                      // the corner bit of axis k: (d >> 2, (d >> 1) & 1, d & 1)
+                const bool lo = cell[k] >= 1, hi = cell[k] + 2 <= n[k];      // do m = p0 - e_k and pp = p1 + e_k lie inside the lattice?
+                const float h2 = h[k] + h[k];
+                float g[8];
+#pragma unroll
+                for (int d0 = 0; d0 < 8; ++d0) {
+                    if (d0 & bit) continue;
+                    const int d1 = d0 | bit;
+                    const size_t qm = lo ? q[d0] - stride[k] : q[d0], qp = hi ? q[d1] + stride[k] : q[d1];
+                    const bool has_m = lo && observed[qm] != 0, has_p = hi && observed[qp] != 0;
+                    const float vm = values[qm], vp = values[qp];
+                    g[d0] = (val[d1] - (has_m ? vm : val[d0])) / (has_m ? h2 : h[k]);
+                    g[d1] = ((has_p ? vp : val[d1]) - val[d0]) / (has_p ? h2 : h[k]);
+                }
+                float s = wd[0] * g[0];
+#pragma unroll
+                for (int d = 1; d < 8; ++d) s = s + wd[d] * g[d];
+                G[k] = s;
+            }
+            const float len = sqrtf((G[0] * G[0] + G[1] * G[1]) + G[2] * G[2]);
+            const float den = len + 1e-8f;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) N[k] = (-G[k]) / den;
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            normal[3 * v + k] = N[k];
+            grad[3 * v + k] = G[k];
+        }
+    }
+}
+
 bool lattice_ok(int nx, int ny, int nz)      // fewer than 2^31 lattice points (every n_k >= 1)
 {
     const int64_t xy = ((int64_t)nx + 1) * ((int64_t)ny + 1);
@@ -390,4 +471,22 @@ SCANERF_API int scanerf_tsdf_vertex_colors(const float *cacc, int nx, int ny, in
     hipLaunchKernelGGL(k_tsdf_vertex_colors, dim3(stream_grid(V, kThreads)), dim3(kThreads), 0, (hipStream_t)stream,
                        reinterpret_cast<const float4 *>(cacc), nx, ny, nz, cells, lattice, V, rgb, weight);
     return check_launch("tsdf_vertex_colors");
+}
+
+SCANERF_API int scanerf_tsdf_vertex_normals(const float *values, const uint8_t *observed, int nx, int ny, int nz, const float *spacing,
+                                            const int32_t *cells, const float *lattice, int V, float *normal, float *grad,
+                                            scanerf_stream_t stream)
+{
+    const float inf = __builtin_huge_valf();
+    SCANERF_REQUIRE(V >= 0, "tsdf_vertex_normals: V=%d (negative size)", V);
+    SCANERF_REQUIRE(nx >= 1 && ny >= 1 && nz >= 1, "tsdf_vertex_normals: n=(%d, %d, %d) (every n_k must be >= 1)", nx, ny, nz);
+    SCANERF_REQUIRE(lattice_ok(nx, ny, nz), "tsdf_vertex_normals: n=(%d, %d, %d) has 2^31 or more lattice points", nx, ny, nz);
+    SCANERF_REQUIRE(values && observed && spacing && cells && lattice && normal && grad, "tsdf_vertex_normals: null pointer");
+    for (int a = 0; a < 3; ++a)
+        SCANERF_REQUIRE(spacing[a] > 0.0f && spacing[a] < inf, "tsdf_vertex_normals: spacing[%d]=%g (must be > 0 and finite)", a,
+                        (double)spacing[a]);
+    if (V == 0) return 0;
+    hipLaunchKernelGGL(k_tsdf_vertex_normals, dim3(stream_grid(V, kThreads)), dim3(kThreads), 0, (hipStream_t)stream, values, observed, nx,
+                       ny, nz, spacing[0], spacing[1], spacing[2], cells, lattice, V, normal, grad);
+    return check_launch("tsdf_vertex_normals");
 }

@@ -1,6 +1,7 @@
 """Geometric evaluation of a mesh against another: sample both surfaces, ask for every sample the exact distance to
 the other mesh (FastMesh.closest_point, csrc/mesh_distance.hip -- the hot step), and reduce: accuracy (pred -> gt), completeness
-(gt -> pred), chamfer distance, precision / recall / F-score at distance thresholds.  The reference scores images only
+(gt -> pred), chamfer distance, precision / recall / F-score at distance thresholds, and on request normal consistency (DESIGN.md 4.22:
+the dot product of the sampled face's and the nearest face's unit normals).  The reference scores images only
 (postprocess/evaluation.py: PSNR / SSIM, here TileTrainer.validate); it has no geometric score.
 
 sample_surface and the reductions are torch ops: they touch each sample once and are not a hot path (the query is)."""
@@ -68,6 +69,55 @@ def summarize(d_pred_to_gt, d_gt_to_pred, thresholds):
     return {"pred_to_gt": a, "gt_to_pred": b, "precision": pr, "recall": rc, "fscore": fs, "chamfer": 0.5 * (a["mean"] + b["mean"])}
 
 
+def _flag(v, name):
+    if not isinstance(v, bool):
+        raise ValueError(f"scanerf: {name} must be True or False, got {v!r}")
+    return v
+
+
+def face_normals(vertices, faces):
+    """-> (unit [F,3] f64, has_area [F] bool): cross(b - a, c - a) of each face in float64 from the float32 vertices, normalised;
+    a face with zero (or non-finite) area has has_area False and the normal 0."""
+    v = torch.as_tensor(vertices).to(_f32).to(_f64)
+    tri = v[torch.as_tensor(faces).to(device=v.device, dtype=_i64)]
+    n = torch.linalg.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0])
+    length = n.norm(dim=1)
+    ok = torch.isfinite(length) & (length > 0)
+    return torch.where(ok[:, None], n / torch.where(ok, length, torch.ones_like(length))[:, None], torch.zeros_like(n)), ok
+
+
+def _consistency(dist, sample_face, nearest_face, sample_normals, sample_area, nearest_normals, nearest_area):
+    """One direction of normal_consistency: dist [n] (+inf = not found), sample_face [n] (rows of sample_normals: the mesh the
+    samples were drawn on), nearest_face [n] (rows of nearest_normals: the other mesh; any value where not found).  A sample counts
+    iff its distance is finite and both faces have area; c = n_sample . n_nearest.  -> mean, mean_abs, skipped (the share of the n
+    samples left out; NaN figures when none counts).  Torch ops on the arrays' device; no GPU needed."""
+    n = int(dist.numel())
+    found = torch.isfinite(dist.to(_f64))
+    sf = sample_face.to(_i64)
+    nf = torch.where(found, nearest_face.to(_i64), torch.zeros_like(sf)).clamp_(0, max(int(nearest_normals.shape[0]) - 1, 0))
+    if nearest_normals.shape[0] == 0 or sample_normals.shape[0] == 0:
+        use = torch.zeros_like(found)
+    else:
+        use = found & sample_area[sf] & nearest_area[nf]
+    c = (sample_normals[sf[use]] * nearest_normals[nf[use]]).sum(1)
+    k = int(c.numel())
+    nan = float("nan")
+    return {"mean": float(c.mean()) if k else nan, "mean_abs": float(c.abs().mean()) if k else nan,
+            "skipped": float(n - k) / n if n else nan}
+
+
+def normal_consistency(pred, gt, pred_to_gt, gt_to_pred):
+    """The orientation score beside the distances: pred, gt = (vertices, faces); pred_to_gt / gt_to_pred =
+    (dist, sample_face, nearest_face) of the direction.  -> {"pred_to_gt", "gt_to_pred": _consistency's figures, "mean": the mean
+    of the two directions' mean}.  1: the surfaces face the same way where they are close; -1: one of them is wound inside out;
+    mean_abs ignores the winding."""
+    pn, pa = face_normals(*pred)
+    gn, ga = face_normals(*gt)
+    a = _consistency(*pred_to_gt, pn, pa, gn, ga)
+    b = _consistency(*gt_to_pred, gn, ga, pn, pa)
+    return {"pred_to_gt": a, "gt_to_pred": b, "mean": 0.5 * (a["mean"] + b["mean"])}
+
+
 def _mesh_arrays(mesh, device):
     if isinstance(mesh, (str, bytes)) or hasattr(mesh, "__fspath__"):
         v, f = formats.read_ply(mesh)
@@ -77,11 +127,16 @@ def _mesh_arrays(mesh, device):
 
 
 @torch.no_grad()
-def compare_meshes(pred, gt, n_samples, thresholds, max_dist=float("inf"), seed=0, log2dim=6, return_distances=False, device=None):
+def compare_meshes(pred, gt, n_samples, thresholds, max_dist=float("inf"), seed=0, log2dim=6, return_distances=False, device=None,
+                   normals=False):
     """pred, gt: (vertices [V,3], faces [F,3]) or PLY paths.  n_samples points are drawn on each surface (sample_surface; seed for
     pred, seed + 1 for gt) and queried against the OTHER mesh's FastMesh (log2dim; exact nearest triangle, cut at max_dist).
     -> summarize()'s dict plus n_samples, thresholds and max_dist (None = no cut); with return_distances=True also "distances":
-    per direction the sample points, their faces, the distances and the nearest faces of the other mesh (tensors on the device)."""
+    per direction the sample points, their faces, the distances and the nearest faces of the other mesh (tensors on the device).
+    normals=True adds "normal_consistency" (normal_consistency above): per direction the mean and mean absolute dot product of the
+    sampled face's and the nearest face's unit normals over the samples that were found and whose two faces have area, the share
+    skipped, and "mean" over the two directions.  Without it the dict is what it was, key for key."""
+    _flag(normals, "normals")
     from .fastmesh import FastMesh
     if device is None:
         dv = [m[0].device for m in (pred, gt) if isinstance(m, (tuple, list)) and isinstance(m[0], torch.Tensor) and m[0].is_cuda]
@@ -99,6 +154,8 @@ def compare_meshes(pred, gt, n_samples, thresholds, max_dist=float("inf"), seed=
     d_gp, f_gp, _ = FastMesh.from_arrays(pv, pf, device, log2dim).closest_point(gs, max_dist, want_closest=False)
     out = summarize(d_pg, d_gp, thresholds)
     out.update(n_samples=int(n_samples), thresholds=thresholds, max_dist=None if math.isinf(max_dist) else max_dist)
+    if normals:
+        out["normal_consistency"] = normal_consistency((pv, pf), (gv, gf), (d_pg, ps_face, f_pg), (d_gp, gs_face, f_gp))
     if return_distances:
         out["distances"] = {"pred_to_gt": {"points": ps, "sample_face": ps_face, "dist": d_pg, "face": f_pg},
                             "gt_to_pred": {"points": gs, "sample_face": gs_face, "dist": d_gp, "face": f_gp}}
@@ -126,12 +183,15 @@ def add_score_arguments(ap, required):
     ap.add_argument("--max-dist", type=float, default=float("inf"), metavar="D", help="give up on a point beyond this distance")
     ap.add_argument("--log2dim", type=int, default=6, help="grid cells per axis of the query structure, as a power of two (4..7)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--normal-consistency", action="store_true",
+                    help="also score orientation: the dot product of the sampled and the nearest face's unit normals (normal_consistency)")
 
 
 def score_line(pred, gt, args, device, distances=None):
     """-> json_line(compare_meshes(pred, gt)) under `args` (add_score_arguments); distances: an .npz path for save_distances."""
     res = compare_meshes(pred, gt, args.samples, args.threshold, max_dist=args.max_dist, seed=args.seed, log2dim=args.log2dim,
-                         return_distances=distances is not None, device=device)
+                         return_distances=distances is not None, device=device,
+                         normals=args.normal_consistency)
     if distances is not None:
         save_distances(distances, res)
     return json_line(res)

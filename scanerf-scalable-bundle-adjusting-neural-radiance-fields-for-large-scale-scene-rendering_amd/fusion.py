@@ -10,6 +10,9 @@ the dense surface-nets op.  The reference has no counterpart; the definition is 
     TSDFVolume(..., color=True)                       also owns cacc [P,4] = (R, G, B, Wc): integrate(..., colors=)
                                                       sums the images' pixels in the same launch, vertex_colors(mesh) reads them
                                                       back at a mesh's vertices, extract(colors=True) -> (mesh, rgb)
+    TSDFVolume.vertex_normals(mesh)                   the volume's own gradient at a mesh's vertices (DESIGN.md 4.22): (normal, grad);
+                                                      extract(normals=True) sets Mesh.normals on the FINAL mesh; route="composed" is
+                                                      the witness, one eager float32 torch op per operation of the definition
     support_cull(mesh, support)                       a face stays iff all three vertices have support 8
     fuse_depth_maps(depths, ks, c2ws, box, n, ...)    the above in one call, the cameras fed in batches; colors= [C,H,W,3] -> (mesh, rgb)
     mask_depth / scale_cameras / clamped_image        what TileSetRenderer.fuse_mesh does to its renders and cameras
@@ -261,14 +264,108 @@ class TSDFVolume:
             rgb[weight == 0] = fill
         return rgb, weight
 
+    def _normals_inputs(self, mesh, values, observed):
+        """The checks of vertex_normals that need no device -> V."""
+        if getattr(mesh, "cells", None) is None or getattr(mesh, "lattice", None) is None:
+            raise RuntimeError("scanerf: vertex_normals needs mesh.cells and mesh.lattice (a mesh of this volume's lattice)")
+        if (values is None) != (observed is None):
+            raise RuntimeError("scanerf: vertex_normals takes values and observed together (what TSDFVolume.values returned), or neither")
+        for t, name in ((mesh.cells, "cells"), (mesh.lattice, "lattice"), (values, "values"), (observed, "observed")):
+            if t is not None and not isinstance(t, torch.Tensor):
+                raise RuntimeError(f"scanerf: {name} must be a torch.Tensor, got {type(t).__name__}")
+        V = int(mesh.cells.shape[0]) if mesh.cells.dim() else -1
+        if mesh.cells.dim() != 2 or mesh.cells.shape[1] != 3 or tuple(mesh.lattice.shape) != (V, 3):
+            raise RuntimeError(f"scanerf: cells and lattice must be [V,3], got {tuple(mesh.cells.shape)} and {tuple(mesh.lattice.shape)}")
+        if values is not None and (tuple(values.shape) != self.shape or tuple(observed.shape) != self.shape):
+            raise RuntimeError(f"scanerf: values and observed must be {list(self.shape)}, got {list(values.shape)} and {list(observed.shape)}")
+        return V
+
     @torch.no_grad()
-    def extract(self, min_weight=1, min_faces=0, min_extent=0, keep_largest=None, report=None, colors=False):
+    def vertex_normals(self, mesh, min_weight=1, values=None, observed=None, route="fused"):
+        """The normals of a mesh's vertices from the volume's own gradient (the mesh from this volume's lattice, with
+        cells and lattice) -> (normal [V,3] f32, grad [V,3] f32).  Per lattice point and axis the difference of the observed
+        neighbours' values (central where both exist, one-sided where one does, 0 where none), interpolated trilinearly over the
+        eight corners of the vertex's cell at mesh.lattice: grad; normal = -grad / (|grad| + 1e-8), pointing out of the surface as the
+        faces are wound.  A vertex whose cell has an unobserved corner (or lies outside the lattice) gets zeros: after the support
+        cull no vertex is of this kind.  values / observed: what self.values(min_weight) returned, when the caller holds them
+        (min_weight is then not used).  route="composed" is the witness: one eager float32 torch op per operation."""
+        if route not in ROUTES:
+            raise RuntimeError(f"scanerf: route must be one of {ROUTES}, got {route!r}")
+        min_weight = _min_weight(min_weight)
+        V = self._normals_inputs(mesh, values, observed)
+        cp, lp = dev_ptr(mesh.cells, _i32, "cells"), dev_ptr(mesh.lattice, _f32, "lattice")
+        if mesh.cells.device != self.acc.device or mesh.lattice.device != self.acc.device:
+            raise RuntimeError(f"scanerf: the mesh lives on {mesh.cells.device}, the volume on {self.acc.device}")
+        if values is None:
+            values, observed = self.values(min_weight)
+        vp, op = dev_ptr(values, _f32, "values"), dev_ptr(observed, (torch.bool, torch.uint8), "observed")
+        if values.device != self.acc.device or observed.device != self.acc.device:
+            raise RuntimeError(f"scanerf: values live on {values.device}, observed on {observed.device}, the volume on {self.acc.device}")
+        if route == "composed":
+            return self._vertex_normals_composed(values, observed, mesh.cells, mesh.lattice)
+        normal = torch.empty((V, 3), dtype=_f32, device=self.acc.device)
+        grad = torch.empty((V, 3), dtype=_f32, device=self.acc.device)
+        if V:
+            check(tool("scanerf_tsdf_vertex_normals")(vp, op, *self.n, self.spacing, cp, lp, V, normal.data_ptr(), grad.data_ptr(),
+                                                      stream()), "tsdf_vertex_normals")
+        return normal, grad
+
+    def _vertex_normals_composed(self, values, observed, cells, lattice):
+        """The witness: the definition of include/scanerf_mesh_tools_hip.h with all four branches of the lattice gradient, every
+        operation one eager float32 torch op, the gathers through index arithmetic."""
+        dev = self.acc.device
+        scalar = lambda v: torch.tensor(v, dtype=_f32, device=dev)
+        V = int(cells.shape[0])
+        val, obs = values.reshape(-1), observed.reshape(-1).view(torch.uint8) != 0
+        n = torch.tensor(self.n, dtype=torch.int64, device=dev)
+        stride = ((self.n[1] + 1) * (self.n[2] + 1), self.n[2] + 1, 1)
+        cell = cells.to(torch.int64)
+        inside = ((cell >= 0) & (cell < n)).all(1)
+        c = torch.where(inside[:, None], cell, torch.zeros_like(cell))
+        zero, one = scalar(0.0), scalar(1.0)
+        t = torch.minimum(torch.maximum(lattice - cell.to(_f32), zero), one)
+        t = torch.where(torch.isnan(t), zero, t)                       # fmaxf(NaN, 0) = 0
+        w = torch.stack([one - t, t], -1)                              # [V,3,2]
+        corner = [(d >> 2, (d >> 1) & 1, d & 1) for d in range(8)]
+        idx = [[c[:, k] + o[k] for k in range(3)] for o in corner]
+        row = lambda i: (i[0] * stride[0] + i[1] * stride[1]) + i[2]
+        ok = inside.clone()
+        for i in idx:
+            ok &= obs[row(i)]
+        G = []
+        for a in range(3):
+            h = scalar(self.spacing[a])
+            h2 = h + h
+            acc = None
+            for d, i in enumerate(idx):
+                q = row(i)
+                in_p, in_m = i[a] + 1 <= n[a], i[a] - 1 >= 0
+                qp, qm = torch.where(in_p, q + stride[a], q), torch.where(in_m, q - stride[a], q)
+                has_p, has_m = in_p & obs[qp], in_m & obs[qm]
+                vq, vp, vm = val[q], val[qp], val[qm]
+                g = torch.where(has_p & has_m, (vp - vm) / h2,
+                                torch.where(has_p, (vp - vq) / h, torch.where(has_m, (vq - vm) / h, torch.zeros_like(vq))))
+                wd = (w[:, 0, corner[d][0]] * w[:, 1, corner[d][1]]) * w[:, 2, corner[d][2]]
+                acc = wd * g if acc is None else acc + wd * g
+            G.append(acc)
+        G = torch.stack(G, 1) if V else torch.zeros((0, 3), dtype=_f32, device=dev)
+        length = torch.sqrt((G[:, 0] * G[:, 0] + G[:, 1] * G[:, 1]) + G[:, 2] * G[:, 2])
+        normal = (-G) / (length + scalar(1e-8))[:, None]
+        none = torch.zeros_like(G)
+        return torch.where(ok[:, None], normal, none).contiguous(), torch.where(ok[:, None], G, none).contiguous()
+
+    @torch.no_grad()
+    def extract(self, min_weight=1, min_faces=0, min_extent=0, keep_largest=None, report=None, colors=False, normals=False):
         """The fused surface: surface_nets(values, 0.5) -> cell_support -> support_cull -> filter_mesh's three rules.  -> meshing.Mesh
-        (no normals).  report: a dict that receives support_cull's rows under "support" and the component filter's.
+        (no normals unless asked for).  report: a dict that receives support_cull's rows under "support" and the component filter's.
         colors=True (a volume with colour): -> (mesh, rgb [V,3] f32), vertex_colors on the FINAL mesh, after the support cull and the
-        component filter; report["color"] receives the number of vertices no camera coloured (they hold vertex_colors' fill)."""
+        component filter; report["color"] receives the number of vertices no camera coloured (they hold vertex_colors' fill).
+        normals=True: the returned Mesh has normals = vertex_normals on the FINAL mesh, from the values / observed
+        this call already holds; report["normals"] receives the number of vertices with a zero normal."""
         if not isinstance(colors, (bool, np.bool_)):
             raise RuntimeError(f"scanerf: colors must be True or False, got {colors!r}")
+        if not isinstance(normals, (bool, np.bool_)):
+            raise RuntimeError(f"scanerf: normals must be True or False, got {normals!r}")
         if colors and self.cacc is None:
             raise RuntimeError("scanerf: extract(colors=True) needs a volume with colour (color=True)")
         min_weight = _min_weight(min_weight)
@@ -280,6 +377,11 @@ class TSDFVolume:
         if report is not None:
             report["support"] = sub
         mesh = meshing._filter(mesh, min_faces, min_extent, keep_largest, "fused", False, report)
+        if normals:
+            normal, _ = self.vertex_normals(mesh, min_weight, values, observed)
+            mesh = meshing.Mesh(mesh.vertices, mesh.faces, mesh.cells, mesh.lattice, normal)
+            if report is not None:
+                report["normals"] = int((normal == 0).all(1).sum())
         if not colors:
             return mesh
         rgb, weight = self.vertex_colors(mesh)
@@ -326,12 +428,15 @@ def _views_per_batch(v):
 
 
 def fuse_depth_maps(depths, ks, c2ws, box_corner, box_size, n, trunc=None, views_per_batch=8, near=0.0, far=math.inf, min_weight=1,
-                    min_faces=0, min_extent=0, keep_largest=None, report=None, colors=None):
+                    min_faces=0, min_extent=0, keep_largest=None, report=None, colors=None, normals=False):
     """Depth maps [C,H,W] f32 (z-depth, 0 = no depth) of the cameras ks / c2ws -> the Mesh of what they saw, on a lattice of n cells
     over the world box box_corner / box_size.  trunc: default_trunc of the spacing.  The cameras are integrated views_per_batch at a
     time (the same bits for every batch size).  The rest: TSDFVolume.extract.  colors [C,H,W,3] f32 (the cameras' images, values in
-    [0, 1] for a PLY): -> (mesh, rgb [V,3] f32), the mesh the one of the call without colours."""
+    [0, 1] for a PLY): -> (mesh, rgb [V,3] f32), the mesh the one of the call without colours.  normals=True: the Mesh carries
+    TSDFVolume.vertex_normals."""
     vpb = _views_per_batch(views_per_batch)
+    if not isinstance(normals, (bool, np.bool_)):
+        raise RuntimeError(f"scanerf: normals must be True or False, got {normals!r}")
     n = meshing._lattice_size(n)
     corner, size = meshing._host3(box_corner, "box_corner"), meshing._host3(box_size, "box_size")
     if not all(0.0 < s < math.inf for s in size):
@@ -351,7 +456,7 @@ def fuse_depth_maps(depths, ks, c2ws, box_corner, box_size, n, trunc=None, views
     for i in range(0, int(depths.shape[0]), vpb):
         vol.integrate(depths[i:i + vpb], ks[i:i + vpb], c2ws[i:i + vpb], near=near, far=far,
                       colors=None if colors is None else colors[i:i + vpb])
-    return vol.extract(min_weight, min_faces, min_extent, keep_largest, report, colors=colors is not None)
+    return vol.extract(min_weight, min_faces, min_extent, keep_largest, report, colors=colors is not None, normals=bool(normals))
 
 
 # ---- what TileSetRenderer.fuse_mesh does to its cameras and renders ---------------------------------------------------------------

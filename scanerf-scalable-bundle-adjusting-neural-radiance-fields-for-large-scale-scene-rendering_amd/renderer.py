@@ -306,18 +306,21 @@ class TileSetRenderer:
 
     @torch.no_grad()
     def evaluate_mesh(self, gt, level, cells_per_axis=256, n_samples=200000, thresholds=(0.05,), max_dist=float("inf"), seed=0,
-                      log2dim=6, return_distances=False, **extract):
+                      log2dim=6, return_distances=False, normals=False, **extract):
         """The geometric score of this scene's mesh against `gt` ((vertices, faces) or a PLY path, e.g. the dataset's scan):
         extract_mesh(level, cells_per_axis, **extract) -- box, route and the filter rules min_faces / min_extent / keep_largest
-        included -- then evaluation.compare_meshes(extracted, gt, ...).  -> its dict (pred = the extracted mesh)."""
+        included -- then evaluation.compare_meshes(extracted, gt, ...).  -> its dict (pred = the extracted mesh).
+        normals=True adds compare_meshes' "normal_consistency" (face normals of both meshes; it is not passed to the extraction)."""
         from . import evaluation
+        evaluation._flag(normals, "normals")
         mesh = self.extract_mesh(level, cells_per_axis, **extract)
         return evaluation.compare_meshes((mesh.vertices, mesh.faces), gt, n_samples, thresholds, max_dist=max_dist, seed=seed,
-                                         log2dim=log2dim, return_distances=return_distances, device=mesh.vertices.device)
+                                         log2dim=log2dim, return_distances=return_distances, device=mesh.vertices.device,
+                                         normals=normals)
 
     @torch.no_grad()
     def fuse_mesh(self, cameras, cells_per_axis=256, box=None, trunc=None, max_transparency=0.5, scale=1, views_per_batch=8,
-                  min_weight=1, min_faces=0, min_extent=0, keep_largest=None, report=None, colors=None, **render_kw):
+                  min_weight=1, min_faces=0, min_extent=0, keep_largest=None, report=None, colors=None, normals=False, **render_kw):
         """ONE mesh of what the cameras saw (fusion.py): cameras = (ks [C,3,3], c2ws [C,3,4], H, W), typically the
         capture's.  Each camera is rendered at H // scale x W // scale (K scaled as fusion.scale_cameras does; render_kw goes to
         render), its depth set to 0 where the transparency exceeds max_transparency or the depth is not finite (fusion.mask_depth),
@@ -326,8 +329,11 @@ class TileSetRenderer:
         TSDFVolume.extract: the zero set, the support cull, filter_mesh's rules.  -> meshing.Mesh (no normals).
         colors: "diffuse" also fuses clamp(diffuse, 0, 1) of the same renders (the view-independent part: the
         sensible colour of a mesh), "rgb" clamp(diffuse + specular, 0, 1) (the image shown everywhere else), batched with the depth
-        maps; -> (mesh, rgb [V,3] f32), the mesh the one of the call without colours.  None: no colour, the Mesh alone."""
+        maps; -> (mesh, rgb [V,3] f32), the mesh the one of the call without colours.  None: no colour, the Mesh alone.
+        normals=True: the Mesh carries the volume's gradient normals (TSDFVolume.vertex_normals)."""
         from . import fusion, meshing
+        if not isinstance(normals, bool):
+            raise RuntimeError(f"scanerf: normals must be True or False, got {normals!r}")
         if colors not in (None, "diffuse", "rgb"):
             raise RuntimeError(f"scanerf: colors must be None, 'diffuse' or 'rgb', got {colors!r}")
         if cameras is None or len(cameras) != 4:
@@ -362,4 +368,4 @@ class TileSetRenderer:
                     images.append(fusion.clamped_image(diffuse, specular if colors == "rgb" else None))
             vol.integrate(torch.stack(maps).contiguous(), ks[i:i + vpb], c2ws[i:i + vpb],
                           colors=torch.stack(images).contiguous() if colors is not None else None)
-        return vol.extract(min_weight, min_faces, min_extent, keep_largest, report, colors=colors is not None)
+        return vol.extract(min_weight, min_faces, min_extent, keep_largest, report, colors=colors is not None, normals=normals)

@@ -2,12 +2,14 @@
 """Geometric score of one mesh against another: accuracy, completeness, chamfer, precision / recall / F-score.
 
     python tools/compare_meshes.py PRED.ply GT.ply --samples N --threshold T [T ...] [--max-dist D] [--log2dim L] [--seed S]
-                                   [--json FILE] [--distances FILE.npz] [--gpu G]
+                                   [--normal-consistency] [--json FILE] [--distances FILE.npz] [--gpu G]
 
 N points are drawn on each surface (area-weighted, stratified) and each is asked the exact distance to the other mesh
 (evaluation.compare_meshes; the query is csrc/mesh_distance.hip).  The result is printed as ONE JSON line: per direction (pred_to_gt
 = accuracy, gt_to_pred = completeness) mean / median / rms over the points found and the share not found within --max-dist; per
-threshold precision, recall and fscore; chamfer = the mean of the two means.  --json also stores the line; --distances stores the
+threshold precision, recall and fscore; chamfer = the mean of the two means.  --normal-consistency adds the orientation score
+(DESIGN.md 4.22): per direction the mean and mean absolute dot product of the sampled face's and the nearest face's unit normals, and
+the share of samples skipped (not found, or a face without area).  --json also stores the line; --distances stores the
 sample points, their faces, the distances and the nearest faces of both directions."""
 import argparse
 import os

@@ -4,7 +4,8 @@
     python tools/extract_mesh.py TILEDIR [TILEDIR ...] --level SIGMA [--cells-per-axis 256] [--out DIR] [--normals] [--route fused|dense]
                                  [--gpu 0] [--min-faces N] [--min-extent CELLS] [--keep-largest K]
                                  [--cameras camera.log --min-views N [--view-bias B] [--view-far D]]
-                                 [--compare GT.ply --threshold T [T ...] [--samples N] [--max-dist D] [--log2dim L] [--seed S]]
+                                 [--compare GT.ply --threshold T [T ...] [--samples N] [--max-dist D] [--log2dim L] [--seed S]
+                                  [--normal-consistency]]
 
 TILEDIR holds feature.npz and decoder.pth as renderer.export_tile writes and renderer.load_tile reads them.  The lattice covers the
 tile box (the inner half of the exported 2x box) with --cells-per-axis cells along its longest side and the other sides by the box's

@@ -5,7 +5,8 @@
                                        [--box X Y Z SX SY SZ] --out FILE.ply [--normals] [--route fused|dense] [--gpu 0]
                                        [--min-faces N] [--min-extent CELLS] [--keep-largest K]
                                        [--cameras camera.log --min-views N [--view-bias B] [--view-far D]]
-                                       [--compare GT.ply --threshold T [T ...] [--samples N] [--max-dist D] [--log2dim L] [--seed S]]
+                                       [--compare GT.ply --threshold T [T ...] [--samples N] [--max-dist D] [--log2dim L] [--seed S]
+                                        [--normal-consistency]]
 
 Every TILEDIR holds feature.npz and decoder.pth as renderer.export_tile writes and renderer.load_tile reads them; together they are
 the scene renderer.TileSetRenderer draws.  The field is the one it draws: the tiles' densities blended per point with the render-time

@@ -5,8 +5,9 @@ distance volume, the zero set written as a PLY.
     python tools/fuse_mesh.py TILEDIR [TILEDIR ...] --cameras camera.log --out FILE.ply [--cells-per-axis 256]
                               [--box X Y Z SX SY SZ] [--trunc T] [--min-weight N] [--scale S] [--max-transparency A]
                               [--views-per-batch B] [--min-faces N] [--min-extent CELLS] [--keep-largest K] [--gpu 0]
-                              [--colors diffuse|rgb]
-                              [--compare GT.ply --threshold T [T ...] [--samples N] [--max-dist D] [--log2dim L] [--seed S]]
+                              [--colors diffuse|rgb] [--normals]
+                              [--compare GT.ply --threshold T [T ...] [--samples N] [--max-dist D] [--log2dim L] [--seed S]
+                               [--normal-consistency]]
 
 Every TILEDIR holds feature.npz and decoder.pth as renderer.export_tile writes and renderer.load_tile reads them.  Each camera of
 camera.log (formats.read_campara) is rendered at 1 / --scale of its size; a pixel whose ray kept more than --max-transparency of its
@@ -17,6 +18,8 @@ zero set, in world units; what no ray stopped at never enters it.  Faces that to
 (fusion.support_cull), then --min-faces / --min-extent / --keep-largest drop components (meshing.filter_mesh).
 --colors fuses the renders' images with the same weights and writes them as uchar red / green / blue per vertex:
 `diffuse` the view-independent part, `rgb` diffuse + specular, each clamped to [0, 1]; a vertex no camera coloured is mid grey.
+--normals writes nx / ny / nz per vertex: the volume's own gradient at the vertex, pointing out of the surface (DESIGN.md 4.22);
+with --colors one PLY holds both.
 --compare GT.ply prints the geometric score against GT.ply as the one JSON line of tools/compare_meshes.py.
 tools/extract_scene_mesh.py cuts the density's level set instead."""
 import argparse
@@ -46,6 +49,7 @@ def parser():
     ap.add_argument("--gpu", type=int, default=0)
     ap.add_argument("--colors", choices=("diffuse", "rgb"), default=None,
                     help="also fuse the renders' colours and write them as red / green / blue per vertex")
+    ap.add_argument("--normals", action="store_true", help="also write nx / ny / nz per vertex: the volume's gradient normals")
     ap.add_argument("--compare", default=None, metavar="GT.ply",
                     help="after writing the PLY, print the geometric score of the mesh against GT.ply as one JSON line (needs --threshold)")
     import scanerf_amd  # noqa: F401
@@ -66,12 +70,14 @@ def main(argv=None):
     cameras = formats.read_campara(args.cameras, return_shape=True)
     mesh = rnd.fuse_mesh(cameras, args.cells_per_axis, box=box, trunc=args.trunc, max_transparency=args.max_transparency, scale=args.scale,
                          views_per_batch=args.views_per_batch, min_weight=args.min_weight, min_faces=args.min_faces,
-                         min_extent=args.min_extent, keep_largest=args.keep_largest, report=report, colors=args.colors)
+                         min_extent=args.min_extent, keep_largest=args.keep_largest, report=report, colors=args.colors,
+                         normals=args.normals)
     rgb = None
     if args.colors:
         mesh, rgb = mesh
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    formats.write_ply(args.out, mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy(), colors=None if rgb is None else rgb.cpu().numpy())
+    formats.write_ply(args.out, mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy(), colors=None if rgb is None else rgb.cpu().numpy(),
+                      normals=mesh.normals.cpu().numpy() if args.normals else None)
     sup = report["support"]
     print(f"{args.out}: {len(args.tiles)} tiles, {len(cameras[0])} cameras, {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} faces")
     print(f"{args.out}: support cull: vertices {sup['vertices'][0]} -> {sup['vertices'][1]}, faces {sup['faces'][0]} -> {sup['faces'][1]}")
@@ -79,6 +85,8 @@ def main(argv=None):
           f"{report['vertices'][1]}, faces {report['faces'][0]} -> {report['faces'][1]}")
     if args.colors:
         print(f"{args.out}: colours ({args.colors}): {report['color']} of {mesh.vertices.shape[0]} vertices uncoloured")
+    if args.normals:
+        print(f"{args.out}: normals: {report['normals']} of {mesh.vertices.shape[0]} vertices with a zero normal")
     if args.compare:
         print(evaluation.score_line((mesh.vertices, mesh.faces), args.compare, args, mesh.vertices.device))
     return 0
