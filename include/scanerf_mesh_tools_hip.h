@@ -157,6 +157,55 @@ int scanerf_tsdf_vertex_normals(const float *values, const uint8_t *observed, in
                                 const int32_t *cells, const float *lattice, int V, float *normal, float *grad,
                                 scanerf_stream_t stream);
 
+/* ---- mesh simplification by vertex clustering (csrc/mesh_simplify.hip): the vertices that fall into one cell of a
+ *   world-aligned grid of cubic cells become one vertex (Rossignac-Borrel).  What "hand out the fused mesh at the resolution the
+ *   consumer wants" needs.  The reference has no counterpart; the definition is this comment.
+ *   Inputs: vertices [V,3] f32; faces [F,3] i32; normals [V,3] f32 and colors [V,3] f32 (each may be NULL); origin[3]: a HOST array,
+ *     finite (the grid is the world's: meshes simplified separately cluster alike); cell = h, finite and > 0.
+ *   KEY, per axis a, in float32, one IEEE operation each, without FMA contraction, the division correctly rounded:
+ *     u = (v_a - o_a) / h;  k = floorf(u);  f = u - k;  q = (int)(f * 65536).
+ *     0 <= f <= 1.  The subtraction is exact except for -1/2 < u < 0 (k = -1, and u carries bits below the result's last place): there
+ *     it is one rounding like the others, and a u above -2^-25 gives f = 1, q = 65536.  Nothing below needs exactness or q < 65536.
+ *     f * 65536 is an exact scaling.
+ *   A vertex is BAD iff a coordinate is not finite, or not |k| < 2^20 on some axis, or one of its normal / colour values is not
+ *     finite.  A bad vertex belongs to no cluster and a face with a bad corner counts for nothing; n_bad is their number.
+ *   CLUSTERS: the sets of (good) vertices with equal (kx, ky, kz).  A cluster's label is its smallest member index; clusters are
+ *     numbered by ascending label, and that number is the output vertex index (the output follows the input's order).
+ *   POSITION: n members, S_a = the sum of q_a (an integer), M_a = (2 S_a + n) div (2 n);
+ *     out_a = o_a + ((float)k_a + (float)M_a * 2^-16) * h, in float32 in that order.
+ *   ATTRIBUTES, per value a: t = rintf(fminf(fmaxf(a, -32767), 32767) * 65536) as an integer; S = the sum of t in int64;
+ *     M = floor((2 S + n) / (2 n)) (floor division for negative values too); m = (float)M * 2^-16.
+ *     Colours are m.  Normals are m_a / (sqrtf((mx mx + my my) + mz mz) + 1e-8f): zero sums give a zero normal.
+ *   A cluster of ONE member copies its vertex, normal and colour bit for bit: a cell below the vertex spacing returns the input.
+ *   FACES: each corner goes to its cluster's number; a face with two equal corners is dropped; kept faces stay in order and keep
+ *     their winding.  A cluster that ends with no face stays a vertex.  Duplicate faces are kept.
+ *   Everything that decides the result is an integer or a single-rounded float32 operation: the output does not depend on thread
+ *     order, launch geometry or timing.
+ *   scanerf_mesh_simplify_scratch_bytes: *bytes = the scratch both passes need, for 1 <= V <= 2^29 and 0 <= F < 2^31 / 3 (otherwise
+ *     refused, *bytes = 0).  With T = the smallest power of two >= max(64, 2 V) (the lookup table's slots: its load is at most 1/2)
+ *     and r16(x) = x rounded up to a multiple of 16:
+ *     bytes = 64 + 12 T + 2 r16(4 V) + r16(4 (ceil(V / 256) + 1)) + r16(4 (ceil(F / 256) + 1)).
+ *   scanerf_mesh_simplify_cluster: the table, labels, numbers and per-vertex rows, the counts of kept faces and their scan, all on
+ *     `stream`, no host synchronisation.  Afterwards the scratch starts with int64 (V', F', n_bad): the caller's one host read.
+ *     Writes the scratch only.  scratch: 16-byte aligned, scratch_bytes >= the formula.
+ *   scanerf_mesh_simplify_emit: the same vertices, faces, normals, colors, V, F, origin, cell and scratch as the cluster call.
+ *     sums [V',9] i64 and counts [V'] i32: work arrays the caller allocates after its read; the entry zeroes them (per row: the
+ *     sums of q, of the normals' t, of the colours' t).  out_vertices [V',3] f32, out_faces [F',3] i32 (may be NULL when F' == 0),
+ *     out_normals / out_colors [V',3] f32 iff normals / colors are given.  The entry reads (V', F', n_bad) back from the scratch (one
+ *     24-byte read, one synchronisation of `stream`) and REFUSES, writing nothing, when n_bad != 0 or when Vout / Fout are not V' / F'.
+ *     Every row of every output is written exactly once by a plain store.
+ *   Refused before any launch (nothing written): V or F outside the ranges above, null pointers (but faces with F == 0, normals,
+ *     colors), a cell not finite and positive, an origin not finite, a scratch that is null, unaligned or too small; in the emit
+ *     entry also Vout outside [1, V], Fout outside [0, F], an attribute input without its output or the reverse.  A face index
+ *     outside [0, V) is never dereferenced: such a face is dropped.  No allocation, no environment variable. */
+int scanerf_mesh_simplify_scratch_bytes(int V, int F, size_t *bytes);
+int scanerf_mesh_simplify_cluster(const float *vertices, const int32_t *faces, const float *normals, const float *colors, int V, int F,
+                                  const float *origin, float cell, void *scratch, size_t scratch_bytes, scanerf_stream_t stream);
+int scanerf_mesh_simplify_emit(const float *vertices, const int32_t *faces, const float *normals, const float *colors, int V, int F,
+                               const float *origin, float cell, const void *scratch, size_t scratch_bytes, int64_t *sums,
+                               int32_t *counts, float *out_vertices, int32_t *out_faces, float *out_normals, float *out_colors,
+                               int Vout, int Fout, scanerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

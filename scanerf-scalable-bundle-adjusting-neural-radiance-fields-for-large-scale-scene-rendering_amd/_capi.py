@@ -144,6 +144,9 @@ TOOL_PROTOTYPES = {
     "scanerf_tsdf_integrate_color_counted": ("I", "PPPPIIIPPIIIFFFPPPP"),
     "scanerf_tsdf_vertex_colors": ("I", "PIIIPPIPPP"),
     "scanerf_tsdf_vertex_normals": ("I", "PPIIIPPPIPPP"),
+    "scanerf_mesh_simplify_scratch_bytes": ("I", "IIP"),
+    "scanerf_mesh_simplify_cluster": ("I", "PPPPIIPFPZP"),
+    "scanerf_mesh_simplify_emit": ("I", "PPPPIIPFPZPPPPPPIIP"),
 }
 CTYPES = {"P": ctypes.c_void_p, "I": ctypes.c_int, "U": ctypes.c_uint, "F": ctypes.c_float, "Z": ctypes.c_size_t,
           "L": ctypes.c_int64, "S": ctypes.c_char_p}

@@ -38,6 +38,7 @@
 #include <limits.h>
 
 #include "common.h"
+#include "ordered_device.h"
 
 using namespace scanerf;
 
@@ -169,47 +170,7 @@ __global__ void __launch_bounds__(kBlock) k_count(int n, int V, int C, const int
     }
 }
 
-// One workgroup: blocks [n] -> its exclusive sums in place, blocks[n] = *total = the sum.
-constexpr int kScanThreads = 1024;
-__global__ void __launch_bounds__(kScanThreads) k_scan(int *__restrict__ blocks, int n, long long *__restrict__ total)
-{
-    __shared__ int sums[kScanThreads];
-    const int per = (n + kScanThreads - 1) / kScanThreads;
-    const int lo = min(n, (int)threadIdx.x * per), hi = min(n, lo + per);
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += blocks[i];
-    sums[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 1; off < kScanThreads; off <<= 1) {          // inclusive scan of the threads' sums
-        const int add = (int)threadIdx.x >= off ? sums[threadIdx.x - off] : 0;
-        __syncthreads();
-        sums[threadIdx.x] += add;
-        __syncthreads();
-    }
-    int run = sums[threadIdx.x] - s;
-    for (int i = lo; i < hi; ++i) {
-        const int c = blocks[i];
-        blocks[i] = run;
-        run += c;
-    }
-    if (threadIdx.x == kScanThreads - 1) {
-        blocks[n] = sums[threadIdx.x];
-        *total = sums[threadIdx.x];
-    }
-}
-
-// The destination of a flagged item: (flagged items of earlier workgroups) + (of earlier waves) + (of lower lanes).
-__device__ __forceinline__ int destination(bool on, const int *__restrict__ blocks, int *part)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const unsigned long long ballot = __ballot(on);
-    if (lane == 0) part[wv] = __popcll(ballot);
-    __syncthreads();
-    int dst = blocks[blockIdx.x];
-    for (int w = 0; w < wv; ++w) dst += part[w];
-    return dst + __popcll(ballot & ((1ull << lane) - 1ull));
-}
-
+// (the scan of the per-workgroup counts and an item's destination: ordered_device.h)
 // row_of[v] = the row of root v among the roots in ascending order; -1 for every other vertex
 __global__ void __launch_bounds__(kBlock) k_root_rows(int V, const int *__restrict__ labels, const int *__restrict__ blocks,
                                                       int *__restrict__ row_of)

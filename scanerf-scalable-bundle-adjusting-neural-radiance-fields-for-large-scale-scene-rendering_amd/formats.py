@@ -270,6 +270,25 @@ def read_ply(path, normals=False, colors=False):
     return (verts, faces) + ((nrm,) if normals else ()) + ((rgb,) if colors else ())
 
 
+def ply_vertex_properties(path):
+    """The names of the vertex element's properties, in file order, from a PLY's header alone: what read_ply can be asked for."""
+    names, in_vertex = [], False
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        for line in f:
+            tok = line.decode("ascii", "replace").strip().split()
+            if not tok:
+                continue
+            if tok[0] == "end_header":
+                return names
+            if tok[0] == "element":
+                in_vertex = tok[1] == "vertex"
+            elif tok[0] == "property" and in_vertex:
+                names.append(tok[-1])
+    raise ValueError(f"{path}: unterminated PLY header")
+
+
 def quantize_colors(colors):
     """[V,3] floats in [0, 1] -> [V,3] u8: floor(clamp(c, 0, 1) * 255 + 0.5), in float64; a non-finite value is refused."""
     c = np.asarray(colors, np.float64)

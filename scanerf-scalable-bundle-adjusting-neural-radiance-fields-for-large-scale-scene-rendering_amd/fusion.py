@@ -355,13 +355,17 @@ class TSDFVolume:
         return torch.where(ok[:, None], normal, none).contiguous(), torch.where(ok[:, None], G, none).contiguous()
 
     @torch.no_grad()
-    def extract(self, min_weight=1, min_faces=0, min_extent=0, keep_largest=None, report=None, colors=False, normals=False):
+    def extract(self, min_weight=1, min_faces=0, min_extent=0, keep_largest=None, report=None, colors=False, normals=False,
+                simplify=None):
         """The fused surface: surface_nets(values, 0.5) -> cell_support -> support_cull -> filter_mesh's three rules.  -> meshing.Mesh
         (no normals unless asked for).  report: a dict that receives support_cull's rows under "support" and the component filter's.
         colors=True (a volume with colour): -> (mesh, rgb [V,3] f32), vertex_colors on the FINAL mesh, after the support cull and the
         component filter; report["color"] receives the number of vertices no camera coloured (they hold vertex_colors' fill).
         normals=True: the returned Mesh has normals = vertex_normals on the FINAL mesh, from the values / observed
-        this call already holds; report["normals"] receives the number of vertices with a zero normal."""
+        this call already holds; report["normals"] receives the number of vertices with a zero normal.
+        simplify=cell: meshing.simplify_mesh on the world grid of that cell as the LAST step, the normals and colours
+        averaged with the vertices; the Mesh then has no cells / lattice; report["simplify"] receives its rows.  None: nothing."""
+        meshing._simplify_rule(simplify)
         if not isinstance(colors, (bool, np.bool_)):
             raise RuntimeError(f"scanerf: colors must be True or False, got {colors!r}")
         if not isinstance(normals, (bool, np.bool_)):
@@ -383,11 +387,11 @@ class TSDFVolume:
             if report is not None:
                 report["normals"] = int((normal == 0).all(1).sum())
         if not colors:
-            return mesh
+            return meshing._simplified(mesh, simplify, None, report)
         rgb, weight = self.vertex_colors(mesh)
         if report is not None:
             report["color"] = int((weight == 0).sum())
-        return mesh, rgb
+        return meshing._simplified(mesh, simplify, rgb, report)
 
 
 def support_cull(mesh, support, report=None):
@@ -428,12 +432,13 @@ def _views_per_batch(v):
 
 
 def fuse_depth_maps(depths, ks, c2ws, box_corner, box_size, n, trunc=None, views_per_batch=8, near=0.0, far=math.inf, min_weight=1,
-                    min_faces=0, min_extent=0, keep_largest=None, report=None, colors=None, normals=False):
+                    min_faces=0, min_extent=0, keep_largest=None, report=None, colors=None, normals=False, simplify=None):
     """Depth maps [C,H,W] f32 (z-depth, 0 = no depth) of the cameras ks / c2ws -> the Mesh of what they saw, on a lattice of n cells
     over the world box box_corner / box_size.  trunc: default_trunc of the spacing.  The cameras are integrated views_per_batch at a
     time (the same bits for every batch size).  The rest: TSDFVolume.extract.  colors [C,H,W,3] f32 (the cameras' images, values in
     [0, 1] for a PLY): -> (mesh, rgb [V,3] f32), the mesh the one of the call without colours.  normals=True: the Mesh carries
-    TSDFVolume.vertex_normals."""
+    TSDFVolume.vertex_normals.  simplify=cell: TSDFVolume.extract's last step."""
+    meshing._simplify_rule(simplify)
     vpb = _views_per_batch(views_per_batch)
     if not isinstance(normals, (bool, np.bool_)):
         raise RuntimeError(f"scanerf: normals must be True or False, got {normals!r}")
@@ -456,7 +461,8 @@ def fuse_depth_maps(depths, ks, c2ws, box_corner, box_size, n, trunc=None, views
     for i in range(0, int(depths.shape[0]), vpb):
         vol.integrate(depths[i:i + vpb], ks[i:i + vpb], c2ws[i:i + vpb], near=near, far=far,
                       colors=None if colors is None else colors[i:i + vpb])
-    return vol.extract(min_weight, min_faces, min_extent, keep_largest, report, colors=colors is not None, normals=bool(normals))
+    return vol.extract(min_weight, min_faces, min_extent, keep_largest, report, colors=colors is not None, normals=bool(normals),
+                       simplify=simplify)
 
 
 # ---- what TileSetRenderer.fuse_mesh does to its cameras and renders ---------------------------------------------------------------

@@ -17,6 +17,8 @@ lattice.  The reference has no mesh extraction; the definition is the comment of
                                                         DESIGN.md 4.19)
     cull_unseen(mesh, ks, c2ws, H, W, min_views, bias)  drop the faces none of whose vertices min_views cameras saw; the extractors take
                                                         cameras / min_views / view_bias and cull before the component rule
+    simplify_mesh(mesh, cell, origin, colors)           vertex clustering on a world grid: positions, normals and colours averaged per cell
+                                                        (csrc/mesh_simplify.hip); the scene extractors take simplify=cell
 
 All return a Mesh: vertices [V,3] f32 (world), faces [F,3] i32 (counter-clockwise seen from the outside), cells [V,3] i32 (the owning
 cell of each vertex), lattice [V,3] f32 (the vertices in lattice coordinates) and, on request, normals [V,3] f32.  Two launches with
@@ -240,7 +242,7 @@ def _scene_tile_args(feature_tables, resolutions, blobs, corners, sizes, occupie
 
 def extract_scene_mesh(feature_tables, resolutions, blobs, corners, sizes, occupied_grid, grid_starts, log2dim, box_corner, box_size, n,
                        level, route="fused", normals=False, min_faces=0, min_extent=0, keep_largest=None, report=None, cameras=None,
-                       min_views=0, view_bias=None, view_far=None):
+                       min_views=0, view_bias=None, view_far=None, simplify=None):
     """One mesh of a tiled scene: the level set of the field the multi-tile renderer draws -- the tiles' densities blended per lattice
     point with the renderer's xz-distance weights -- on a lattice of n cells over the world box box_corner / box_size (the definition:
     include/scanerf_hip.h, scanerf_isosurface_count_tiles).  The tile arrays are TileSetRenderer's: feature_tables [nb,16,T,2] f16,
@@ -251,7 +253,10 @@ def extract_scene_mesh(feature_tables, resolutions, blobs, corners, sizes, occup
     min_faces / min_extent / keep_largest: filter_mesh's keep rule, applied BEFORE the normals are evaluated; the
     defaults keep everything.  report: a dict that receives the component count and the rows before and after the filter.
     cameras = (ks, c2ws, H, W) with min_views >= 1: cull_unseen on the raw mesh (DESIGN.md 4.19), BEFORE the component rule;
-    view_bias: half a lattice spacing by default; view_far: the cameras' range (None: no limit)."""
+    view_bias: half a lattice spacing by default; view_far: the cameras' range (None: no limit).
+    simplify=cell: simplify_mesh on the world grid of that cell as the LAST step, after the filter and the normals (DESIGN.md 4.23);
+    the Mesh then has no cells / lattice; report["simplify"] receives its rows."""
+    _simplify_rule(simplify)
     if route not in ROUTES:
         raise RuntimeError(f"scanerf: route must be one of {ROUTES}, got {route!r}")
     _rules(min_faces, min_extent, keep_largest, True)
@@ -275,7 +280,7 @@ def extract_scene_mesh(feature_tables, resolutions, blobs, corners, sizes, occup
     mesh = _filter(mesh, min_faces, min_extent, keep_largest, _COMPONENT_ROUTE[route], False, report)
     if normals:
         mesh = mesh._replace(normals=scene_sigma_normals_points(mesh.vertices, *tiles, route=route)[2])
-    return mesh
+    return _simplified(mesh, simplify, None, report, _SIMPLIFY_ROUTE[route])
 
 
 # ---- the blended density's gradient at world points (csrc/scene_normals.hip) -----------------------------------------
@@ -675,6 +680,177 @@ def cull_unseen(mesh, ks, c2ws, H, W, min_views=1, bias=None, near=0.0, far=floa
         return mesh
     views, _ = vertex_views(mesh, ks, c2ws, H, W, bias, near=near, far=far, route=route, log2dim=log2dim)
     return cull_by_views(mesh, views, min_views, report)
+
+
+# ---- simplification by vertex clustering (csrc/mesh_simplify.hip) ----------------------------------------------------
+SIMPLIFY_ROUTES = ("fused", "composed")
+_CELL_LIMIT = 2 ** 20
+
+
+def _simplify_cell(cell):
+    """The cluster cell's side, checked -> the float32 value as a Python float."""
+    if isinstance(cell, bool) or not isinstance(cell, (int, float, np.integer, np.floating)):
+        raise RuntimeError(f"scanerf: cell must be a number, got {cell!r}")
+    with np.errstate(over="ignore"):
+        h = float(np.float32(cell))
+    if not 0.0 < h < float("inf"):
+        raise RuntimeError(f"scanerf: cell must be positive and finite in float32, got {cell!r}")
+    return h
+
+
+def _simplify_args(mesh, cell, origin, colors, route):
+    """The checks simplify_mesh makes before any library call -> (V, F, h, origin as 3 floats)."""
+    if route not in SIMPLIFY_ROUTES:
+        raise RuntimeError(f"scanerf: route must be one of {SIMPLIFY_ROUTES}, got {route!r}")
+    h = _simplify_cell(cell)
+    o = [float(np.float32(v)) for v in _host3(origin, "origin")]
+    if not all(np.isfinite(o)):
+        raise RuntimeError(f"scanerf: origin must be finite, got {list(o)}")
+    dev_ptr(mesh.vertices, _f32, "vertices")
+    if mesh.vertices.dim() != 2 or mesh.vertices.shape[1] != 3:
+        raise RuntimeError(f"scanerf: mesh.vertices must be [V,3], got {tuple(mesh.vertices.shape)}")
+    Vn = int(mesh.vertices.shape[0])
+    for name, t in (("normals", mesh.normals), ("colors", colors)):
+        if t is None:
+            continue
+        dev_ptr(t, _f32, name)
+        if tuple(t.shape) != (Vn, 3) or t.device != mesh.vertices.device:
+            raise RuntimeError(f"scanerf: {name} must be [{Vn},3] on {mesh.vertices.device}, got {tuple(t.shape)} on {t.device}")
+    V, F = _component_args(mesh.faces, Vn, None, "fused", True)
+    if mesh.faces.device != mesh.vertices.device:
+        raise RuntimeError(f"scanerf: mesh.faces lives on {mesh.faces.device}, the vertices on {mesh.vertices.device}")
+    if V > 2 ** 29:
+        raise RuntimeError(f"scanerf: V={V} vertices are more than simplify_mesh takes (2^29)")
+    return V, F, h, o
+
+
+def _fixed(a):
+    """t of the definition: rint(clamp(a, -32767, 32767) * 65536) as int64."""
+    return torch.round(torch.clamp(a, -32767.0, 32767.0) * 65536.0).to(torch.int64)
+
+
+def _rounded_mean(S, n):
+    """M = floor((2 S + n) / (2 n)) on int64."""
+    return torch.div(2 * S + n, 2 * n, rounding_mode="floor")
+
+
+def _simplify_key(vertices, o, h):
+    """-> (k [V,3] f32, q [V,3] i64, good [V] bool by the coordinates): the key's four float32 operations, one torch op each."""
+    # (h as a device tensor: torch divides by a host scalar by multiplying with its reciprocal, which is another rounding)
+    u = (vertices - torch.tensor(o, dtype=_f32, device=vertices.device)) / torch.tensor([h], dtype=_f32, device=vertices.device)
+    k = torch.floor(u)
+    f = u - k
+    good = (torch.isfinite(vertices) & (k.abs() < float(_CELL_LIMIT))).all(1)
+    q = torch.where(good[:, None], f * 65536.0, torch.zeros_like(f)).to(torch.int64)
+    return k, q, good
+
+
+def _simplify_composed(mesh, colors, V, F, h, o):
+    """The witness: the definition of include/scanerf_mesh_tools_hip.h in torch ops -> (vertices, faces, normals, colors, counts)."""
+    device = mesh.vertices.device
+    k, q, good = _simplify_key(mesh.vertices, o, h)
+    for t in (mesh.normals, colors):
+        if t is not None:
+            good &= torch.isfinite(t).all(1)
+    n_bad = int((~good).sum())
+    if n_bad:
+        raise RuntimeError(f"scanerf: simplify_mesh: {n_bad} bad vertices (not finite, or more than 2^20 cells from the origin)")
+    index = torch.arange(V, dtype=torch.int64, device=device)
+    cells, member = torch.unique(k.to(torch.int64), dim=0, return_inverse=True)
+    first = torch.full((cells.shape[0],), V, dtype=torch.int64, device=device).scatter_reduce(0, member, index, "amin")
+    label = first[member]
+    root = label == index
+    row = (torch.cumsum(root, 0) - 1)[label]
+    roots = index[root]
+    Vk = int(roots.shape[0])
+    counts = torch.zeros(Vk, dtype=torch.int64, device=device).index_add_(0, row, torch.ones_like(row))
+    single = (counts == 1)[:, None]
+    n = counts[:, None]
+
+    def mean(t):
+        return _rounded_mean(torch.zeros((Vk, 3), dtype=torch.int64, device=device).index_add_(0, row, t), n).to(_f32) * 2.0 ** -16
+
+    o_t = torch.tensor(o, dtype=_f32, device=device)
+    out_v = torch.where(single, mesh.vertices[roots], o_t + (k[roots] + mean(q)) * h)
+    out_n = out_c = None
+    if mesh.normals is not None:
+        m = mean(_fixed(mesh.normals))
+        length = torch.sqrt((m[:, 0] * m[:, 0] + m[:, 1] * m[:, 1]) + m[:, 2] * m[:, 2]) + 1e-8
+        out_n = torch.where(single, mesh.normals[roots], m / length[:, None]).contiguous()
+    if colors is not None:
+        out_c = torch.where(single, colors[roots], mean(_fixed(colors))).contiguous()
+    rf = row[mesh.faces.to(torch.int64)].reshape(-1, 3)
+    keep = (rf[:, 0] != rf[:, 1]) & (rf[:, 0] != rf[:, 2]) & (rf[:, 1] != rf[:, 2])
+    return out_v.contiguous(), rf[keep].to(_i32).contiguous(), out_n, out_c, counts
+
+
+def _simplify_fused(mesh, colors, V, F, h, o):
+    from ._capi import tool
+    device = mesh.vertices.device
+    nbytes = ctypes.c_size_t(0)
+    check(tool("scanerf_mesh_simplify_scratch_bytes")(V, F, ctypes.addressof(nbytes)), "mesh_simplify_scratch_bytes")
+    nbytes = int(nbytes.value)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    host_o = (ctypes.c_float * 3)(*o)
+    head = (mesh.vertices.data_ptr(), mesh.faces.data_ptr() if F else None, ptr(mesh.normals), ptr(colors), V, F,
+            ctypes.addressof(host_o), h, scratch.data_ptr(), nbytes)
+    check(tool("scanerf_mesh_simplify_cluster")(*head, stream()), "mesh_simplify_cluster")
+    Vk, Fk, n_bad = (int(v) for v in scratch[:24].view(torch.int64).tolist())      # the one host read
+    if n_bad:
+        raise RuntimeError(f"scanerf: simplify_mesh: {n_bad} bad vertices (not finite, or more than 2^20 cells from the origin)")
+    new = lambda rows, dt, on=True: torch.empty((rows, 3), dtype=dt, device=device) if on else None
+    out_v, out_f = new(Vk, _f32), new(Fk, _i32)
+    out_n, out_c = new(Vk, _f32, mesh.normals is not None), new(Vk, _f32, colors is not None)
+    sums = torch.empty((Vk, 9), dtype=torch.int64, device=device)
+    counts = torch.empty((Vk,), dtype=_i32, device=device)
+    check(tool("scanerf_mesh_simplify_emit")(*head, sums.data_ptr(), counts.data_ptr(), out_v.data_ptr(), out_f.data_ptr() if Fk else None,
+                                             ptr(out_n), ptr(out_c), Vk, Fk, stream()), "mesh_simplify_emit")
+    return out_v, out_f, out_n, out_c, counts
+
+
+def simplify_mesh(mesh, cell, origin=(0.0, 0.0, 0.0), colors=None, route="fused", report=None):
+    """Simplify a Mesh by vertex clustering (the definition: include/scanerf_mesh_tools_hip.h, scanerf_mesh_simplify_cluster): the
+    vertices in one cell of the world grid of cubic cells of side `cell` at `origin` become one vertex at their (fixed-point) mean,
+    with the mean normal (renormalised) and, with colors [V,3] f32, the mean colour; faces are re-indexed, those that lose a corner
+    disappear, the rest keep their order and winding.  Output vertices follow the input's order (a cluster stands where its first
+    member stood); a cluster of one member is that member, bit for bit.  -> Mesh with cells=None, lattice=None and normals iff the
+    input has them, or (Mesh, colors) when colors are given.  route="fused": a lock-free table and integer atomics on the GPU, one
+    host read of (V', F', n_bad); route="composed": torch.unique / scatter_reduce / index_add_ / cumsum (the witness).  Both give
+    the same bits.  A vertex that is not finite, has a non-finite attribute or lies 2^20 cells or more from the origin is an error.
+    report: a dict that receives clusters, largest_cluster and vertices / faces as (before, after)."""
+    V, F, h, o = _simplify_args(mesh, cell, origin, colors, route)
+    device = mesh.vertices.device
+    if V == 0:
+        e = lambda dt, on=True: torch.empty((0, 3), dtype=dt, device=device) if on else None
+        out = (e(_f32), e(_i32), e(_f32, mesh.normals is not None), e(_f32, colors is not None), None)
+    else:
+        out = (_simplify_composed if route == "composed" else _simplify_fused)(mesh, colors, V, F, h, o)
+    if report is not None:
+        report.update(clusters=int(out[0].shape[0]), largest_cluster=int(out[4].max()) if V else 0,
+                      vertices=(V, int(out[0].shape[0])), faces=(F, int(out[1].shape[0])))
+    simplified = Mesh(out[0], out[1], None, None, out[2])
+    return simplified if colors is None else (simplified, out[3])
+
+
+_SIMPLIFY_ROUTE = {"fused": "fused", "dense": "composed"}      # the extractors' witness route composes the simplification too
+
+
+def _simplify_rule(simplify):
+    """The extractors' simplify argument, checked before any launch."""
+    if simplify is not None:
+        _simplify_cell(simplify)
+
+
+def _simplified(mesh, simplify, colors, report, route="fused"):
+    """The extractors' last step: simplify=None leaves the mesh (and the colours) as they are."""
+    if simplify is None:
+        return mesh if colors is None else (mesh, colors)
+    sub = {} if report is not None else None
+    out = simplify_mesh(mesh, simplify, colors=colors, route=route, report=sub)
+    if report is not None:
+        report["simplify"] = sub
+    return out
 
 
 def cells_per_axis(occ_size, longest):

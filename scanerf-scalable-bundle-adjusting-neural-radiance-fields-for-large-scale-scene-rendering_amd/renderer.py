@@ -286,7 +286,7 @@ class TileSetRenderer:
 
     @torch.no_grad()
     def extract_mesh(self, level, cells_per_axis=256, box=None, route="fused", normals=False, min_faces=0, min_extent=0,
-                     keep_largest=None, report=None, cameras=None, min_views=0, view_bias=None, view_far=None):
+                     keep_largest=None, report=None, cameras=None, min_views=0, view_bias=None, view_far=None, simplify=None):
         """ONE mesh of the whole scene: the level set sigma == level of the density this renderer draws, the tiles' densities blended
         per point with the render-time weights (meshing.extract_scene_mesh).  box = (corner, size) of the world box
         the lattice covers (default: scene_box()), with cells_per_axis cells along its longest side.  normals=True: the vertex normals,
@@ -294,7 +294,7 @@ class TileSetRenderer:
         keep_largest: meshing.filter_mesh's keep rule (floaters and unused vertices go), applied before the normals
         are evaluated; report: a dict that receives the component count and the rows before and after.  cameras = (ks, c2ws, H, W)
         with min_views >= 1: the parts no camera saw go first (meshing.cull_unseen; view_bias: half a lattice spacing
-        by default).  -> meshing.Mesh."""
+        by default).  simplify=cell: meshing.simplify_mesh as the last step.  -> meshing.Mesh."""
         from . import meshing
         corner, size = self.scene_box() if box is None else box
         size = [float(v) for v in size]
@@ -302,7 +302,7 @@ class TileSetRenderer:
                                           self.occupied_grid, self.grid_starts, self.grid_log2dim, corner, size,
                                           meshing.cells_per_axis(size, cells_per_axis), level, route=route, normals=normals,
                                           min_faces=min_faces, min_extent=min_extent, keep_largest=keep_largest, report=report,
-                                          cameras=cameras, min_views=min_views, view_bias=view_bias, view_far=view_far)
+                                          cameras=cameras, min_views=min_views, view_bias=view_bias, view_far=view_far, simplify=simplify)
 
     @torch.no_grad()
     def evaluate_mesh(self, gt, level, cells_per_axis=256, n_samples=200000, thresholds=(0.05,), max_dist=float("inf"), seed=0,
@@ -320,7 +320,8 @@ class TileSetRenderer:
 
     @torch.no_grad()
     def fuse_mesh(self, cameras, cells_per_axis=256, box=None, trunc=None, max_transparency=0.5, scale=1, views_per_batch=8,
-                  min_weight=1, min_faces=0, min_extent=0, keep_largest=None, report=None, colors=None, normals=False, **render_kw):
+                  min_weight=1, min_faces=0, min_extent=0, keep_largest=None, report=None, colors=None, normals=False, simplify=None,
+                  **render_kw):
         """ONE mesh of what the cameras saw (fusion.py): cameras = (ks [C,3,3], c2ws [C,3,4], H, W), typically the
         capture's.  Each camera is rendered at H // scale x W // scale (K scaled as fusion.scale_cameras does; render_kw goes to
         render), its depth set to 0 where the transparency exceeds max_transparency or the depth is not finite (fusion.mask_depth),
@@ -330,8 +331,10 @@ class TileSetRenderer:
         colors: "diffuse" also fuses clamp(diffuse, 0, 1) of the same renders (the view-independent part: the
         sensible colour of a mesh), "rgb" clamp(diffuse + specular, 0, 1) (the image shown everywhere else), batched with the depth
         maps; -> (mesh, rgb [V,3] f32), the mesh the one of the call without colours.  None: no colour, the Mesh alone.
-        normals=True: the Mesh carries the volume's gradient normals (TSDFVolume.vertex_normals)."""
+        normals=True: the Mesh carries the volume's gradient normals (TSDFVolume.vertex_normals).
+        simplify=cell: TSDFVolume.extract's last step, meshing.simplify_mesh on the world grid of that cell."""
         from . import fusion, meshing
+        meshing._simplify_rule(simplify)
         if not isinstance(normals, bool):
             raise RuntimeError(f"scanerf: normals must be True or False, got {normals!r}")
         if colors not in (None, "diffuse", "rgb"):
@@ -368,4 +371,5 @@ class TileSetRenderer:
                     images.append(fusion.clamped_image(diffuse, specular if colors == "rgb" else None))
             vol.integrate(torch.stack(maps).contiguous(), ks[i:i + vpb], c2ws[i:i + vpb],
                           colors=torch.stack(images).contiguous() if colors is not None else None)
-        return vol.extract(min_weight, min_faces, min_extent, keep_largest, report, colors=colors is not None, normals=normals)
+        return vol.extract(min_weight, min_faces, min_extent, keep_largest, report, colors=colors is not None, normals=normals,
+                           simplify=simplify)

@@ -4,7 +4,7 @@
     python tools/extract_scene_mesh.py TILEDIR [TILEDIR ...] --level SIGMA [--cells-per-axis 256]
                                        [--box X Y Z SX SY SZ] --out FILE.ply [--normals] [--route fused|dense] [--gpu 0]
                                        [--min-faces N] [--min-extent CELLS] [--keep-largest K]
-                                       [--cameras camera.log --min-views N [--view-bias B] [--view-far D]]
+                                       [--cameras camera.log --min-views N [--view-bias B] [--view-far D]] [--simplify CELL]
                                        [--compare GT.ply --threshold T [T ...] [--samples N] [--max-dist D] [--log2dim L] [--seed S]
                                         [--normal-consistency]]
 
@@ -17,7 +17,8 @@ gradient, weight terms included.  --min-faces / --min-extent / 
 connected component before the normals are evaluated (meshing.filter_mesh); the component count and the rows before
 and after are printed either way.  --cameras camera.log --min-views N first drops the faces none of whose vertices N of the log's
 cameras see (the mesh itself occluding; meshing.cull_unseen; --view-bias: half a lattice spacing by default,
---view-far: the cameras' range).  --compare GT.ply prints, after the PLY is written, the geometric score of the mesh against GT.ply
+--view-far: the cameras' range).  --simplify CELL clusters the finished mesh on the world grid of cubic cells of side CELL as the last
+step, the normals averaged with the vertices (meshing.simplify_mesh).  --compare GT.ply prints, after the PLY is written, the geometric score of the mesh against GT.ply
 (e.g. the dataset's scan) as the one JSON line of tools/compare_meshes.py.  tools/extract_mesh.py writes one open mesh per tile instead."""
 import argparse
 import os
@@ -44,6 +45,8 @@ def parser():
     ap.add_argument("--min-views", type=int, default=0, metavar="N", help="keep a face iff N cameras see one of its vertices (needs --cameras)")
     ap.add_argument("--view-bias", type=float, default=None, metavar="B", help="start of a sight line, off the vertex (default: half a lattice spacing)")
     ap.add_argument("--view-far", type=float, default=None, metavar="D", help="the cameras' range (default: no limit)")
+    ap.add_argument("--simplify", type=float, default=None, metavar="CELL",
+                    help="last step: cluster the vertices on a world grid of cells of this side (world units)")
     ap.add_argument("--gpu", type=int, default=0)
     ap.add_argument("--compare", default=None, metavar="GT.ply",
                     help="after writing the PLY, print the geometric score of the mesh against GT.ply as one JSON line (needs --threshold)")
@@ -67,7 +70,7 @@ def main(argv=None):
     cameras = formats.read_campara(args.cameras, return_shape=True) if args.cameras else None
     mesh = rnd.extract_mesh(args.level, args.cells_per_axis, box=box, route=args.route, normals=args.normals, min_faces=args.min_faces,
                             min_extent=args.min_extent, keep_largest=args.keep_largest, report=report, cameras=cameras,
-                            min_views=args.min_views, view_bias=args.view_bias, view_far=args.view_far)
+                            min_views=args.min_views, view_bias=args.view_bias, view_far=args.view_far, simplify=args.simplify)
     out_dir = os.path.dirname(os.path.abspath(args.out))
     os.makedirs(out_dir, exist_ok=True)
     formats.write_ply(args.out, mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy(),
@@ -79,6 +82,10 @@ def main(argv=None):
         cull, hist = report["cull"], report["cull"]["views_histogram"]
         print(f"{args.out}: unseen parts culled first: vertices {cull['vertices'][0]} -> {cull['vertices'][1]}, faces {cull['faces'][0]} -> "
               f"{cull['faces'][1]}; {hist[0] if hist else 0} vertices seen by no camera, at most {max(len(hist) - 1, 0)} views")
+    if args.simplify is not None:
+        simp = report["simplify"]
+        print(f"{args.out}: simplified at cell {args.simplify:g}: vertices {simp['vertices'][0]} -> {simp['vertices'][1]}, faces "
+              f"{simp['faces'][0]} -> {simp['faces'][1]}")
     if args.compare:
         print(evaluation.score_line((mesh.vertices, mesh.faces), args.compare, args, mesh.vertices.device))
     return 0

@@ -5,7 +5,7 @@ distance volume, the zero set written as a PLY.
     python tools/fuse_mesh.py TILEDIR [TILEDIR ...] --cameras camera.log --out FILE.ply [--cells-per-axis 256]
                               [--box X Y Z SX SY SZ] [--trunc T] [--min-weight N] [--scale S] [--max-transparency A]
                               [--views-per-batch B] [--min-faces N] [--min-extent CELLS] [--keep-largest K] [--gpu 0]
-                              [--colors diffuse|rgb] [--normals]
+                              [--colors diffuse|rgb] [--normals] [--simplify CELL]
                               [--compare GT.ply --threshold T [T ...] [--samples N] [--max-dist D] [--log2dim L] [--seed S]
                                [--normal-consistency]]
 
@@ -20,6 +20,8 @@ zero set, in world units; what no ray stopped at never enters it.  Faces that to
 `diffuse` the view-independent part, `rgb` diffuse + specular, each clamped to [0, 1]; a vertex no camera coloured is mid grey.
 --normals writes nx / ny / nz per vertex: the volume's own gradient at the vertex, pointing out of the surface (DESIGN.md 4.22);
 with --colors one PLY holds both.
+--simplify CELL clusters the finished mesh on the world grid of cubic cells of side CELL (world units) as the last step, the normals
+and colours averaged with the vertices (meshing.simplify_mesh): fuse fine, hand out coarse.
 --compare GT.ply prints the geometric score against GT.ply as the one JSON line of tools/compare_meshes.py.
 tools/extract_scene_mesh.py cuts the density's level set instead."""
 import argparse
@@ -50,6 +52,8 @@ def parser():
     ap.add_argument("--colors", choices=("diffuse", "rgb"), default=None,
                     help="also fuse the renders' colours and write them as red / green / blue per vertex")
     ap.add_argument("--normals", action="store_true", help="also write nx / ny / nz per vertex: the volume's gradient normals")
+    ap.add_argument("--simplify", type=float, default=None, metavar="CELL",
+                    help="last step: cluster the vertices on a world grid of cells of this side (world units)")
     ap.add_argument("--compare", default=None, metavar="GT.ply",
                     help="after writing the PLY, print the geometric score of the mesh against GT.ply as one JSON line (needs --threshold)")
     import scanerf_amd  # noqa: F401
@@ -71,7 +75,7 @@ def main(argv=None):
     mesh = rnd.fuse_mesh(cameras, args.cells_per_axis, box=box, trunc=args.trunc, max_transparency=args.max_transparency, scale=args.scale,
                          views_per_batch=args.views_per_batch, min_weight=args.min_weight, min_faces=args.min_faces,
                          min_extent=args.min_extent, keep_largest=args.keep_largest, report=report, colors=args.colors,
-                         normals=args.normals)
+                         normals=args.normals, simplify=args.simplify)
     rgb = None
     if args.colors:
         mesh, rgb = mesh
@@ -87,6 +91,10 @@ def main(argv=None):
         print(f"{args.out}: colours ({args.colors}): {report['color']} of {mesh.vertices.shape[0]} vertices uncoloured")
     if args.normals:
         print(f"{args.out}: normals: {report['normals']} of {mesh.vertices.shape[0]} vertices with a zero normal")
+    if args.simplify is not None:
+        simp = report["simplify"]
+        print(f"{args.out}: simplified at cell {args.simplify:g}: vertices {simp['vertices'][0]} -> {simp['vertices'][1]}, faces "
+              f"{simp['faces'][0]} -> {simp['faces'][1]}")
     if args.compare:
         print(evaluation.score_line((mesh.vertices, mesh.faces), args.compare, args, mesh.vertices.device))
     return 0
