@@ -206,6 +206,60 @@ int scanerf_mesh_simplify_emit(const float *vertices, const int32_t *faces, cons
                                int32_t *counts, float *out_vertices, int32_t *out_faces, float *out_normals, float *out_colors,
                                int Vout, int Fout, scanerf_stream_t stream);
 
+/* ---- the hit record of the tracer, and a mesh rendered with its vertex attributes through a set of cameras (csrc/mesh_render.hip;
+ *   DESIGN.md 4.24).  What "look at the coloured mesh from the capture's cameras" needs.  The reference has no counterpart; the
+ *   definition is this comment.  Everything below is float32, operation by operation, without FMA contraction.
+ *   The tracer's arrays are taken as scanerf_mesh_first_hit takes them (tris != NULL: pre-gathered triangles, else vertices / faces),
+ *     but cell_faces is ALWAYS required: it names the faces.  log2dim 4..7.
+ *   scanerf_mesh_trace: rays_o, rays_d [B,3] -> t [B] f32, face [B] i32, bary [B,2] f32 = (u, v).
+ *     The walk is scanerf_mesh_first_hit's: the same cells in the same order, the same ray / triangle test (Moeller-Trumbore,
+ *     two-sided, edges inclusive, |det| <= 1e-12 is a dead face that is never returned, t > 0) on the same operands
+ *     (A, B - A, C - A), the same stop rule (the walk ends after the first cell whose exit t1 >= the candidate's t).  t has the bits
+ *     scanerf_mesh_first_hit writes for the ray, at every log2dim and in both triangle forms.
+ *     Candidates are compared as (t, face index): a later face, or a later cell, replaces the candidate only with a smaller t, or an
+ *     equal t and a lower index.  face is therefore the lowest index, AMONG THE FACES THE WALK TESTED, that attains t: a face that
+ *     ties the answer exactly at the exit of the cell the walk stops in, and is registered only in cells beyond it, goes untested.
+ *     u, v are Moeller-Trumbore's for that face: with p = d x e2, w = o - A, q = w x e1, inv = 1 / (e1 . p) (dot products summed
+ *     left to right, each cross component two products and one subtraction): u = (w . p) inv, v = (d . q) inv, t = (e2 . q) inv.
+ *     The hit point is A + u e1 + v e2.
+ *     A MISS gives t = 0, face = -1, u = v = 0: no face hit, a ray that misses the grid cube, non-finite input (its walk ends at
+ *     the step cap).
+ *   scanerf_mesh_trace_brute (the witness): the same outputs from the same device function over the faces 0 .. F-1 in order, no
+ *     grid.  A face answers iff the build registers it (indices in [0, V), box not outside the cube, cell > 0); a ray answers iff
+ *     it meets the grid cube (the first-hit walk's clip).  It tests every face, so its face is the lowest index over ALL faces.
+ *   scanerf_mesh_render_views: C cameras in one launch.  Ks [C,9], C2Ws [C,12] f32 row-major; the image size H, W; vertices and
+ *     faces are required here (the attributes are gathered by vertex index); vertex_normals [V,3], vertex_colors [V,3] f32 or NULL.
+ *     The ray of pixel (px, py) of camera c, K = Ks[c], M = C2Ws[c], is scanerf_compute_ray_forward's, operation for operation:
+ *       x = (1.0f px + 0.5f - K[2]) / K[0];  y = (1.0f py + 0.5f - K[5]) / K[4];
+ *       d_a = (M[4a] x + M[4a+1] y) + M[4a+2], a = 0, 1, 2;  o = (M[3], M[7], M[11]).
+ *     The camera-z component of d is 1, so t is z-depth: what scanerf_tsdf_integrate reads.  No ray is stored.
+ *     The hit is scanerf_mesh_trace's.  With (ia, ib, ic) = the face's vertex indices and w0 = (1 - u) - v, a vertex attribute a
+ *     becomes a = (w0 a[ia] + u a[ib]) + v a[ic] per component.
+ *     Outputs: depth [C,H,W] f32 = t; face [C,H,W] i32; normal [C,H,W,3] f32 or NULL (not written); color [C,H,W,3] f32 or NULL
+ *       (not written; a non-NULL color needs vertex_colors).
+ *     normal: n = the interpolated vertex normal, or with vertex_normals == NULL the face normal e1 x e2 (each component two
+ *       products and one subtraction; its orientation follows the winding); then n_a / (sqrtf((nx nx + ny ny) + nz nz) + 1e-8f).
+ *     color: the interpolated vertex colour, as it is.
+ *     A miss writes depth 0, face -1, normal 0, colour 0.
+ *     A wavefront owns an 8 x 8 pixel block of one camera (partial blocks at the right and bottom borders are masked); the output
+ *       bits do not depend on that mapping.
+ *   Every element of every output is written exactly once by a plain store and nothing else is written: two launches give equal bits.
+ *   B == 0 and C == 0 launch nothing.  Refused before any launch (nothing written): B < 0 or B > 2^29; null pointers (but tris,
+ *     and vertices / faces where tris is given, in scanerf_mesh_trace; tris, vertex_normals, vertex_colors, normal, color in
+ *     scanerf_mesh_render_views; vertices / faces with F == 0 in the brute entry); V or F < 0; C < 0; H or W < 1; C H W >= 2^31;
+ *     log2dim outside 4..7; a color output without vertex_colors.
+ *   No allocation, no host synchronisation, no atomics, no scratch; every launch on `stream`. */
+int scanerf_mesh_trace(const float *rays_o, const float *rays_d, int B, const float *vertices, const int32_t *faces, const float *tris,
+                       const uint64_t *bitmask, const uint32_t *rank, const int32_t *start_num, const int32_t *cell_faces,
+                       const float *scene_info, int log2dim, float *t, int32_t *face, float *bary, scanerf_stream_t stream);
+int scanerf_mesh_trace_brute(const float *rays_o, const float *rays_d, int B, const float *vertices, const int32_t *faces, int V, int F,
+                             const float *scene_info, int log2dim, float *t, int32_t *face, float *bary, scanerf_stream_t stream);
+int scanerf_mesh_render_views(const float *Ks, const float *C2Ws, int C, int H, int W, const float *vertices, const int32_t *faces,
+                              const float *tris, const uint64_t *bitmask, const uint32_t *rank, const int32_t *start_num,
+                              const int32_t *cell_faces, const float *scene_info, int log2dim, const float *vertex_normals,
+                              const float *vertex_colors, float *depth, int32_t *face, float *normal, float *color,
+                              scanerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

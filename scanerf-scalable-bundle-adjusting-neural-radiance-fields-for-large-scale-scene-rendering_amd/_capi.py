@@ -147,6 +147,9 @@ TOOL_PROTOTYPES = {
     "scanerf_mesh_simplify_scratch_bytes": ("I", "IIP"),
     "scanerf_mesh_simplify_cluster": ("I", "PPPPIIPFPZP"),
     "scanerf_mesh_simplify_emit": ("I", "PPPPIIPFPZPPPPPPIIP"),
+    "scanerf_mesh_trace": ("I", "PPIPPPPPPPPIPPPP"),
+    "scanerf_mesh_trace_brute": ("I", "PPIPPIIPIPPPP"),
+    "scanerf_mesh_render_views": ("I", "PPIIIPPPPPPPPIPPPPPPP"),
 }
 CTYPES = {"P": ctypes.c_void_p, "I": ctypes.c_int, "U": ctypes.c_uint, "F": ctypes.c_float, "Z": ctypes.c_size_t,
           "L": ctypes.c_int64, "S": ctypes.c_char_p}

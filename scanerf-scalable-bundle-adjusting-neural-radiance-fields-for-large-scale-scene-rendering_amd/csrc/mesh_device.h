@@ -1,5 +1,5 @@
-// mesh_device.h -- the device side of the ray / triangle-mesh tracer shared by its kernels: the traces of mesh.hip and the fused
-// view-coverage kernel of coverage.hip.  The structure's arrays are described in mesh.hip.  Include only from files built with
+// mesh_device.h -- the device side of the ray / triangle-mesh tracer shared by its kernels: the traces of mesh.hip, the fused
+// view-coverage kernel of coverage.hip and the hit-record kernels of mesh_render.hip.  The structure's arrays are described in mesh.hip.  Include only from files built with
 // -ffp-contract=off (dda_device.h).  Everything here sits in an unnamed namespace, as it did inside mesh.hip: Grid is a kernel
 // parameter, so its namespace is part of the kernels' names in csrc/isa_manifest.json.
 #pragma once
@@ -133,6 +133,111 @@ __device__ __forceinline__ float first_hit_walk(const float o[3], const float d[
         }
     }
     return best < kInf ? best : 0.0f;
+}
+
+// ---- the hit record (mesh_render.hip; include/scanerf_mesh_tools_hip.h): which face, and where on it ----------------------------
+
+struct TriHit {
+    float t, u, v;   // t = -1: no intersection (u, v then mean nothing)
+};
+
+// ray_triangle with its barycentrics kept: the same operations in the same order, so t has ray_triangle's bits.
+__device__ __forceinline__ TriHit ray_triangle_uv(const float o[3], const float d[3], const float A[3], const float e1[3], const float e2[3])
+{
+    TriHit r = { -1.0f, 0.0f, 0.0f };
+    const float p[3] = { d[1] * e2[2] - d[2] * e2[1], d[2] * e2[0] - d[0] * e2[2], d[0] * e2[1] - d[1] * e2[0] };
+    const float det = e1[0] * p[0] + e1[1] * p[1] + e1[2] * p[2];
+    if (!(fabsf(det) > 1e-12f)) return r;
+    const float inv = 1.0f / det;
+    const float tv[3] = { o[0] - A[0], o[1] - A[1], o[2] - A[2] };
+    const float u = (tv[0] * p[0] + tv[1] * p[1] + tv[2] * p[2]) * inv;
+    const float q[3] = { tv[1] * e1[2] - tv[2] * e1[1], tv[2] * e1[0] - tv[0] * e1[2], tv[0] * e1[1] - tv[1] * e1[0] };
+    const float v = (d[0] * q[0] + d[1] * q[1] + d[2] * q[2]) * inv;
+    const float t = (e2[0] * q[0] + e2[1] * q[1] + e2[2] * q[2]) * inv;
+    if (u >= 0.0f && v >= 0.0f && u + v <= 1.0f && t > 0.0f) {
+        r.t = t;
+        r.u = u;
+        r.v = v;
+    }
+    return r;
+}
+
+// The nearest hit as (t, face, u, v).  Candidates are compared as (t, face index): a later face or a later cell replaces the
+// candidate only with a smaller t, or an equal t and a lower index, so the answer does not depend on the order of the tests.
+struct HitRecord {
+    float t;
+    int face;
+    float u, v;
+    __device__ __forceinline__ void clear()
+    {
+        t = kInf;
+        face = 0x7fffffff;
+        u = v = 0.0f;
+    }
+    __device__ __forceinline__ void offer(const float o[3], const float d[3], const float A[3], const float e1[3], const float e2[3], int f)
+    {
+        const TriHit h = ray_triangle_uv(o, d, A, e1, e2);
+        if (h.t > 0.0f && (h.t < t || (h.t == t && f < face))) {   // (a NaN is never taken)
+            t = h.t;
+            face = f;
+            u = h.u;
+            v = h.v;
+        }
+    }
+    // the miss: t = 0, face = -1, u = v = 0
+    __device__ __forceinline__ void finish()
+    {
+        if (!(t < kInf)) {
+            t = 0.0f;
+            face = -1;
+            u = v = 0.0f;
+        }
+    }
+};
+
+// first_hit_walk with the record kept: the same cells, the same tests, the same stop rule (the candidate's t against the cell's
+// exit), so t has first_hit_walk's bits.  cell_faces names the faces in both triangle forms.  A face that ties the candidate
+// exactly at the exit of the cell the walk stops in, and is registered only beyond it, is never tested: face is the lowest index
+// among the faces the walk tested.
+template <bool LDS, bool PRE>
+__device__ __forceinline__ HitRecord hit_record_walk(const float o[3], const float d[3], const Grid &g, const Words<LDS> &words,
+                                                     const float *__restrict__ vertices, const int32_t *__restrict__ faces,
+                                                     const int32_t *__restrict__ cell_faces, const float *__restrict__ tris)
+{
+    HitRecord best;
+    best.clear();
+    RayWalk rw;
+    if (rw.start(o, d, g)) {
+        while (!rw.done()) {
+            rw.w.pick();
+            const int c = words.lookup(rw.cell(g.L));
+            if (c >= 0) {
+                const int start = g.start_num[2 * c], num = g.start_num[2 * c + 1];
+                for (int k = 0; k < num; ++k) {
+                    const int f = cell_faces[start + k];
+                    float A[3], e1[3], e2[3];
+                    if (PRE) {
+                        const float *t = tris + 9 * (size_t)(start + k);
+#pragma unroll
+                        for (int a = 0; a < 3; ++a) { A[a] = t[a]; e1[a] = t[3 + a]; e2[a] = t[6 + a]; }
+                    } else {
+                        const int ia = faces[3 * f], ib = faces[3 * f + 1], ic = faces[3 * f + 2];
+#pragma unroll
+                        for (int a = 0; a < 3; ++a) {
+                            A[a] = vertices[3 * ia + a];
+                            e1[a] = vertices[3 * ib + a] - A[a];
+                            e2[a] = vertices[3 * ic + a] - A[a];
+                        }
+                    }
+                    best.offer(o, d, A, e1, e2, f);
+                }
+            }
+            if (best.t <= rw.w.t1) break;   // nothing in a later cell can be nearer
+            rw.w.advance();
+        }
+    }
+    best.finish();
+    return best;
 }
 
 }  // namespace

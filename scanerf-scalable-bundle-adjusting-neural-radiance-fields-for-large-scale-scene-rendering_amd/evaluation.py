@@ -3,6 +3,9 @@ the other mesh (FastMesh.closest_point, csrc/mesh_distance.hip -- the hot step),
 (gt -> pred), chamfer distance, precision / recall / F-score at distance thresholds, and on request normal consistency (DESIGN.md 4.22:
 the dot product of the sampled face's and the nearest face's unit normals).  The reference scores images only
 (postprocess/evaluation.py: PSNR / SSIM, here TileTrainer.validate); it has no geometric score.
+The image-space score: render_mesh draws a mesh with its vertex colours and normals at the capture's cameras
+(FastMesh.render_views, csrc/mesh_render.hip) and compare_renders sets those images against the field's renders there: coverage, depth
+error, PSNR over the jointly covered pixels, normal angle.
 
 sample_surface and the reductions are torch ops: they touch each sample once and are not a hot path (the query is)."""
 import math
@@ -195,3 +198,161 @@ def score_line(pred, gt, args, device, distances=None):
     if distances is not None:
         save_distances(distances, res)
     return json_line(res)
+
+
+# ---- image-space score of a mesh: the mesh rendered at the capture's cameras against the field's renders there ----------
+def _render_mesh_inputs(mesh, colors, normals, device):
+    """-> vertices, faces, vertex normals or None, vertex colours or None, want_normals."""
+    vn = None
+    if hasattr(mesh, "_fields") and "vertices" in mesh._fields:          # meshing.Mesh
+        vn = getattr(mesh, "normals", None)
+        mesh = (mesh.vertices, mesh.faces)
+    if device is None:
+        device = mesh[0].device if isinstance(mesh, (tuple, list)) and isinstance(mesh[0], torch.Tensor) and mesh[0].is_cuda else \
+            torch.device("cuda", torch.cuda.current_device())
+    v, f = _mesh_arrays(mesh, device)
+    if isinstance(normals, bool):
+        vn = vn if normals else None
+        want = normals
+    elif normals is None:
+        vn, want = None, False
+    else:
+        vn, want = normals, True
+    as_rows = lambda a, name: None if a is None else _rows(a, v.shape[0], name, device)
+    return v, f, as_rows(vn, "normals"), as_rows(colors, "colors"), want
+
+
+def _rows(a, V, name, device):
+    a = torch.as_tensor(a)
+    if a.dim() != 2 or tuple(a.shape) != (V, 3) or not a.dtype.is_floating_point:
+        raise RuntimeError(f"scanerf: {name} must be [V,3] floating point with V={V}, got {tuple(a.shape)} {a.dtype}")
+    return a.to(device=device, dtype=_f32).contiguous()
+
+
+@torch.no_grad()
+def render_mesh(mesh, cameras, colors=None, normals=True, log2dim=6, views_per_batch=8, device=None, collect=False):
+    """The mesh seen from cameras = (ks [C,3,3], c2ws [C,3,4], H, W) (FastMesh.render_views, csrc/mesh_render.hip -- the hot step).
+    mesh: (vertices, faces), a PLY path or a meshing.Mesh; colors: vertex colours [V,3] in 0..1, or None; normals: True = a normal map
+    from the Mesh's vertex normals (interpolated) or, where it has none, from the face normals; False / None = no normal map; an
+    array [V,3] = those vertex normals.  The FastMesh is built once (log2dim); the cameras are rendered views_per_batch at a time.
+    -> an iterator of (first view index, {"depth" [B,H,W], "face" [B,H,W], "normal" [B,H,W,3], "color" [B,H,W,3]}): one batch of
+    images exists at a time.  collect=True: one dict with all C views instead."""
+    from .fastmesh import FastMesh
+    from .fusion import _views_per_batch
+    vpb = _views_per_batch(views_per_batch)
+    if cameras is None or len(cameras) != 4:
+        raise RuntimeError("scanerf: render_mesh needs cameras=(ks, c2ws, H, W)")
+    ks, c2ws, H, W = cameras
+    v, f, vn, vc, want = _render_mesh_inputs(mesh, colors, normals, device)
+    fm = FastMesh.from_arrays(v, f, v.device, log2dim)
+    ks, c2ws = torch.as_tensor(ks), torch.as_tensor(c2ws)
+    C = int(ks.shape[0])
+
+    def batches():
+        for i in range(0, C, vpb):
+            yield i, fm.render_views(ks[i:i + vpb], c2ws[i:i + vpb], H, W, normals=vn, colors=vc, want_normals=want)
+    if not collect:
+        return batches()
+    parts = [b for _, b in batches()]
+    if not parts:
+        return fm.render_views(ks, c2ws, H, W, normals=vn, colors=vc, want_normals=want)
+    return {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+
+
+class RenderScore:
+    """compare_renders, fed batch by batch: add(pred, target) any number of times, then result().  It keeps per-view figures and
+    float64 sums, never an image."""
+
+    def __init__(self, max_depth_diff=None):
+        if max_depth_diff is not None and not float(max_depth_diff) >= 0.0:
+            raise ValueError(f"scanerf: max_depth_diff must be >= 0 or None, got {max_depth_diff!r}")
+        self.max_depth_diff = None if max_depth_diff is None else float(max_depth_diff)
+        self.views = []
+        self.sums = None
+        self.has_color = self.has_normal = None
+
+    @staticmethod
+    def _figures(s, has_color, has_normal):
+        nan = float("nan")
+        div = lambda a, b: a / b if b else nan
+        out = {"coverage": div(s["joint"], s["either"]), "pred_only": div(s["pred_only"], s["either"]),
+               "target_only": div(s["target_only"], s["either"]), "depth_abs_mean": div(s["abs"], s["joint"]),
+               "depth_rmse": math.sqrt(s["sq"] / s["joint"]) if s["joint"] else nan}
+        if has_color:
+            out["psnr"] = 10.0 * math.log10(255.0 ** 2 / (s["color_sq"] / s["color_n"] + 1e-8)) if s["color_n"] else nan
+        if has_normal:
+            out["normal_deg_mean"] = div(s["angle"], s["angle_n"])
+        return out
+
+    def add(self, pred, target):
+        dp, dt = torch.as_tensor(pred["depth"]), torch.as_tensor(target["depth"])
+        if dp.dim() != 3 or dp.shape != dt.shape:
+            raise RuntimeError(f"scanerf: compare_renders needs depth [C,H,W] on both sides, got {tuple(dp.shape)} and {tuple(dt.shape)}")
+        dt = dt.to(dp.device)
+        has_color = "color" in pred and "color" in target
+        has_normal = "normal" in pred and "normal" in target
+        if self.has_color is None:
+            self.has_color, self.has_normal = has_color, has_normal
+        elif (self.has_color, self.has_normal) != (has_color, has_normal):
+            raise RuntimeError("scanerf: compare_renders: the batches do not carry the same maps")
+        for name, on in (("color", has_color), ("normal", has_normal)):
+            if on and (tuple(pred[name].shape) != tuple(dp.shape) + (3,) or tuple(target[name].shape) != tuple(dp.shape) + (3,)):
+                raise RuntimeError(f"scanerf: compare_renders: {name} must be [C,H,W,3] on both sides")
+        from . import metrics
+        for c in range(dp.shape[0]):
+            a, b = dp[c].to(_f64), dt[c].to(_f64)
+            P, T = torch.isfinite(a) & (a > 0), torch.isfinite(b) & (b > 0)
+            J = P & T
+            diff = (a - b)[J]
+            s = {"joint": int(J.sum()), "either": int((P | T).sum()), "pred_only": int((P & ~T).sum()),
+                 "target_only": int((T & ~P).sum()), "abs": float(diff.abs().sum()), "sq": float(diff.square().sum()),
+                 "color_sq": 0.0, "color_n": 0, "angle": 0.0, "angle_n": 0}
+            S = J if self.max_depth_diff is None else J & ((a - b).abs() <= self.max_depth_diff)
+            view_psnr = None
+            if has_color:
+                cp = pred["color"][c][S].to(_f32) * 255.0
+                ct = target["color"][c].to(dp.device)[S].to(_f32) * 255.0
+                s["color_n"] = int(cp.numel())
+                s["color_sq"] = float((cp.to(_f64) - ct.to(_f64)).square().sum())
+                view_psnr = metrics.psnr(cp, ct) if s["color_n"] else float("nan")
+            if has_normal:
+                np_, nt = pred["normal"][c][S].to(_f64), target["normal"][c].to(dp.device)[S].to(_f64)
+                lp, lt = np_.norm(dim=1), nt.norm(dim=1)
+                ok = (lp > 0) & (lt > 0) & torch.isfinite(lp) & torch.isfinite(lt)
+                cos = ((np_[ok] / lp[ok, None]) * (nt[ok] / lt[ok, None])).sum(1).clamp(-1.0, 1.0)
+                s["angle_n"] = int(ok.sum())
+                s["angle"] = float(torch.rad2deg(torch.acos(cos)).sum())
+            fig = self._figures(s, has_color, has_normal)
+            if view_psnr is not None:
+                fig["psnr"] = view_psnr
+            self.views.append(fig)
+            self.sums = dict(s) if self.sums is None else {k: self.sums[k] + s[k] for k in s}
+        return self
+
+    def result(self):
+        zero = {k: 0 for k in ("joint", "either", "pred_only", "target_only", "abs", "sq", "color_sq", "color_n", "angle", "angle_n")}
+        return {"n_views": len(self.views), "max_depth_diff": self.max_depth_diff, "per_view": list(self.views),
+                "pooled": self._figures(self.sums or zero, bool(self.has_color), bool(self.has_normal))}
+
+
+def compare_renders(pred, target, max_depth_diff=None):
+    """Two sets of renders of the same cameras, pixel against pixel.  pred, target: {"depth": [C,H,W]} and optionally "color"
+    [C,H,W,3] in 0..1 and "normal" [C,H,W,3] (any length; 0 = none), tensors or arrays.  A render COVERS a pixel iff its depth there
+    is finite and > 0.  With P, T the covered sets, J = P and T (jointly covered), E = P or T, per view, in float64:
+        coverage = |J| / |E|;  pred_only = |P - T| / |E|;  target_only = |T - P| / |E|       (the three add up to 1)
+        depth_abs_mean = mean over J of |d_pred - d_target|;  depth_rmse = sqrt(mean over J of (d_pred - d_target)^2)
+        psnr (only when both sides have "color") = metrics.psnr(255 pred, 255 target) over the pixels S:
+            10 log10(255^2 / (mse + 1e-8)), mse the mean over the 3 |S| values
+        normal_deg_mean (only when both sides have "normal") = the mean angle in degrees, acos of the clamped dot product of the two
+            normalised normals, over the pixels of S where both normals are non-zero.
+    S = J, or with max_depth_diff the pixels of J whose depths differ by at most that much: where the two renders show different
+    surfaces (an occlusion the mesh lacks) the colours and normals are not comparable; the depth figures and the shares keep all of J.
+    -> {"n_views", "max_depth_diff", "per_view": [one dict per view], "pooled": the same figures over the pixels of all views
+    together (from float64 sums)}.  A figure over an empty set is nan.  Plain torch on the arrays' device; not a hot path."""
+    return RenderScore(max_depth_diff).add(pred, target).result()
+
+
+def render_score_line(score):
+    """compare_renders' dict as one JSON line (nan stays NaN, as json writes it)."""
+    import json
+    return json.dumps(score)

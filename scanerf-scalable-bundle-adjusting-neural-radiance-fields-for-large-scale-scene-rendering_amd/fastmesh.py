@@ -13,6 +13,8 @@ Two deliberate differences from the reference's kernels:
 closest_point (csrc/mesh_distance.hip) has no counterpart in the reference: the exact nearest triangle per query
 point on the same structure, for the geometric evaluation of evaluation.py.  Neither has point_views (csrc/mesh_visibility.hip;
 DESIGN.md 4.19): which cameras see which points, the mesh occluding -- what meshing.cull_unseen drops unseen surface by.
+trace and render_views (csrc/mesh_render.hip) keep first_hit's hit record -- which face, where on it -- and render the
+mesh with its vertex normals and colours through a set of cameras in one launch: what evaluation.render_mesh / compare_renders score.
 There is no CPU path: CPU tensors raise.
 """
 import torch
@@ -277,6 +279,143 @@ class FastMesh:
             views[seen] += 1
             words[seen, c >> 5] |= 1 << (c & 31)
         return views, (words.to(_i32) if want_mask else None)
+
+    # ---- the hit record and the rendered mesh (csrc/mesh_render.hip) ----------------------------------------------
+    def _tracer_args(self):
+        """vertices .. log2dim as scanerf_mesh_trace and scanerf_mesh_render_views take them."""
+        return (dev_ptr(self.vertices, _f32, "vertices"), dev_ptr(self.faces, _i32, "faces"),
+                dev_ptr(self.tris, _f32, "tris", allow_none=True), dev_ptr(self.bitmask, _i64, "bitmask"),
+                dev_ptr(self.rank, _i32, "rank"), dev_ptr(self.start_num, _i32, "start_num"),
+                dev_ptr(self.cell_faces, _i32, "cell_faces"), dev_ptr(self.scene_info, _f32, "scene_info"), self.log2dim)
+
+    @staticmethod
+    def _strict(t, name, tail, dtype=_f32):
+        """A contiguous tensor of `dtype` and shape `tail` (None = any length), or an error: nothing is converted.  The device is
+        the caller's next check (_require_gpu), after every argument's shape."""
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError(f"scanerf: {name} must be a torch.Tensor, got {type(t).__name__}")
+        if t.dtype != dtype or t.dim() != len(tail) or any(w is not None and s != w for s, w in zip(t.shape, tail)):
+            want = "[" + ",".join("N" if w is None else str(w) for w in tail) + "]"
+            raise RuntimeError(f"scanerf: {name} must be {want} {dtype}, got {tuple(t.shape)} {t.dtype}")
+        if not t.is_contiguous():
+            raise RuntimeError(f"scanerf: {name} must be contiguous")
+        return t.detach()
+
+    @torch.no_grad()
+    def trace(self, rays_o, rays_d, route="grid"):
+        """rays_o, rays_d [B,3] float32 on the GPU -> (t [B] f32, face [B] i32, bary [B,2] f32): first_hit's distance with its bits,
+        the lowest index of the faces the walk tested that attains it, and Moeller-Trumbore's (u, v) on that face: the hit point is
+        A + u (B - A) + v (C - A).  A miss: t = 0, face = -1, bary = 0.  include/scanerf_mesh_tools_hip.h is the definition.
+        route: "grid" (the tracer's walk) or "brute" (every face in order; the witness)."""
+        if route not in ("grid", "brute"):
+            raise ValueError(f"scanerf: trace route must be 'grid' or 'brute', got {route!r}")
+        o = self._strict(rays_o, "rays_o", (None, 3))
+        d = self._strict(rays_d, "rays_d", (o.shape[0], 3))
+        _require_gpu(o, "rays_o")
+        _require_gpu(d, "rays_d")
+        B = o.shape[0]
+        t = torch.empty(B, dtype=_f32, device=o.device)
+        face = torch.empty(B, dtype=_i32, device=o.device)
+        bary = torch.empty(B, 2, dtype=_f32, device=o.device)
+        if B == 0:
+            return t, face, bary
+        from ._capi import tool
+        out = (dev_ptr(t, _f32, "t"), dev_ptr(face, _i32, "face"), dev_ptr(bary, _f32, "bary"))
+        if route == "grid":
+            check(tool("scanerf_mesh_trace")(dev_ptr(o, _f32, "rays_o"), dev_ptr(d, _f32, "rays_d"), B, *self._tracer_args(), *out,
+                                             stream()), "mesh_trace")
+        else:
+            check(tool("scanerf_mesh_trace_brute")(
+                dev_ptr(o, _f32, "rays_o"), dev_ptr(d, _f32, "rays_d"), B, dev_ptr(self.vertices, _f32, "vertices"),
+                dev_ptr(self.faces, _i32, "faces"), self.vertices.shape[0], self.faces.shape[0],
+                dev_ptr(self.scene_info, _f32, "scene_info"), self.log2dim, *out, stream()), "mesh_trace_brute")
+        return t, face, bary
+
+    @torch.no_grad()
+    def render_views(self, ks, c2ws, H, W, normals=None, colors=None, want_normals=False, route="fused"):
+        """The mesh seen through cameras ks [C,3,3] / c2ws [C,3,4] (arrays or tensors, moved to the mesh's device) at H x W pixels ->
+        {"depth": [C,H,W] f32 z-depth (0 = nothing), "face": [C,H,W] i32 (-1 = nothing)} and, when asked for, "normal" [C,H,W,3] (unit:
+        the interpolated `normals` [V,3] when given, else with want_normals=True the face normal as wound) and "color" [C,H,W,3]
+        (with `colors` [V,3]: interpolated).  Pixel (px, py)'s ray is compute_ray_forward's; include/scanerf_mesh_tools_hip.h is the
+        definition.  route="fused": one launch for all cameras; route="composed": the witness -- compute_ray_forward on a locs grid,
+        trace, then the interpolation as one eager float32 torch op per operation (the same bits)."""
+        if route not in ("fused", "composed"):
+            raise ValueError(f"scanerf: render_views route must be 'fused' or 'composed', got {route!r}")
+        if not isinstance(want_normals, bool):
+            raise ValueError(f"scanerf: want_normals must be True or False, got {want_normals!r}")
+        for name, v in (("H", H), ("W", W)):
+            if isinstance(v, bool) or int(v) != v or v < 1:
+                raise ValueError(f"scanerf: render_views {name} must be a positive integer, got {v!r}")
+        H, W = int(H), int(W)
+        V = self.vertices.shape[0]
+        vn = None if normals is None else self._strict(normals, "normals", (V, 3))
+        vc = None if colors is None else self._strict(colors, "colors", (V, 3))
+        want_normals = want_normals or vn is not None
+        for name, a in (("normals", vn), ("colors", vc)):
+            if a is not None:
+                _require_gpu(a, name)
+        from .allocation import _cameras
+        dev = self.vertices.device
+        k9, c12 = _cameras(ks, c2ws, dev)
+        C = k9.shape[0]
+        if C * H * W >= 1 << 31:
+            raise ValueError(f"scanerf: render_views: {C} x {H} x {W} pixels do not fit 31 bits; render fewer views per call")
+        if route == "composed":
+            return self._render_views_composed(k9, c12, H, W, vn, vc, want_normals)
+        out = {"depth": torch.empty(C, H, W, dtype=_f32, device=dev), "face": torch.empty(C, H, W, dtype=_i32, device=dev)}
+        if want_normals:
+            out["normal"] = torch.empty(C, H, W, 3, dtype=_f32, device=dev)
+        if vc is not None:
+            out["color"] = torch.empty(C, H, W, 3, dtype=_f32, device=dev)
+        if C == 0:
+            return out
+        from ._capi import tool
+        check(tool("scanerf_mesh_render_views")(
+            dev_ptr(k9, _f32, "ks"), dev_ptr(c12, _f32, "c2ws"), C, H, W, *self._tracer_args(),
+            dev_ptr(vn, _f32, "normals", allow_none=True), dev_ptr(vc, _f32, "colors", allow_none=True),
+            dev_ptr(out["depth"], _f32, "depth"), dev_ptr(out["face"], _i32, "face"),
+            dev_ptr(out.get("normal"), _f32, "normal", allow_none=True), dev_ptr(out.get("color"), _f32, "color", allow_none=True),
+            stream()), "mesh_render_views")
+        return out
+
+    def _render_views_composed(self, k9, c12, H, W, vn, vc, want_normals):
+        from .cuda.lib.CUDA_EXT import compute_ray_forward
+        dev = k9.device
+        C = k9.shape[0]
+        n = C * H * W
+        cam = torch.arange(C, device=dev, dtype=_i32)[:, None, None].expand(C, H, W)
+        py = torch.arange(H, device=dev, dtype=_i32)[None, :, None].expand(C, H, W)
+        px = torch.arange(W, device=dev, dtype=_i32)[None, None, :].expand(C, H, W)
+        locs = torch.stack([cam, px, py], -1).reshape(-1, 3).contiguous()
+        o = torch.empty(n, 3, dtype=_f32, device=dev)
+        d = torch.empty(n, 3, dtype=_f32, device=dev)
+        if n:
+            compute_ray_forward(o, d, k9, c12, locs)
+        t, face, bary = self.trace(o, d)
+        out = {"depth": t.reshape(C, H, W), "face": face.reshape(C, H, W)}
+        if not want_normals and vc is None:
+            return out
+        hit = face >= 0
+        idx = self.faces[face.clamp(min=0).to(_i64)].to(_i64)            # [n,3]; row 0 stands in for a miss and is masked below
+        ia, ib, ic = idx[:, 0], idx[:, 1], idx[:, 2]
+        u, v = bary[:, 0:1], bary[:, 1:2]
+        w0 = (1.0 - u) - v
+        interp = lambda a: (w0 * a[ia] + u * a[ib]) + v * a[ic]
+        zero = torch.zeros((), dtype=_f32, device=dev)
+        if want_normals:
+            if vn is not None:
+                nrm = interp(vn)
+            else:
+                A = self.vertices[ia]
+                e1, e2 = self.vertices[ib] - A, self.vertices[ic] - A
+                nrm = torch.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
+                                   e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], 1)
+            sq = (nrm[:, 0] * nrm[:, 0] + nrm[:, 1] * nrm[:, 1]) + nrm[:, 2] * nrm[:, 2]
+            length = torch.sqrt(sq) + 1e-8
+            out["normal"] = torch.where(hit[:, None], nrm / length[:, None], zero).reshape(C, H, W, 3)
+        if vc is not None:
+            out["color"] = torch.where(hit[:, None], interp(vc), zero).reshape(C, H, W, 3)
+        return out
 
     # ---- the reference's methods --------------------------------------------------------------------------------------------
     def _box(self):

@@ -318,10 +318,72 @@ class TileSetRenderer:
                                          log2dim=log2dim, return_distances=return_distances, device=mesh.vertices.device,
                                          normals=normals)
 
+    def _scene_batches(self, ks, c2ws, h, w, vpb, colors, max_transparency, render_kw, normals=False):
+        """The scene rendered at cameras ks / c2ws (already scaled) at h x w, vpb at a time -> an iterator of (first index, depth maps
+        [B,h,w] masked by fusion.mask_depth, images [B,h,w,3] (fusion.clamped_image; None without colors), normal maps [B,h,w,3] or
+        None): what fuse_mesh integrates and score_mesh compares with."""
+        from . import fusion
+        kw = dict(render_kw, normals=True) if normals else render_kw
+        for i in range(0, int(ks.shape[0]), vpb):
+            maps, images, nmaps = [], [], []
+            for c in range(i, min(i + vpb, int(ks.shape[0]))):
+                diffuse, specular, depth, transp, *nm = self.render(h, w, ks[c], c2ws[c], **kw)
+                maps.append(fusion.mask_depth(depth[..., 0], transp[..., 0], max_transparency))
+                if colors is not None:
+                    images.append(fusion.clamped_image(diffuse, specular if colors == "rgb" else None))
+                if normals:
+                    nmaps.append(nm[0])
+            yield (i, torch.stack(maps).contiguous(), torch.stack(images).contiguous() if colors is not None else None,
+                   torch.stack(nmaps).contiguous() if normals else None)
+
+    @torch.no_grad()
+    def score_mesh(self, mesh, cameras, colors=None, which="diffuse", scale=1, max_transparency=0.5, views_per_batch=8, normals=False,
+                   log2dim=6, max_depth_diff=None, **render_kw):
+        """Does the mesh, seen from the capture's cameras, look like what the field renders there?  cameras = (ks,
+        c2ws, H, W); every camera is rendered exactly as fuse_mesh renders it (H // scale x W // scale, K scaled, the depth masked at
+        max_transparency, render_kw to render) and the mesh -- (vertices, faces), a PLY path or a meshing.Mesh -- is rendered at the same
+        cameras (evaluation.render_mesh), views_per_batch at a time.  colors: the mesh's vertex colours [V,3] in 0..1 (fuse_mesh's
+        second return): compared with the scene's clamp(diffuse) (which="diffuse") or clamp(diffuse + specular) ("rgb").
+        normals=True: the mesh's normal map (its vertex normals, or its face normals) against the scene's.
+        -> evaluation.compare_renders' dict (pred = the mesh, target = the scene)."""
+        from . import evaluation, fusion
+        if which not in ("diffuse", "rgb"):
+            raise RuntimeError(f"scanerf: which must be 'diffuse' or 'rgb', got {which!r}")
+        if not isinstance(normals, bool):
+            raise RuntimeError(f"scanerf: normals must be True or False, got {normals!r}")
+        if cameras is None or len(cameras) != 4:
+            raise RuntimeError("scanerf: score_mesh needs cameras=(ks, c2ws, H, W)")
+        ks, c2ws, H, W = cameras
+        scale = fusion._positive_int(scale, "scale")
+        vpb = fusion._views_per_batch(views_per_batch)
+        H, W = fusion._positive_int(H, "H"), fusion._positive_int(W, "W")
+        h, w = H // scale, W // scale
+        if h < 1 or w < 1:
+            raise RuntimeError(f"scanerf: H={H} W={W} leave no pixel at scale={scale}")
+        if not 0.0 <= float(max_transparency) <= 1.0:
+            raise RuntimeError(f"scanerf: max_transparency must lie in [0, 1], got {max_transparency!r}")
+        ks = fusion.scale_cameras(ks, scale)
+        c2ws = torch.as_tensor(c2ws).to(torch.float32)
+        if c2ws.dim() != 3 or c2ws.shape[0] != ks.shape[0] or c2ws.shape[1] < 3 or c2ws.shape[2] != 4:
+            raise RuntimeError(f"scanerf: c2ws must be [C,3,4] (or [C,4,4]) with C={ks.shape[0]}, got {tuple(c2ws.shape)}")
+        acc = evaluation.RenderScore(max_depth_diff)
+        preds = evaluation.render_mesh(mesh, (ks, c2ws, h, w), colors=colors, normals=normals, log2dim=log2dim, views_per_batch=vpb,
+                                       device=self.device)
+        scene = self._scene_batches(ks, c2ws, h, w, vpb, which if colors is not None else None, float(max_transparency), render_kw,
+                                    normals=normals)
+        for (i, pred), (j, maps, images, nmaps) in zip(preds, scene):
+            target = {"depth": maps}
+            if images is not None:
+                target["color"] = images
+            if nmaps is not None:
+                target["normal"] = nmaps
+            acc.add(pred, target)
+        return acc.result()
+
     @torch.no_grad()
     def fuse_mesh(self, cameras, cells_per_axis=256, box=None, trunc=None, max_transparency=0.5, scale=1, views_per_batch=8,
                   min_weight=1, min_faces=0, min_extent=0, keep_largest=None, report=None, colors=None, normals=False, simplify=None,
-                  **render_kw):
+                  score=False, **render_kw):
         """ONE mesh of what the cameras saw (fusion.py): cameras = (ks [C,3,3], c2ws [C,3,4], H, W), typically the
         capture's.  Each camera is rendered at H // scale x W // scale (K scaled as fusion.scale_cameras does; render_kw goes to
         render), its depth set to 0 where the transparency exceeds max_transparency or the depth is not finite (fusion.mask_depth),
@@ -332,9 +394,17 @@ class TileSetRenderer:
         sensible colour of a mesh), "rgb" clamp(diffuse + specular, 0, 1) (the image shown everywhere else), batched with the depth
         maps; -> (mesh, rgb [V,3] f32), the mesh the one of the call without colours.  None: no colour, the Mesh alone.
         normals=True: the Mesh carries the volume's gradient normals (TSDFVolume.vertex_normals).
-        simplify=cell: TSDFVolume.extract's last step, meshing.simplify_mesh on the world grid of that cell."""
+        simplify=cell: TSDFVolume.extract's last step, meshing.simplify_mesh on the world grid of that cell.
+        score=True (needs a `report` dict): the finished mesh is rendered at the same cameras, with the fused colours
+        when there are any, and compared with the renders it was fused from (evaluation.compare_renders, views_per_batch at a time);
+        the dict goes to report["render_score"].  The scene is rendered once: the masked depth maps and images of all cameras are
+        kept until then.  What is returned does not change."""
         from . import fusion, meshing
         meshing._simplify_rule(simplify)
+        if not isinstance(score, bool):
+            raise RuntimeError(f"scanerf: score must be True or False, got {score!r}")
+        if score and not isinstance(report, dict):
+            raise RuntimeError("scanerf: fuse_mesh(score=True) writes report['render_score']: pass report={}")
         if not isinstance(normals, bool):
             raise RuntimeError(f"scanerf: normals must be True or False, got {normals!r}")
         if colors not in (None, "diffuse", "rgb"):
@@ -362,14 +432,22 @@ class TileSetRenderer:
         spacing = fusion.lattice_spacing(size, n)
         vol = fusion.TSDFVolume([float(v) for v in corner], spacing, n, fusion.default_trunc(spacing) if trunc is None else trunc,
                                 self.device, color=colors is not None)
-        for i in range(0, int(ks.shape[0]), vpb):
-            maps, images = [], []
-            for c in range(i, min(i + vpb, int(ks.shape[0]))):
-                diffuse, specular, depth, transp = self.render(h, w, ks[c], c2ws[c], **render_kw)[:4]
-                maps.append(fusion.mask_depth(depth[..., 0], transp[..., 0], float(max_transparency)))
-                if colors is not None:
-                    images.append(fusion.clamped_image(diffuse, specular if colors == "rgb" else None))
-            vol.integrate(torch.stack(maps).contiguous(), ks[i:i + vpb], c2ws[i:i + vpb],
-                          colors=torch.stack(images).contiguous() if colors is not None else None)
+        kept = []
+        for i, maps, images, _ in self._scene_batches(ks, c2ws, h, w, vpb, colors, float(max_transparency), render_kw):
+            vol.integrate(maps, ks[i:i + vpb], c2ws[i:i + vpb], colors=images)
+            if score:
+                kept.append((i, maps, images))
+        if score:
+            from . import evaluation
+            out = vol.extract(min_weight, min_faces, min_extent, keep_largest, report, colors=colors is not None, normals=normals,
+                              simplify=simplify)
+            mesh, rgb = out if colors is not None else (out, None)
+            acc = evaluation.RenderScore()
+            if mesh.faces.shape[0]:
+                batches = evaluation.render_mesh(mesh, (ks, c2ws, h, w), colors=rgb, normals=False, views_per_batch=vpb)
+                for (i, pred), (j, maps, images) in zip(batches, kept):
+                    acc.add(pred, {"depth": maps} if images is None else {"depth": maps, "color": images})
+            report["render_score"] = acc.result()
+            return out
         return vol.extract(min_weight, min_faces, min_extent, keep_largest, report, colors=colors is not None, normals=normals,
                            simplify=simplify)
