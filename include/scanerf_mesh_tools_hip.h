@@ -260,6 +260,53 @@ int scanerf_mesh_render_views(const float *Ks, const float *C2Ws, int C, int H, 
                               const float *vertex_colors, float *depth, int32_t *face, float *normal, float *color,
                               scanerf_stream_t stream);
 
+/* ---- vertex colours for any mesh from posed images (csrc/mesh_colors.hip): every point is projected into every
+ *   camera, the cameras that see it are sampled bilinearly there and blended.  What "colour an extracted, simplified or foreign mesh
+ *   from the field's renders or the capture's photographs" needs.  The reference has no counterpart; the definition is this comment.
+ *   Everything below is float32, operation by operation, without FMA contraction; division and sqrtf correctly rounded.
+ *   scanerf_mesh_project_colors.  Inputs: points [N,3] f32; normals [N,3] f32 or NULL; images [C,H,W,3] f32, any values; Ks [C,9],
+ *     C2Ws [C,12], H, W, bias, near, far and the tracer's arrays with log2dim exactly as scanerf_mesh_point_views takes them; min_cos in
+ *     [0, 1); acc [N,4] f32, interleaved (R, G, B, Wt), 16-byte aligned, read AND written; count [N] i32, read and written.
+ *   For point p and camera c = 0 .. C-1, IN THIS ORDER:
+ *     IN VIEW, SEGMENT, HIDDEN, SEEN: w, xc, yc, zc, len, px = fx (xc / zc) + cx, py = fy (yc / zc) + cy and the three rules are exactly
+ *       scanerf_mesh_point_views': the same operands, the same walk, the same early ends.
+ *     FACING (only with normals != NULL; n = the point's normal):
+ *       nl = sqrtf((n0 n0 + n1 n1) + n2 n2);  q = (n0 w0 + n1 w1) + n2 w2;  cosv = (-q) / (len * nl);
+ *       the pair faces the camera iff cosv > min_cos (false for a NaN: a zero or non-finite normal contributes nothing); wt = cosv.
+ *       With normals == NULL every pair faces and wt = 1.
+ *     SAMPLE (pixel j covers [j, j + 1), its centre is at j + 0.5):
+ *       u = px - 0.5f, v = py - 0.5f;  x0f = floorf(u), ax = u - x0f;  y0f = floorf(v), ay = v - y0f;
+ *       x0 = clamp((int)x0f, 0, W-1), x1 = clamp((int)x0f + 1, 0, W-1);  y0, y1 likewise with H;
+ *       per channel k, I = images[c]:  top = (1 - ax) * I[y0][x0][k] + ax * I[y0][x1][k];  bot the same on row y1;
+ *       val_k = (1 - ay) * top + ay * bot.
+ *     The pair CONTRIBUTES iff it is seen, faces the camera, and all 12 taps are finite.  Then
+ *       R <- R + wt * val_0, G <- G + wt * val_1, B <- B + wt * val_2, Wt <- Wt + wt, count <- count + 1.
+ *   The sums START FROM THE VALUES IN acc / count and run in ascending camera order: consecutive batches of cameras give the bits
+ *     of one call.  The order does not depend on which lane walked which segment: two launches give equal bits, both triangle forms
+ *     and every log2dim give equal bits.  One lane owns a point; no atomics on floats, no global atomics; every row of acc (one 16-byte
+ *     load, one 16-byte store) and of count is read once and written once per call by plain stores; nothing else is written.
+ *   N == 0 launches nothing.  C == 0 launches nothing: acc and count stay as they are (the image, camera and tracer arrays are not
+ *     read).  Refused before any launch (nothing written): N < 0 or C < 0, null pointers (but normals, tris), H or W < 1, log2dim
+ *     outside 4..7, bias not in (0, inf), near negative or NaN, far not > 0, min_cos outside [0, 1) or NaN, an acc that is not 16-byte
+ *     aligned.  No allocation, no host synchronisation; the launch goes on `stream`.
+ *   scanerf_mesh_project_colors_counted (measurement): also adds to counters [4] u64, which the caller zeroes: the pairs in view (the
+ *     segments walked), the occupied cells looked at, the ray / triangle tests, the pairs that contributed.
+ *   scanerf_mesh_resolve_colors: fill[3]: a HOST array.  For p < N: valid[p] (u8) = Wt > 0; colors[p][k] = valid ? acc[p][k] / Wt :
+ *     fill[k].  One launch, every element of colors [N,3] f32 and valid [N] written once.  N == 0 launches nothing; N < 0, null
+ *     pointers and an acc that is not 16-byte aligned are refused. */
+int scanerf_mesh_project_colors(const float *points, const float *normals, int N, const float *images, const float *Ks,
+                                const float *C2Ws, int C, int H, int W, float bias, float near, float far, float min_cos,
+                                const float *vertices, const int32_t *faces, const float *tris, const uint64_t *bitmask,
+                                const uint32_t *rank, const int32_t *start_num, const int32_t *cell_faces, const float *scene_info,
+                                int log2dim, float *acc, int32_t *count, scanerf_stream_t stream);
+int scanerf_mesh_project_colors_counted(const float *points, const float *normals, int N, const float *images, const float *Ks,
+                                        const float *C2Ws, int C, int H, int W, float bias, float near, float far, float min_cos,
+                                        const float *vertices, const int32_t *faces, const float *tris, const uint64_t *bitmask,
+                                        const uint32_t *rank, const int32_t *start_num, const int32_t *cell_faces,
+                                        const float *scene_info, int log2dim, float *acc, int32_t *count, uint64_t *counters,
+                                        scanerf_stream_t stream);
+int scanerf_mesh_resolve_colors(const float *acc, int N, const float *fill, float *colors, uint8_t *valid, scanerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

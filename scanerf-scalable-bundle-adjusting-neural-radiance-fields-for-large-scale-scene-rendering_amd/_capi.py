@@ -150,6 +150,9 @@ TOOL_PROTOTYPES = {
     "scanerf_mesh_trace": ("I", "PPIPPPPPPPPIPPPP"),
     "scanerf_mesh_trace_brute": ("I", "PPIPPIIPIPPPP"),
     "scanerf_mesh_render_views": ("I", "PPIIIPPPPPPPPIPPPPPPP"),
+    "scanerf_mesh_project_colors": ("I", "PPIPPPIIIFFFFPPPPPPPPIPPP"),
+    "scanerf_mesh_project_colors_counted": ("I", "PPIPPPIIIFFFFPPPPPPPPIPPPP"),
+    "scanerf_mesh_resolve_colors": ("I", "PIPPPP"),
 }
 CTYPES = {"P": ctypes.c_void_p, "I": ctypes.c_int, "U": ctypes.c_uint, "F": ctypes.c_float, "Z": ctypes.c_size_t,
           "L": ctypes.c_int64, "S": ctypes.c_char_p}

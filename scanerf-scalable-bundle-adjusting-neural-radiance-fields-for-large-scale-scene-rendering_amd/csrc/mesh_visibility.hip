@@ -19,7 +19,7 @@
 // same operands, stops at the first t in (0, 1) (then h <= t < 1) and after the first cell with t1 >= 1.  If first_hit_walk ends
 // earlier, at best <= t1 with best >= 1, that cell's t1 is >= 1 as well; if it goes on beyond a cell with t1 >= 1 it can only meet
 // faces whose hit lies in a cell already passed.
-#include "mesh_device.h"
+#include "mesh_visibility_device.h"   // wave_sync, in_view, segment_hidden: shared with mesh_colors.hip
 
 #include "scanerf_mesh_tools_hip.h"
 
@@ -31,68 +31,6 @@ constexpr int kWordsPerPass = 2;                     // mask words a lane keeps 
 constexpr int kCamsPerPass = 32 * kWordsPerPass;     // 64: an entry's camera fits 6 bits
 constexpr int kQueue = 2 * kWave;                    // fewer than 64 entries wait when up to 64 arrive
 constexpr int kMaxGroups = 2048;
-
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// the in-view test of the definition
-__device__ __forceinline__ bool in_view(const float p[3], bool finite, const float *__restrict__ K, const float *__restrict__ T, float Hf,
-                                        float Wf, float bias, float near, float far)
-{
-    const float fx = K[0], cx = K[2], fy = K[4], cy = K[5];
-    const float w[3] = { p[0] - T[3], p[1] - T[7], p[2] - T[11] };
-    const float xc = (w[0] * T[0] + w[1] * T[4]) + w[2] * T[8];
-    const float yc = (w[0] * T[1] + w[1] * T[5]) + w[2] * T[9];
-    const float zc = (w[0] * T[2] + w[1] * T[6]) + w[2] * T[10];
-    const float len = sqrtf((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
-    const float px = fx * (xc / zc) + cx, py = fy * (yc / zc) + cy;
-    return finite && zc > near && len <= far && len > bias && px >= 0.0f && px < Wf && py >= 0.0f && py < Hf;
-}
-
-// true iff some registered face meets the segment o + t d at 0 < t < 1
-template <bool PRE, bool COUNT>
-__device__ __forceinline__ bool segment_hidden(const float o[3], const float d[3], const Grid &g, const Words<false> &words,
-                                               const float *__restrict__ vertices, const int32_t *__restrict__ faces,
-                                               const int32_t *__restrict__ cell_faces, const float *__restrict__ tris,
-                                               unsigned long long &n_cells, unsigned long long &n_tests)
-{
-    RayWalk rw;
-    if (!rw.start(o, d, g)) return false;
-    while (!rw.done()) {
-        rw.w.pick();
-        const int c = words.lookup(rw.cell(g.L));
-        if (c >= 0) {
-            if (COUNT) ++n_cells;
-            const int start = g.start_num[2 * c], num = g.start_num[2 * c + 1];
-            for (int k = 0; k < num; ++k) {
-                float A[3], e1[3], e2[3];
-                if (PRE) {
-                    const float *t = tris + 9 * (size_t)(start + k);
-#pragma unroll
-                    for (int a = 0; a < 3; ++a) { A[a] = t[a]; e1[a] = t[3 + a]; e2[a] = t[6 + a]; }
-                } else {
-                    const int f = cell_faces[start + k];
-                    const int ia = faces[3 * f], ib = faces[3 * f + 1], ic = faces[3 * f + 2];
-#pragma unroll
-                    for (int a = 0; a < 3; ++a) {
-                        A[a] = vertices[3 * ia + a];
-                        e1[a] = vertices[3 * ib + a] - A[a];
-                        e2[a] = vertices[3 * ic + a] - A[a];
-                    }
-                }
-                if (COUNT) ++n_tests;
-                const float t = ray_triangle(o, d, A, e1, e2);
-                if (t > 0.0f && t < 1.0f) return true;
-            }
-        }
-        if (rw.w.t1 >= 1.0f) break;   // the eye lies in this cell or before it
-        rw.w.advance();
-    }
-    return false;
-}
 
 template <bool PRE, bool COUNT>
 __global__ void __launch_bounds__(kThreads) k_point_views(const float *__restrict__ points, int N, const float *__restrict__ Ks,

@@ -15,6 +15,8 @@ point on the same structure, for the geometric evaluation of evaluation.py.  Nei
 DESIGN.md 4.19): which cameras see which points, the mesh occluding -- what meshing.cull_unseen drops unseen surface by.
 trace and render_views (csrc/mesh_render.hip) keep first_hit's hit record -- which face, where on it -- and render the
 mesh with its vertex normals and colours through a set of cameras in one launch: what evaluation.render_mesh / compare_renders score.
+project_colors (csrc/mesh_colors.hip) goes the other way: points projected into posed images, the cameras that see them
+sampled and blended -- vertex colours for any mesh (meshing.color_from_views, TileSetRenderer.color_mesh).
 There is no CPU path: CPU tensors raise.
 """
 import torch
@@ -247,6 +249,29 @@ class FastMesh:
             dev_ptr(views, _i32, "views"), dev_ptr(mask, _i32, "mask", allow_none=True), stream()), "mesh_point_views")
         return views, mask
 
+    def _seen_composed(self, p, finite, K, T, bias, near, far, Hf, Wf):
+        """One camera of the composed routes: the definition's operands as separate torch elementwise ops, first_hit on the pairs in
+        view -> (indices of the points the camera sees, w [N,3], len [N], px [N], py [N])."""
+        E = torch.stack([T[3], T[7], T[11]])
+        w = p - E
+        w0, w1, w2 = w[:, 0], w[:, 1], w[:, 2]
+        xc = (w0 * T[0] + w1 * T[4]) + w2 * T[8]
+        yc = (w0 * T[1] + w1 * T[5]) + w2 * T[9]
+        zc = (w0 * T[2] + w1 * T[6]) + w2 * T[10]
+        length = torch.sqrt((w0 * w0 + w1 * w1) + w2 * w2)
+        px = K[0] * (xc / zc) + K[2]
+        py = K[4] * (yc / zc) + K[5]
+        inview = finite & (zc > near) & (length <= far) & (length > bias) & (px >= 0) & (px < Wf) & (py >= 0) & (py < Hf)
+        idx = torch.nonzero(inview).reshape(-1)
+        if idx.shape[0] == 0:
+            return idx, w, length, px, py
+        pi, wi = p[idx], w[idx]
+        s = bias / length[idx]
+        P = pi - s[:, None] * wi
+        d = E - P
+        h = self.first_hit(P.contiguous(), d.contiguous())
+        return idx[~((h > 0) & (h < 1))], w, length, px, py
+
     def _point_views_composed(self, p, k9, c12, H, W, bias, near, far, want_mask):
         dev = p.device
         N, C = p.shape[0], k9.shape[0]
@@ -256,29 +281,103 @@ class FastMesh:
         views = torch.zeros(N, dtype=_i32, device=dev)
         words = torch.zeros((N, (C + 31) // 32), dtype=_i64, device=dev)
         for c in range(C):
-            K, T = k9[c], c12[c]
-            E = torch.stack([T[3], T[7], T[11]])
-            w = p - E
-            w0, w1, w2 = w[:, 0], w[:, 1], w[:, 2]
-            xc = (w0 * T[0] + w1 * T[4]) + w2 * T[8]
-            yc = (w0 * T[1] + w1 * T[5]) + w2 * T[9]
-            zc = (w0 * T[2] + w1 * T[6]) + w2 * T[10]
-            length = torch.sqrt((w0 * w0 + w1 * w1) + w2 * w2)
-            px = K[0] * (xc / zc) + K[2]
-            py = K[4] * (yc / zc) + K[5]
-            inview = finite & (zc > near) & (length <= far) & (length > bias) & (px >= 0) & (px < Wf) & (py >= 0) & (py < Hf)
-            idx = torch.nonzero(inview).reshape(-1)
-            if idx.shape[0] == 0:
-                continue
-            pi, wi = p[idx], w[idx]
-            s = bias / length[idx]
-            P = pi - s[:, None] * wi
-            d = E - P
-            h = self.first_hit(P.contiguous(), d.contiguous())
-            seen = idx[~((h > 0) & (h < 1))]
+            seen = self._seen_composed(p, finite, k9[c], c12[c], bias, near, far, Hf, Wf)[0]
             views[seen] += 1
             words[seen, c >> 5] |= 1 << (c & 31)
         return views, (words.to(_i32) if want_mask else None)
+
+    # ---- colours from posed images (csrc/mesh_colors.hip) ----------------------------------------------------------
+    @torch.no_grad()
+    def project_colors(self, points, images, ks, c2ws, bias, normals=None, near=0.0, far=float("inf"), min_cos=0.0, acc=None,
+                       count=None, route="fused"):
+        """points [N,3] float32 on the GPU, images [C,H,W,3] float32 on the same device, cameras ks [C,3,3] / c2ws [C,3,4] (arrays or
+        tensors, moved to the points' device) -> (acc [N,4] f32 = the sums (R, G, B, Wt), count [N] i32 = the cameras that
+        contributed).  Every camera that sees a point (point_views' rule, this mesh occluding) is sampled bilinearly where the point
+        projects and added with the weight cos(normal, direction to the eye) when `normals` [N,3] are given (only cosines above
+        min_cos count), else 1; a sample with a non-finite tap is left out.  include/scanerf_mesh_tools_hip.h is the definition.
+        acc / count: the sums of earlier batches of cameras, continued IN PLACE (both or neither; None: zeros); consecutive batches
+        give the bits of one call.  route="fused": one launch; route="composed": the witness, per camera _point_views_composed's seen
+        rule, then the sample and the blend as one eager float32 torch op per operation in the same order (the same bits)."""
+        if route not in ("fused", "composed"):
+            raise ValueError(f"scanerf: project_colors route must be 'fused' or 'composed', got {route!r}")
+        bias, near, far, min_cos = float(bias), float(near), float(far), float(min_cos)
+        if not (0.0 < bias < float("inf")):
+            raise ValueError(f"scanerf: project_colors bias must be > 0 and finite, got {bias}")
+        if not near >= 0.0:
+            raise ValueError(f"scanerf: project_colors near must be >= 0, got {near}")
+        if not far > 0.0:
+            raise ValueError(f"scanerf: project_colors far must be > 0 (inf for no limit), got {far}")
+        if not 0.0 <= min_cos < 1.0:
+            raise ValueError(f"scanerf: project_colors min_cos must lie in [0, 1), got {min_cos}")
+        if (acc is None) != (count is None):
+            raise ValueError("scanerf: project_colors continues acc and count together: pass both or neither")
+        p = self._strict(points, "points", (None, 3))
+        N = p.shape[0]
+        img = self._strict(images, "images", (None, None, None, 3))
+        C, H, W = (int(v) for v in img.shape[:3])
+        if H < 1 or W < 1:
+            raise ValueError(f"scanerf: project_colors images must have at least one pixel, got {H} x {W}")
+        nrm = None if normals is None else self._strict(normals, "normals", (N, 3))
+        if acc is not None:
+            acc = self._strict(acc, "acc", (N, 4))
+            count = self._strict(count, "count", (N,), _i32)
+        for name, t in (("points", p), ("images", img), ("normals", nrm), ("acc", acc), ("count", count)):
+            if t is not None:
+                _require_gpu(t, name)
+        from .allocation import _cameras
+        k9, c12 = _cameras(ks, c2ws, p.device)
+        if k9.shape[0] != C:
+            raise ValueError(f"scanerf: project_colors got {C} images and {k9.shape[0]} cameras")
+        if acc is None:
+            acc = torch.zeros(N, 4, dtype=_f32, device=p.device)
+            count = torch.zeros(N, dtype=_i32, device=p.device)
+        if N == 0 or C == 0:
+            return acc, count
+        if route == "composed":
+            return self._project_colors_composed(p, nrm, img, k9, c12, bias, near, far, min_cos, acc, count)
+        from ._capi import tool
+        check(tool("scanerf_mesh_project_colors")(
+            dev_ptr(p, _f32, "points"), dev_ptr(nrm, _f32, "normals", allow_none=True), N, dev_ptr(img, _f32, "images"),
+            dev_ptr(k9, _f32, "ks"), dev_ptr(c12, _f32, "c2ws"), C, H, W, bias, near, far, min_cos, *self._tracer_args(),
+            dev_ptr(acc, _f32, "acc"), dev_ptr(count, _i32, "count"), stream()), "mesh_project_colors")
+        return acc, count
+
+    def _project_colors_composed(self, p, nrm, img, k9, c12, bias, near, far, min_cos, acc, count):
+        dev = p.device
+        C, H, W = (int(v) for v in img.shape[:3])
+        scalar = lambda v: torch.tensor(v, dtype=_f32, device=dev)
+        bias, near, far, Hf, Wf, min_cos = scalar(bias), scalar(near), scalar(far), scalar(float(H)), scalar(float(W)), scalar(min_cos)
+        finite = torch.isfinite(p).all(1)
+        for c in range(C):
+            idx, w, length, px, py = self._seen_composed(p, finite, k9[c], c12[c], bias, near, far, Hf, Wf)
+            if idx.shape[0] == 0:
+                continue
+            if nrm is not None:
+                n, wi = nrm[idx], w[idx]
+                nl = torch.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2])
+                q = (n[:, 0] * wi[:, 0] + n[:, 1] * wi[:, 1]) + n[:, 2] * wi[:, 2]
+                wt = (-q) / (length[idx] * nl)
+                facing = wt > min_cos
+                idx, wt = idx[facing], wt[facing]
+            else:
+                wt = torch.ones(idx.shape[0], dtype=_f32, device=dev)
+            u, v = px[idx] - 0.5, py[idx] - 0.5
+            x0f, y0f = torch.floor(u), torch.floor(v)
+            ax, ay = (u - x0f)[:, None], (v - y0f)[:, None]
+            xi, yi = x0f.to(_i64), y0f.to(_i64)
+            x0, x1 = xi.clamp(0, W - 1), (xi + 1).clamp(0, W - 1)
+            y0, y1 = yi.clamp(0, H - 1), (yi + 1).clamp(0, H - 1)
+            I = img[c]
+            a, b, cc, d = I[y0, x0], I[y0, x1], I[y1, x0], I[y1, x1]
+            ok = torch.isfinite(a).all(1) & torch.isfinite(b).all(1) & torch.isfinite(cc).all(1) & torch.isfinite(d).all(1)
+            top = (1.0 - ax) * a + ax * b
+            bot = (1.0 - ax) * cc + ax * d
+            val = (1.0 - ay) * top + ay * bot
+            idx, wt, val = idx[ok], wt[ok], val[ok]
+            acc[idx, :3] = acc[idx, :3] + wt[:, None] * val      # (idx holds a point once: no accumulation inside the assignment)
+            acc[idx, 3] = acc[idx, 3] + wt
+            count[idx] += 1
+        return acc, count
 
     # ---- the hit record and the rendered mesh (csrc/mesh_render.hip; DESIGN.md 4.24) ----------------------------------------------
     def _tracer_args(self):

@@ -19,6 +19,8 @@ lattice.  The reference has no mesh extraction; the definition is the comment of
                                                         cameras / min_views / view_bias and cull before the component rule
     simplify_mesh(mesh, cell, origin, colors)           vertex clustering on a world grid: positions, normals and colours averaged per cell
                                                         (csrc/mesh_simplify.hip); the scene extractors take simplify=cell
+    color_from_views(mesh, images, ks, c2ws, bias)      vertex colours for any mesh from posed images: project, sample, blend
+                                                        (csrc/mesh_colors.hip); extract_scene_mesh takes colors=callable
 
 All return a Mesh: vertices [V,3] f32 (world), faces [F,3] i32 (counter-clockwise seen from the outside), cells [V,3] i32 (the owning
 cell of each vertex), lattice [V,3] f32 (the vertices in lattice coordinates) and, on request, normals [V,3] f32.  Two launches with
@@ -242,7 +244,7 @@ def _scene_tile_args(feature_tables, resolutions, blobs, corners, sizes, occupie
 
 def extract_scene_mesh(feature_tables, resolutions, blobs, corners, sizes, occupied_grid, grid_starts, log2dim, box_corner, box_size, n,
                        level, route="fused", normals=False, min_faces=0, min_extent=0, keep_largest=None, report=None, cameras=None,
-                       min_views=0, view_bias=None, view_far=None, simplify=None):
+                       min_views=0, view_bias=None, view_far=None, simplify=None, colors=None):
     """One mesh of a tiled scene: the level set of the field the multi-tile renderer draws -- the tiles' densities blended per lattice
     point with the renderer's xz-distance weights -- on a lattice of n cells over the world box box_corner / box_size (the definition:
     include/scanerf_hip.h, scanerf_isosurface_count_tiles).  The tile arrays are TileSetRenderer's: feature_tables [nb,16,T,2] f16,
@@ -255,12 +257,17 @@ def extract_scene_mesh(feature_tables, resolutions, blobs, corners, sizes, occup
     cameras = (ks, c2ws, H, W) with min_views >= 1: cull_unseen on the raw mesh (DESIGN.md 4.19), BEFORE the component rule;
     view_bias: half a lattice spacing by default; view_far: the cameras' range (None: no limit).
     simplify=cell: simplify_mesh on the world grid of that cell as the LAST step, after the filter and the normals (DESIGN.md 4.23);
-    the Mesh then has no cells / lattice; report["simplify"] receives its rows."""
+    the Mesh then has no cells / lattice; report["simplify"] receives its rows.
+    colors=callable: called as colors(mesh, bias) on the FINAL mesh -- after the cull, the filter and simplify --
+    with bias = view_bias or its default; it returns the vertex colours [V,3] (TileSetRenderer.extract_mesh passes its color_mesh:
+    the scene's renders projected onto the vertices).  -> (Mesh, rgb).  None: the Mesh alone, exactly as without the argument."""
     _simplify_rule(simplify)
     if route not in ROUTES:
         raise RuntimeError(f"scanerf: route must be one of {ROUTES}, got {route!r}")
     _rules(min_faces, min_extent, keep_largest, True)
     _view_rule(cameras, min_views, view_bias, view_far)
+    if colors is not None and not callable(colors):
+        raise RuntimeError(f"scanerf: extract_scene_mesh colors must be None or a callable (mesh, bias) -> [V,3], got {colors!r}")
     n = _lattice_size(n)
     tiles = (feature_tables, resolutions, blobs, corners, sizes, occupied_grid, grid_starts, log2dim)
     head, T, nb = _scene_tile_args(*tiles)
@@ -280,7 +287,10 @@ def extract_scene_mesh(feature_tables, resolutions, blobs, corners, sizes, occup
     mesh = _filter(mesh, min_faces, min_extent, keep_largest, _COMPONENT_ROUTE[route], False, report)
     if normals:
         mesh = mesh._replace(normals=scene_sigma_normals_points(mesh.vertices, *tiles, route=route)[2])
-    return _simplified(mesh, simplify, None, report, _SIMPLIFY_ROUTE[route])
+    mesh = _simplified(mesh, simplify, None, report, _SIMPLIFY_ROUTE[route])
+    if colors is None:
+        return mesh
+    return mesh, colors(mesh, default_view_bias(size, n) if view_bias is None else float(view_bias))
 
 
 # ---- the blended density's gradient at world points (csrc/scene_normals.hip) -----------------------------------------
@@ -857,3 +867,141 @@ def cells_per_axis(occ_size, longest):
     """Lattice for a box: `longest` cells along its longest side, the other sides by the box's aspect (at least 1)."""
     size = [float(v) for v in (occ_size.detach().cpu().tolist() if isinstance(occ_size, torch.Tensor) else occ_size)]
     return [max(1, int(round(int(longest) * s / max(size)))) for s in size]
+
+
+# ---- vertex colours from posed images (csrc/mesh_colors.hip; DESIGN.md 4.25) ----------------------------------------------------------
+COLOR_ROUTES = ("fused", "composed")
+DEFAULT_FILL = (0.5, 0.5, 0.5)
+
+
+def _fill(fill):
+    try:
+        out = [float(v) for v in fill]
+    except (TypeError, ValueError):
+        out = []
+    if len(out) != 3 or not all(abs(v) < float("inf") for v in out):
+        raise RuntimeError(f"scanerf: fill must be three finite numbers, got {fill!r}")
+    return out
+
+
+def resolve_colors(acc, fill=DEFAULT_FILL):
+    """The sums of FastMesh.project_colors -> (colors [N,3] f32, valid [N] bool): acc[:, :3] / Wt where Wt > 0 (some camera
+    contributed), else `fill`.  One launch; include/scanerf_mesh_tools_hip.h is the definition."""
+    from ._capi import tool
+    fill = _fill(fill)
+    if not isinstance(acc, torch.Tensor) or acc.dtype != _f32 or acc.dim() != 2 or acc.shape[1] != 4:
+        raise RuntimeError(f"scanerf: acc must be [N,4] float32, got {tuple(acc.shape) if isinstance(acc, torch.Tensor) else type(acc).__name__}")
+    N = int(acc.shape[0])
+    ptr = dev_ptr(acc, _f32, "acc")
+    colors = torch.empty(N, 3, dtype=_f32, device=acc.device)
+    valid = torch.empty(N, dtype=torch.uint8, device=acc.device)
+    if N:
+        check(tool("scanerf_mesh_resolve_colors")(ptr, N, (ctypes.c_float * 3)(*fill), dev_ptr(colors, _f32, "colors"),
+                                                  dev_ptr(valid, torch.uint8, "valid"), stream()), "mesh_resolve_colors")
+    return colors, valid.to(torch.bool)
+
+
+def _views_per_batch(views_per_batch):
+    if isinstance(views_per_batch, bool) or not isinstance(views_per_batch, (int, np.integer)) or views_per_batch < 1:
+        raise RuntimeError(f"scanerf: views_per_batch must be a positive integer, got {views_per_batch!r}")
+    return int(views_per_batch)
+
+
+def _color_rule(min_cos, fill, route):
+    """color_from_views' scalar arguments, checked before any launch."""
+    if route not in COLOR_ROUTES:
+        raise RuntimeError(f"scanerf: route must be one of {COLOR_ROUTES}, got {route!r}")
+    if not 0.0 <= float(min_cos) < 1.0:
+        raise RuntimeError(f"scanerf: min_cos must lie in [0, 1), got {min_cos!r}")
+    return float(min_cos), _fill(fill)
+
+
+def default_edge_bias(mesh):
+    """Half the mean edge length of the mesh's faces: the bias of a mesh that comes without its lattice (one host read)."""
+    if mesh.faces.shape[0] == 0:
+        return 1.0
+    v = mesh.vertices[mesh.faces.to(torch.int64)]
+    edges = torch.stack([v[:, 1] - v[:, 0], v[:, 2] - v[:, 1], v[:, 0] - v[:, 2]], 1)
+    mean = float(torch.linalg.norm(edges, dim=-1).mean())
+    if not 0.0 < mean < float("inf"):
+        raise RuntimeError(f"scanerf: the mesh's mean edge length is {mean}: pass bias")
+    return 0.5 * mean
+
+
+class ViewColors:
+    """The running blend of one mesh's vertex colours: the tracer is built once on the mesh, add(images, ks, c2ws) projects a batch
+    of cameras into the sums (consecutive batches give the bits of one call), result() divides.  What color_from_views and
+    TileSetRenderer.color_mesh feed batch by batch."""
+
+    def __init__(self, mesh, bias, normals="mesh", near=0.0, far=float("inf"), min_cos=0.0, fill=DEFAULT_FILL, log2dim=6, route="fused"):
+        from .fastmesh import FastMesh
+        self.min_cos, self.fill = _color_rule(min_cos, fill, route)
+        self.route, self.bias, self.near, self.far = route, bias, near, far
+        if isinstance(normals, str):
+            if normals != "mesh":
+                raise RuntimeError(f"scanerf: normals must be 'mesh', None or a [V,3] tensor, got {normals!r}")
+            normals = getattr(mesh, "normals", None)
+        dev_ptr(mesh.vertices, _f32, "vertices")
+        dev_ptr(mesh.faces, _i32, "faces")
+        self.points = mesh.vertices
+        V, device = int(mesh.vertices.shape[0]), mesh.vertices.device
+        if normals is not None and (not isinstance(normals, torch.Tensor) or tuple(normals.shape) != (V, 3) or normals.dtype != _f32):
+            raise RuntimeError(f"scanerf: normals must be [{V},3] float32")
+        self.normals = None if normals is None else normals.contiguous()
+        self.empty = V == 0 or mesh.faces.shape[0] == 0      # nothing to build a tracer on: every vertex keeps `fill`
+        self.fm = None if self.empty else FastMesh.from_arrays(mesh.vertices, mesh.faces, device, log2dim=log2dim)
+        self.acc = torch.zeros(V, 4, dtype=_f32, device=device)
+        self.count = torch.zeros(V, dtype=_i32, device=device)
+
+    def add(self, images, ks, c2ws):
+        if self.empty:
+            return
+        images = torch.as_tensor(images)
+        if images.dtype == torch.uint8:
+            # (a one-element tensor, not a Python number: torch multiplies by the reciprocal of a scalar divisor on the GPU)
+            images = images.to(self.points.device).to(_f32) / torch.full((1,), 255.0, dtype=_f32, device=self.points.device)
+        images = images.to(self.points.device, _f32).contiguous()
+        self.fm.project_colors(self.points, images, ks, c2ws, self.bias, normals=self.normals, near=self.near, far=self.far,
+                               min_cos=self.min_cos, acc=self.acc, count=self.count, route=self.route)
+
+    def result(self, report=None):
+        V = int(self.points.shape[0])
+        if V == 0:
+            colors, valid = torch.empty(0, 3, dtype=_f32, device=self.points.device), torch.empty(0, dtype=torch.bool, device=self.points.device)
+        elif self.empty:
+            colors = torch.tensor(self.fill, dtype=_f32, device=self.points.device).repeat(V, 1)
+            valid = torch.zeros(V, dtype=torch.bool, device=self.points.device)
+        else:
+            colors, valid = resolve_colors(self.acc, self.fill)
+        if report is not None:
+            report.update(count_histogram=torch.bincount(self.count.to(torch.int64)).tolist() if V else [],
+                          invalid=int((~valid).sum()) if V else 0)
+        return colors, valid
+
+
+def color_from_views(mesh, images, ks, c2ws, bias, normals="mesh", near=0.0, far=float("inf"), min_cos=0.0, views_per_batch=8,
+                     fill=DEFAULT_FILL, log2dim=6, route="fused", report=None):
+    """Vertex colours for ANY mesh from posed images: every vertex is projected into every camera, the cameras that
+    see it (vertex_views' rule, the mesh itself occluding; bias as there) are sampled bilinearly and blended, weighted by the cosine
+    between the vertex normal and the direction to the eye.  -> (colors [V,3] f32, valid [V] bool); a vertex nobody contributed to
+    gets `fill` and valid False.
+    images: [C,H,W,3] (array or tensor on any device; uint8 is read as 0..255 -> 0..1), moved views_per_batch at a time, or a
+    callable (i0, i1) -> [i1-i0,H,W,3].  normals: "mesh" = mesh.normals when present, else no weighting; None = no weighting; a
+    [V,3] tensor.  min_cos drops grazing views.  report: a dict that receives count_histogram (entry k: the vertices k cameras
+    contributed to) and invalid.  The tracer is built once; V == 0 or F == 0 returns without a launch."""
+    vpb = _views_per_batch(views_per_batch)
+    from .allocation import _cameras
+    ks, c2ws = torch.as_tensor(ks), torch.as_tensor(c2ws)
+    C = int(_cameras(ks, c2ws)[0].shape[0])
+    if not callable(images) and (getattr(images, "ndim", 0) != 4 or images.shape[0] != C or images.shape[3] != 3):
+        raise RuntimeError(f"scanerf: images must be [C,H,W,3] with C={C}, or a callable (i0, i1) -> [i1-i0,H,W,3]")
+    blend = ViewColors(mesh, bias, normals, near, far, min_cos, fill, log2dim, route)
+    if not blend.empty:
+        for i in range(0, C, vpb):
+            j = min(i + vpb, C)
+            batch = images(i, j) if callable(images) else images[i:j]
+            if tuple(batch.shape[:1]) != (j - i,) or batch.ndim != 4 or batch.shape[3] != 3:
+                raise RuntimeError(f"scanerf: images({i}, {j}) must be [{j - i},H,W,3], got {tuple(batch.shape)}")
+            blend.add(np.array(batch) if isinstance(batch, np.ndarray) else batch,      # (a copy: a memory-mapped file is read here)
+                      ks[i:j], c2ws[i:j])
+    return blend.result(report)

@@ -286,7 +286,8 @@ class TileSetRenderer:
 
     @torch.no_grad()
     def extract_mesh(self, level, cells_per_axis=256, box=None, route="fused", normals=False, min_faces=0, min_extent=0,
-                     keep_largest=None, report=None, cameras=None, min_views=0, view_bias=None, view_far=None, simplify=None):
+                     keep_largest=None, report=None, cameras=None, min_views=0, view_bias=None, view_far=None, simplify=None,
+                     colors=None, color_scale=1, **color_kw):
         """ONE mesh of the whole scene: the level set sigma == level of the density this renderer draws, the tiles' densities blended
         per point with the render-time weights (meshing.extract_scene_mesh).  box = (corner, size) of the world box
         the lattice covers (default: scene_box()), with cells_per_axis cells along its longest side.  normals=True: the vertex normals,
@@ -294,10 +295,29 @@ class TileSetRenderer:
         keep_largest: meshing.filter_mesh's keep rule (floaters and unused vertices go), applied before the normals
         are evaluated; report: a dict that receives the component count and the rows before and after.  cameras = (ks, c2ws, H, W)
         with min_views >= 1: the parts no camera saw go first (meshing.cull_unseen; view_bias: half a lattice spacing
-        by default).  simplify=cell: meshing.simplify_mesh as the last step.  -> meshing.Mesh."""
+        by default).  simplify=cell: meshing.simplify_mesh as the last step.  -> meshing.Mesh.
+        colors="diffuse" | "rgb" (needs cameras): the FINAL vertices -- after the cull, the filter and simplify --
+        are coloured by color_mesh from this scene's renders at the cameras (H // color_scale x W // color_scale; color_kw goes to
+        color_mesh).  -> (mesh, rgb [V,3] f32), the mesh the one of the call without colours.  None: the Mesh alone, as before."""
         from . import meshing
+        if colors not in (None, "diffuse", "rgb"):
+            raise RuntimeError(f"scanerf: colors must be None, 'diffuse' or 'rgb', got {colors!r}")
+        if colors is None and (color_kw or color_scale != 1):
+            raise RuntimeError(f"scanerf: extract_mesh: {sorted(color_kw) or 'color_scale'} only mean something with colors=")
+        if colors is not None and (cameras is None or len(cameras) != 4):
+            raise RuntimeError("scanerf: extract_mesh(colors=...) needs cameras=(ks, c2ws, H, W)")
         corner, size = self.scene_box() if box is None else box
         size = [float(v) for v in size]
+        paint = None
+        if colors is not None:
+            paint = lambda mesh, bias: self.color_mesh(mesh, cameras, which=colors, scale=color_scale, bias=bias,
+                                                       **dict({"far": float("inf") if view_far is None else float(view_far)}, **color_kw))[0]
+            return meshing.extract_scene_mesh(self.feature_tables, self.resolution, self.params, self.block_corner, self.block_size,
+                                              self.occupied_grid, self.grid_starts, self.grid_log2dim, corner, size,
+                                              meshing.cells_per_axis(size, cells_per_axis), level, route=route, normals=normals,
+                                              min_faces=min_faces, min_extent=min_extent, keep_largest=keep_largest, report=report,
+                                              cameras=cameras, min_views=min_views, view_bias=view_bias, view_far=view_far,
+                                              simplify=simplify, colors=paint)
         return meshing.extract_scene_mesh(self.feature_tables, self.resolution, self.params, self.block_corner, self.block_size,
                                           self.occupied_grid, self.grid_starts, self.grid_log2dim, corner, size,
                                           meshing.cells_per_axis(size, cells_per_axis), level, route=route, normals=normals,
@@ -317,6 +337,43 @@ class TileSetRenderer:
         return evaluation.compare_meshes((mesh.vertices, mesh.faces), gt, n_samples, thresholds, max_dist=max_dist, seed=seed,
                                          log2dim=log2dim, return_distances=return_distances, device=mesh.vertices.device,
                                          normals=normals)
+
+    @torch.no_grad()
+    def color_mesh(self, mesh, cameras, which="diffuse", scale=1, max_transparency=0.5, views_per_batch=8, min_cos=0.0, bias=None,
+                   normals="mesh", far=float("inf"), fill=(0.5, 0.5, 0.5), log2dim=6, route="fused", report=None, **render_kw):
+        """Vertex colours for any mesh of this scene from the field's own renders: cameras = (ks, c2ws, H, W) are
+        rendered exactly as fuse_mesh / score_mesh render them (H // scale x W // scale, K scaled, render_kw to render;
+        which="diffuse": clamp(diffuse), "rgb": clamp(diffuse + specular)), views_per_batch at a time, and each batch is projected
+        onto the vertices while it is held (meshing.ViewColors: the mesh occludes itself, bilinear samples, cosine weights with the
+        mesh's normals).  mesh: a meshing.Mesh or anything with .vertices / .faces on this device.  bias: how far towards the eye a
+        segment starts, so that a vertex's own faces do not hide it: None takes half the mean edge length (meshing.default_edge_bias);
+        extract_mesh passes the extractors' view_bias (half a lattice spacing by default).  far: the cameras' range.
+        -> (rgb [V,3] f32, valid [V] bool); report receives count_histogram and invalid."""
+        from . import fusion, meshing
+        if which not in ("diffuse", "rgb"):
+            raise RuntimeError(f"scanerf: which must be 'diffuse' or 'rgb', got {which!r}")
+        if cameras is None or len(cameras) != 4:
+            raise RuntimeError("scanerf: color_mesh needs cameras=(ks, c2ws, H, W)")
+        ks, c2ws, H, W = cameras
+        scale = fusion._positive_int(scale, "scale")
+        vpb = fusion._views_per_batch(views_per_batch)
+        H, W = fusion._positive_int(H, "H"), fusion._positive_int(W, "W")
+        h, w = H // scale, W // scale
+        if h < 1 or w < 1:
+            raise RuntimeError(f"scanerf: H={H} W={W} leave no pixel at scale={scale}")
+        if not 0.0 <= float(max_transparency) <= 1.0:
+            raise RuntimeError(f"scanerf: max_transparency must lie in [0, 1], got {max_transparency!r}")
+        ks = fusion.scale_cameras(ks, scale)
+        c2ws = torch.as_tensor(c2ws).to(torch.float32)
+        if c2ws.dim() != 3 or c2ws.shape[0] != ks.shape[0] or c2ws.shape[1] < 3 or c2ws.shape[2] != 4:
+            raise RuntimeError(f"scanerf: c2ws must be [C,3,4] (or [C,4,4]) with C={ks.shape[0]}, got {tuple(c2ws.shape)}")
+        if bias is None:
+            bias = meshing.default_edge_bias(mesh)
+        blend = meshing.ViewColors(mesh, float(bias), normals, 0.0, far, min_cos, fill, log2dim, route)
+        if not blend.empty:
+            for i, _, images, _ in self._scene_batches(ks, c2ws, h, w, vpb, which, float(max_transparency), render_kw):
+                blend.add(images, ks[i:i + vpb], c2ws[i:i + vpb])
+        return blend.result(report)
 
     def _scene_batches(self, ks, c2ws, h, w, vpb, colors, max_transparency, render_kw, normals=False):
         """The scene rendered at cameras ks / c2ws (already scaled) at h x w, vpb at a time -> an iterator of (first index, depth maps
